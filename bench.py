@@ -16,12 +16,17 @@ batched spiral (4096 x 2, rk4 x 100: launch-bound), --config c3b BASELINE config
 all-reduce per step attempt when sharded), --config c5 the Burgers IMEX shard (64 x 1024 fp64 per GPU, ARKIMEX 3 + ksponly +
 batched LU; --strong: 512 global).  --dtype f64 runs c3a / c2 / c3b in the reference's CI precision.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
 Without WORLD_SIZE in the environment `--gpus N` (N > 1) starts the N ranks itself (fresh child processes
 under torch.distributed.run; this process never touches a GPU) and fails if the box has fewer GPUs.
+
+A plain run sets up, warms up, times the --steps solves and prints the headline line (`roofline`, `variants`,
+`cpu_baseline` null).  --full adds everything else the line can carry: the roofline pass and its profiler children,
+the copy-ceiling microbenchmark, the variants, the collectives timed alone and the CPU baseline (each still switched
+off by its own --no-* option).  --dump-outputs DIR writes what the last timed solve returned to its caller as .npy files.
 
 Rank 0 prints ONE JSON line.  `roofline` covers the solver kernels (the pn_* entry points:
 stage AXPYs, adjoint cotangents, lambda update AND the parameter-sensitivity accumulation -- SURVEY
@@ -48,6 +53,7 @@ MFMA_F32_PEAK_TFLOPS = 157.3    # dense fp32-input MFMA (v_mfma_f32_32x32x2_f32:
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA (the guide: ~2.5 PFLOP/s; AMD's headline figure includes 2:1 sparsity)
 MFMA_F64_PEAK_TFLOPS = 78.6     # fp64 matrix (v_mfma_f64_16x16x4_f64): AMD's MI355X data sheet (the guide does not list an fp64 MFMA rate)
 ALG_VECTORS_PER_STEP = 32       # rk4 fwd (15) + adjoint (17) vector moves per step
+DUMP_OUTPUTS_BYTES = 64 << 20   # --dump-outputs: at most this many bytes of .npy data
 
 
 def parse():
@@ -104,8 +110,17 @@ def parse():
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="an engine option for every solver of the run (A/B experiments; e.g. --opt pn_linear_side_stream=0); "
                          "the headline is the run WITHOUT any")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: roofline pass and profiler children, copy ceiling, "
+                         "variants, collectives timed alone, CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", dest="dump_outputs",
+                    help="after the timed steps: what the last timed solve returned (states at the output times, dL/dy0, "
+                         "dL/dtheta of every parameter, the loss) as DIR/<name>.npy in float32 / float64, rank 0's shard, at most "
+                         "%d MB in all (a fixed seeded sample of an array that does not fit)" % (DUMP_OUTPUTS_BYTES >> 20))
     a = ap.parse_args()
     a.opt = dict(kv.split("=", 1) for kv in a.opt)
+    if not a.full:
+        a.no_cpu_baseline = a.no_variants = a.no_pmc = a.no_rocprof = a.no_roofline_pass = a.no_ceiling = True
     if a.config in ("c3a", "c3b"):
         a.batch = a.batch or 4096
         a.nt = a.nt or 100
@@ -647,6 +662,25 @@ def pmc_traffic(args):
                      "pn_linear_wgrad kernels excluded from the average; all of them are listed in per_kernel)"}
 
 
+def write_outputs(directory, arrays, torch):
+    """--dump-outputs: [(name, tensor)] -> directory/<name>.npy, float64 tensors as float64, every other dtype as float32.
+    The smaller arrays are written whole; one that does not fit into its share of what the budget has left is written as
+    a 1-D sample at fixed, seeded positions (the same positions on every run of the same shapes)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = [(name, t.detach() if t.dtype == torch.float64 else t.detach().float()) for name, t in arrays]
+    left = DUMP_OUTPUTS_BYTES - 4096 * len(arrays)              # (room for the .npy headers)
+    for i, (name, t) in enumerate(sorted(arrays, key=lambda nt: nt[1].numel())):
+        share = left // (len(arrays) - i)
+        if t.numel() * t.element_size() > share:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=share // t.element_size(), replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            sys.stderr.write("bench: --dump-outputs: %s is a seeded sample of %d elements\n" % (name, t.numel()))
+        a = t.cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -740,6 +774,8 @@ def main():
         o._bench_opts, o._bench_kw, o._bench_pb = opts, kw, q
         return o
 
+    last = {}                                         # --dump-outputs: what the latest solve returned to its caller
+
     def one_solve(o):
         q = o._bench_pb
         for par in q.params:
@@ -753,6 +789,8 @@ def main():
         out = o.odeint_adjoint(y, q.t)
         loss = out.abs().mean()
         loss.backward()
+        if args.dump_outputs:
+            last.update(out=out.detach(), y=y, loss=loss.detach())
         return loss
 
     def sync():
@@ -821,6 +859,13 @@ def main():
     for _ in range(args.warmup):
         one_solve(ode)
     elapsed = timed(ode, args.steps)
+    if args.dump_outputs and rank == 0:
+        if not last:
+            raise SystemExit("bench.py: --dump-outputs needs at least one timed step")
+        grads = [("dtheta.%s.%s" % (mname, pname), par.grad if par.grad is not None else torch.zeros_like(par))
+                 for mname, m in (("func", pb.func), ("func2", pb.func2)) if m is not None
+                 for pname, par in m.named_parameters() if par.requires_grad]
+        write_outputs(args.dump_outputs, [("out", last["out"]), ("dy0", last["y"].grad), ("loss", last["loss"])] + grads, torch)
     if pb.adaptive and not mode.startswith("eager("):
         mode = ode.graph_status                       # (an adaptive solve over a sharded batch stays with eager launches)
     head_rep_ms = sorted(rep_ms)
@@ -888,7 +933,7 @@ def main():
     # ---- the collectives of the path, timed alone: the all-reduce of dL/dtheta after every backward and, for
     # an adaptive scheme, the two-double all-reduce (+ read-back) every step attempt makes so that all ranks take the same step
     allreduce_us = enorm_allreduce_us = None
-    if world > 1:
+    if world > 1 and args.full:
         flat = torch.zeros(max(sum(q.numel() for q in pb.params), 1), device=dev, dtype=pb.dtype)
         for _ in range(3):
             dist.all_reduce(flat)

@@ -118,3 +118,26 @@ def test_measured_traffic_keeps_the_mfma_bound_kernel_out_of_the_hbm_average(mon
     wg = t["per_kernel"]["pn_linear_wgrad_kernel"]
     assert wg["launches"] == 16 and wg["read_bytes"] == 2 * 12288 * 1024 and wg["write_bytes"] == 8448 * 1024
     assert "pn_linear_wgrad" in t["units"]
+
+
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_a_large_one_the_same_way_every_time(tmp_path, monkeypatch):
+    """--dump-outputs: float64 stays float64, other dtypes become float32; an array that does not fit into the budget is
+    written as a fixed, seeded sample, and the files stay within the budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_OUTPUTS_BYTES", 1 << 20)
+    big = torch.arange(1 << 20, dtype=torch.float32)
+    arrays = [("big", big), ("small", torch.ones(3, 4, dtype=torch.float64)), ("half", torch.ones(5, dtype=torch.float16)),
+              ("loss", torch.tensor(0.5, dtype=torch.float32))]
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays, torch)
+    a = {f: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(a) == ["big.npy", "half.npy", "loss.npy", "small.npy"]
+    assert a["small.npy"].dtype == np.float64 and a["small.npy"].shape == (3, 4)
+    assert a["half.npy"].dtype == np.float32 and a["loss.npy"].shape == () and float(a["loss.npy"]) == 0.5
+    s = a["big.npy"]
+    assert s.ndim == 1 and 0 < s.size < (1 << 18) and np.all(np.diff(s) > 0) and np.all(s == np.round(s))
+    assert np.array_equal(s, np.load(str(tmp_path / "b" / "big.npy")))
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in a) <= 1 << 20

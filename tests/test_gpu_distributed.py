@@ -107,7 +107,7 @@ def test_bench_contract_with_two_ranks(strong):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "256", "--dim", "64", "--nt", "6",
-           "--no-cpu-baseline", "--no-variants"] + (["--strong"] if strong else [])
+           "--full", "--no-cpu-baseline", "--no-variants"] + (["--strong"] if strong else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -184,7 +184,7 @@ def test_bench_config_c4_line():
         pytest.skip("no HIP device in this container")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PN_BENCH_BACKEND")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c4", "--steps", "2", "--warmup", "1",
-                        "--batch", "16", "--no-cpu-baseline", "--no-variants"],
+                        "--batch", "16", "--full", "--no-cpu-baseline", "--no-variants"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -217,7 +217,7 @@ def test_bench_two_ranks_on_the_configs_that_add_a_collective_or_name_eight_gpus
         pytest.skip("no HIP device in this container")
     launcher = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port())]
-    d = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--config", config, "--no-cpu-baseline", "--no-variants"] + extra,
+    d = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--config", config, "--full", "--no-cpu-baseline", "--no-variants"] + extra,
                    env={"PN_BENCH_BACKEND": "gloo"}, launcher=launcher)
     assert d["n_gpus"] == 2 and d["unit"] == "time-steps/s" and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert d["config"]["allreduce_us"] > 0 and d["cpu_baseline"] is None
@@ -239,7 +239,7 @@ def test_bench_single_rank_configs_and_the_measured_parts_of_the_line(config, ex
     the same solve in the reference's CI precision (`variants.f64`) with its own roofline."""
     if not torch.cuda.is_available():
         pytest.skip("no HIP device in this container")
-    d = _run_bench(["--steps", "3", "--warmup", "1", "--config", config, "--no-cpu-baseline"] + extra +
+    d = _run_bench(["--steps", "3", "--warmup", "1", "--config", config, "--full", "--no-cpu-baseline"] + extra +
                    ([] if config == "c3a" else ["--no-ceiling"]))
     assert d["n_gpus"] == 1 and d["metric"].startswith("time-steps/sec") and d["higher_is_better"] is True
     # SURVEY 8(d)(i): per-solve HIP-event durations and their median beside the contract's wall clock
@@ -296,6 +296,27 @@ def test_bench_single_rank_configs_and_the_measured_parts_of_the_line(config, ex
         assert "roofline" not in v or 0 < v["roofline"]["frac"] < 1.5
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone (no roofline pass, profiler children, variants or CPU baseline);
+    --dump-outputs writes what the last timed solve returned, the same arrays on a second run with the same arguments."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device in this container")
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "256", "--dim", "64", "--nt", "6"]
+    runs = []
+    for i in range(2):
+        d = _run_bench(argv + ["--dump-outputs", str(tmp_path / str(i))])
+        assert d["steps"] == 3 and d["median"]["reps"] == 3 and d["dtype"] == "f32" and d["unit"] == "time-steps/s"
+        assert d["value"] == pytest.approx(6 * 3 / (d["ms_per_step"] * 3 / 1e3), rel=1e-6)
+        assert d["roofline"] is None and d["variants"] is None and d["cpu_baseline"] is None
+        runs.append({f: np.load(str(tmp_path / str(i) / f)) for f in os.listdir(str(tmp_path / str(i)))})
+    a, b = runs
+    assert sorted(a) == sorted(b) and {"out.npy", "dy0.npy", "loss.npy"} <= set(a) and len(a) == 3 + 8
+    assert a["out.npy"].shape == (1, 256, 64) and a["dy0.npy"].shape == (256, 64) and a["out.npy"].dtype == np.float32
+    for f in a:
+        assert np.all(np.isfinite(a[f])) and np.allclose(a[f], b[f], rtol=1e-6, atol=0), f
+
+
 def test_bench_config_c3b_stiff_line():
     """bench.py --config c3b --stiff through the same contract: the adaptive workload that adapts -- more
     than 100 accepted steps, rejections, eager launches, a roofline over the error-norm kernel's launches."""
@@ -305,7 +326,7 @@ def test_bench_config_c3b_stiff_line():
         pytest.skip("no HIP device in this container")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PN_BENCH_BACKEND")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c3b", "--stiff", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-variants", "--no-rocprof", "--no-pmc"],
+                        "--full", "--no-cpu-baseline", "--no-variants", "--no-rocprof", "--no-pmc"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -328,7 +349,7 @@ def test_bench_eight_ranks_sharing_the_device_shards_concatenate_to_the_one_rank
     import subprocess
     if not torch.cuda.is_available():
         pytest.skip("no HIP device in this container")
-    common = ["--steps", "2", "--warmup", "1", "--strong", "--no-cpu-baseline", "--no-variants", "--no-rocprof", "--no-pmc", "--no-ceiling"]
+    common = ["--steps", "2", "--warmup", "1", "--strong", "--full", "--no-cpu-baseline", "--no-variants", "--no-rocprof", "--no-pmc", "--no-ceiling"]
     cases = {"c3a": ["--config", "c3a", "--batch", "512", "--dim", "64", "--nt", "6"],
              "c4": ["--config", "c4", "--batch", "1024", "--hw", "4", "--nt", "2"],
              "c3b": ["--config", "c3b", "--batch", "512", "--dim", "32"]}

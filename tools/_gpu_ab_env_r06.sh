@@ -5,7 +5,7 @@ mkdir -p $O; cd $R
 mapfile -t ARMS
 for round in 1 2 ${ROUNDS:-}; do
   for i in "${!ARMS[@]}"; do
-    env ${ARMS[$i]} timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-variants --no-pmc --no-ceiling 2>/dev/null | python -c "
+    env ${ARMS[$i]} timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-variants --no-pmc --no-ceiling 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 lw = d['roofline'].get('linear_wgrad') or {}

@@ -12,7 +12,7 @@ python3 $R/tools/trace_stats.py /tmp/p_graph $O/r06_graph_timed_region.csv --las
 unset DEBUG_CLR_GRAPH_PACKET_CAPTURE
 cd $R
 bash tools/_gpu_pmc_wgrad.sh > /dev/null 2>&1; cp gpurun_out/pmc_wgrad/r06_pmc_wgrad.txt $O/
-timeout 1200 python bench.py > $O/r06_bench.json 2> $O/r06_bench.err; echo "rc $?" >> $O/r06_bench.err
-for i in 1 2 3; do timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-variants >> $O/r06_bench_repeat.jsonl 2>> $O/r06_bench_repeat.err; done
+timeout 1200 python bench.py --full > $O/r06_bench.json 2> $O/r06_bench.err; echo "rc $?" >> $O/r06_bench.err
+for i in 1 2 3; do timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-variants >> $O/r06_bench_repeat.jsonl 2>> $O/r06_bench_repeat.err; done
 timeout 900 python tools/fuzz_modes.py 60 6 > $O/fuzz_modes.txt 2>&1; tail -1 $O/fuzz_modes.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1

@@ -17,7 +17,7 @@ cp $(find /tmp/p_graph -name "*kernel_stats.csv" | head -1) $O/r02_graph_run_ker
 python3 $R/tools/trace_stats.py /tmp/p_graph $O/r02_graph_timed_region.csv --last-solves 10 --total-solves 15 --time-steps 100 --label "bench.py --steps 10 --warmup 2 (default: hipGraph replay, tapes retained): the 10 timed replays only" > /dev/null
 # (3) the default command as the driver runs it (graph region + eager event pass + variants)
 rm -rf /tmp/p_default
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_default -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/default_bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_default -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/default_bench_under_rocprof.log 2>&1
 cp $(find /tmp/p_default -name "*kernel_stats.csv" | head -1) $O/r02_default_kernel_stats.csv
 # (4) PMC: HBM bytes (separate passes), then L2 hit/miss
 rm -rf /tmp/pmc_f /tmp/pmc_w /tmp/pmc_l2
@@ -40,7 +40,7 @@ for n, c in sorted(per.items()):
     print("%-60s launches %4d  hit %.3e  miss %.3e  hit rate %.3f" % (n[:60], len(c.get("TCC_HIT_sum", [])), h, m, h / max(h + m, 1)))
 PY
 # (5) un-profiled bench lines for reference
-python3 $R/bench.py --steps 10 --warmup 3 > $O/r02_bench.json 2> $O/r02_bench.err
-python3 $R/bench.py --config c4 --steps 10 --warmup 3 > $O/r02_bench_c4.json 2> $O/r02_bench_c4.err
+python3 $R/bench.py --full --steps 10 --warmup 3 > $O/r02_bench.json 2> $O/r02_bench.err
+python3 $R/bench.py --full --config c4 --steps 10 --warmup 3 > $O/r02_bench_c4.json 2> $O/r02_bench_c4.err
 tail -3 $O/*.log | tail -40
 ls -la $O

@@ -31,8 +31,8 @@ timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_graph
 cp $(find /tmp/p_graph -name "*kernel_stats.csv" | head -1) $O/r03_graph_run_kernel_stats.csv
 python3 $R/tools/trace_stats.py /tmp/p_graph $O/r03_graph_timed_region.csv --last-solves 10 --total-solves 15 --time-steps 100 --label "bench.py --steps 10 --warmup 2 (default: hipGraph replay, tapes retained): the 10 timed replays only" > /dev/null
 cd $R
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/r03_bench.json 2> $O/r03_bench.err; echo "rc $?" >> $O/r03_bench.err
-for c in c2 c3b c4 c5; do timeout 900 python bench.py --config $c --steps 5 --warmup 2 > $O/r03_bench_$c.json 2> $O/r03_bench_$c.err; echo "rc $?" >> $O/r03_bench_$c.err; done
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r03_bench.json 2> $O/r03_bench.err; echo "rc $?" >> $O/r03_bench.err
+for c in c2 c3b c4 c5; do timeout 900 python bench.py --full --config $c --steps 5 --warmup 2 > $O/r03_bench_$c.json 2> $O/r03_bench_$c.err; echo "rc $?" >> $O/r03_bench_$c.err; done
 # (5) host overhead of eager launches
 timeout 300 python tools/host_overhead.py > $O/r03_host_overhead.txt 2>&1
 timeout 300 python tools/profile_host_noop.py > $O/r03_profile_host_noop.txt 2>&1

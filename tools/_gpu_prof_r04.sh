@@ -17,9 +17,9 @@ cp $(find /tmp/p_graph -name "*kernel_stats.csv" | head -1) $O/r04_graph_run_ker
 python3 $R/tools/trace_stats.py /tmp/p_graph $O/r04_graph_timed_region.csv --last-solves 10 --total-solves 16 --time-steps 100 --label "bench.py --steps 10 --warmup 2 (no launch option: -pn_graph_capture auto; tapes retained): the 10 timed replays only" > /dev/null
 cd $R
 # (3) bench lines of the final tree
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/r04_bench.json 2> $O/r04_bench.err; echo "rc $?" >> $O/r04_bench.err
-timeout 900 python bench.py --config c3b --stiff --steps 5 --warmup 2 > $O/r04_bench_c3b_stiff.json 2> $O/r04_bench_c3b_stiff.err; echo "rc $?" >> $O/r04_bench_c3b_stiff.err
-for c in c2 c3b c4 c5; do timeout 900 python bench.py --config $c --steps 5 --warmup 2 > $O/r04_bench_$c.json 2> $O/r04_bench_$c.err; echo "rc $?" >> $O/r04_bench_$c.err; done
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r04_bench.json 2> $O/r04_bench.err; echo "rc $?" >> $O/r04_bench.err
+timeout 900 python bench.py --full --config c3b --stiff --steps 5 --warmup 2 > $O/r04_bench_c3b_stiff.json 2> $O/r04_bench_c3b_stiff.err; echo "rc $?" >> $O/r04_bench_c3b_stiff.err
+for c in c2 c3b c4 c5; do timeout 900 python bench.py --full --config $c --steps 5 --warmup 2 > $O/r04_bench_$c.json 2> $O/r04_bench_$c.err; echo "rc $?" >> $O/r04_bench_$c.err; done
 # (4) host cost of eager launches: C++ step loops against the Python stage loop
 timeout 300 python tools/host_overhead.py > $O/r04_host_overhead.txt 2>&1
 # (5) C5 shard, theta methods: the captured product in the eager path's arithmetic form (default) and with the double-VJP form forced

@@ -20,10 +20,10 @@ timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stiff
 python3 $R/tools/trace_stats.py /tmp/p_stiff $O/r05_c3b_stiff_trace_stats.csv --label "rocprofv3 --kernel-trace --stats -- python3 bench.py --config c3b --stiff --steps 3 --warmup 1, whole run" > /dev/null
 cd $R
 # (4) bench lines of the final tree
-timeout 900 python bench.py > $O/r05_bench.json 2> $O/r05_bench.err; echo "rc $?" >> $O/r05_bench.err
-timeout 900 python bench.py --config c3b --stiff --steps 5 --warmup 2 > $O/r05_bench_c3b_stiff.json 2> $O/r05_bench_c3b_stiff.err; echo "rc $?" >> $O/r05_bench_c3b_stiff.err
-for c in c2 c3b c4 c5; do timeout 900 python bench.py --config $c --steps 5 --warmup 2 > $O/r05_bench_$c.json 2> $O/r05_bench_$c.err; echo "rc $?" >> $O/r05_bench_$c.err; done
-for i in 1 2 3; do timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-variants >> $O/r05_bench_repeat.jsonl 2>> $O/r05_bench_repeat.err; done
+timeout 900 python bench.py --full > $O/r05_bench.json 2> $O/r05_bench.err; echo "rc $?" >> $O/r05_bench.err
+timeout 900 python bench.py --full --config c3b --stiff --steps 5 --warmup 2 > $O/r05_bench_c3b_stiff.json 2> $O/r05_bench_c3b_stiff.err; echo "rc $?" >> $O/r05_bench_c3b_stiff.err
+for c in c2 c3b c4 c5; do timeout 900 python bench.py --full --config $c --steps 5 --warmup 2 > $O/r05_bench_$c.json 2> $O/r05_bench_$c.err; echo "rc $?" >> $O/r05_bench_$c.err; done
+for i in 1 2 3; do timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-variants >> $O/r05_bench_repeat.jsonl 2>> $O/r05_bench_repeat.err; done
 # (5) what the periodic re-validation costs: 230 timed replayed calls contain two re-validating calls (every 100th)
 timeout 900 python bench.py --steps 230 --warmup 5 --no-cpu-baseline --no-variants --no-rocprof --no-pmc --no-ceiling --no-roofline-pass > $O/r05_bench_230_steps.json 2> $O/r05_bench_230_steps.err
 # (6) robustness runs of the final tree

@@ -20,11 +20,11 @@ timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stiff
 python3 $R/tools/trace_stats.py /tmp/p_stiff $O/r06_c3b_stiff_trace_stats.csv --label "rocprofv3 --kernel-trace --stats -- python3 bench.py --config c3b --stiff --steps 3 --warmup 1, whole run" > /dev/null
 cd $R
 # (3) bench lines of the final tree
-timeout 1200 python bench.py > $O/r06_bench.json 2> $O/r06_bench.err; echo "rc $?" >> $O/r06_bench.err
-timeout 900 python bench.py --dtype f64 --no-variants --no-cpu-baseline > $O/r06_bench_f64.json 2> $O/r06_bench_f64.err; echo "rc $?" >> $O/r06_bench_f64.err
-timeout 900 python bench.py --config c3b --stiff --steps 5 --warmup 2 > $O/r06_bench_c3b_stiff.json 2> $O/r06_bench_c3b_stiff.err; echo "rc $?" >> $O/r06_bench_c3b_stiff.err
-for c in c2 c3b c4 c5; do timeout 900 python bench.py --config $c --steps 5 --warmup 2 > $O/r06_bench_$c.json 2> $O/r06_bench_$c.err; echo "rc $?" >> $O/r06_bench_$c.err; done
-for i in 1 2 3; do timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-variants >> $O/r06_bench_repeat.jsonl 2>> $O/r06_bench_repeat.err; done
+timeout 1200 python bench.py --full > $O/r06_bench.json 2> $O/r06_bench.err; echo "rc $?" >> $O/r06_bench.err
+timeout 900 python bench.py --full --dtype f64 --no-variants --no-cpu-baseline > $O/r06_bench_f64.json 2> $O/r06_bench_f64.err; echo "rc $?" >> $O/r06_bench_f64.err
+timeout 900 python bench.py --full --config c3b --stiff --steps 5 --warmup 2 > $O/r06_bench_c3b_stiff.json 2> $O/r06_bench_c3b_stiff.err; echo "rc $?" >> $O/r06_bench_c3b_stiff.err
+for c in c2 c3b c4 c5; do timeout 900 python bench.py --full --config $c --steps 5 --warmup 2 > $O/r06_bench_$c.json 2> $O/r06_bench_$c.err; echo "rc $?" >> $O/r06_bench_$c.err; done
+for i in 1 2 3; do timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-variants >> $O/r06_bench_repeat.jsonl 2>> $O/r06_bench_repeat.err; done
 # (4) robustness runs of the final tree
 timeout 900 python tools/fuzz_guard.py 100 5 24 > $O/r06_fuzz_guard.txt 2>&1
 timeout 1500 python tools/fuzz_modes.py 300 12 > $O/r06_fuzz_modes.txt 2>&1

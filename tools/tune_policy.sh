@@ -2,12 +2,13 @@
 # Runs bench.py once per load/store cache policy of the streaming kernels (PN_TUNE) on the GPU
 # box and prints the solver-kernel roofline of each.  Usage: tools/tune_policy.sh "cfg1" "cfg2" ...
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out
+OUT=${OUT:-tune_out}
+mkdir -p "$OUT"
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  PN_TUNE="$cfg" python bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > gpurun_out/tune_policy_$i.json
-  python - "$cfg" gpurun_out/tune_policy_$i.json <<'PY'
+  PN_TUNE="$cfg" python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT"/tune_policy_$i.json
+  python - "$cfg" "$OUT"/tune_policy_$i.json <<'PY'
 import json, sys
 cfg, f = sys.argv[1], sys.argv[2]
 d = json.load(open(f))
