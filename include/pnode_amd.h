@@ -69,6 +69,14 @@ int pn_tableau_get(const char *rk_type, pn_tableau *out);
  * any other string -> PETSc's default "3bs".  Returns the rk type name (static storage). */
 const char *pn_method_to_rk_type(const char *method);
 
+/* Continuous extension (dense output) of a tableau, for -pn_output_times interpolate (extension: PETSc's TSInterpolate
+ * for RK is not what the reference reaches; its time span forces a step onto every output time instead):
+ *   y(t_n + theta*h) = y_n + h * sum_j beta_j(theta) K_j,   beta_j(theta) = sum_{p < npow} P[j][p] theta^(p+1).
+ * Built for "3bs" (Bogacki-Shampine cubic, order 3), "4" (RK4's cubic, order 3) and "5dp" (Shampine's quartic, order 4);
+ * any other type fails with a message naming those three.  *order: the order of the extension. */
+#define PN_DENSE_MAX_POW 4
+int pn_tableau_dense(const char *rk_type, int *order, int *npow, double P[PN_MAX_STAGES][PN_DENSE_MAX_POW]);
+
 /* ------------------------------------------------------------------------------------------
  * 2. Device entry points.  `stream` is a hipStream_t.  `dtype` selects f32/f64 storage;
  *    coefficients are passed in double and rounded once to the storage type, as PETSc forms
@@ -254,6 +262,8 @@ pn_ts *pn_ts_create(void);
 void pn_ts_destroy(pn_ts *ts);
 int pn_ts_set_rk_type(pn_ts *ts, const char *rk_type);
 int pn_ts_get_tableau(const pn_ts *ts, pn_tableau *out);
+/* pn_tableau_dense for the RK type `ts` currently has. */
+int pn_ts_get_tableau_dense(const pn_ts *ts, int *order, int *npow, double P[PN_MAX_STAGES][PN_DENSE_MAX_POW]);
 /* Options database subset, PETSc spellings without the leading dash: ts_adapt_type
  * (none|basic), ts_rk_type, ts_rtol, ts_atol, ts_max_steps, ts_max_reject,
  * ts_adapt_safety, ts_adapt_reject_safety, ts_adapt_clip (lo,hi), ts_adapt_dt_min,
@@ -344,6 +354,32 @@ typedef int64_t (*pn_vjp_cb)(void *user, int stage, double t, int cot_in_w, doub
  * stage's cotangent while this stage's is written. */
 int pn_rk_adjoint_step(void *stream, int dtype, int64_t n, const pn_ts *ts, const pn_vec_ops *vec_ops, double t, double H,
                        void *lambda, void *wbuf, void *wbuf2, pn_vjp_cb cb, void *user, const void *forcing);
+/* pn_rk_adjoint_step for a step that holds interpolated outputs (-pn_output_times interpolate): dense_w[i] (NULL: none) is
+ * the cotangent D_i = sum_o h*beta_i(theta_o) g_o the step's outputs send to stage i (pn_rk_dense_adjoint), added to that
+ * stage's cotangent as one more source after the lambda / dlambda terms:
+ *   w_i = H b_i lambda + sum_j H a_ji dlambda_j + D_i.
+ * A stage with a D_i is never folded into lambda and is not structurally zero even when b_i == 0.  dense_w == NULL is
+ * pn_rk_adjoint_step.  The vector operations are those of vec_ops (adj_theta takes D_i as its last term). */
+int pn_rk_adjoint_step_dense(void *stream, int dtype, int64_t n, const pn_ts *ts, const pn_vec_ops *vec_ops, double t,
+                             double H, void *lambda, void *wbuf, void *wbuf2, pn_vjp_cb cb, void *user,
+                             const void *const *dense_w, const void *forcing);
+
+/* ------------------------------------------------------------------------------------------
+ * 3a'. Dense output kernels (csrc/pn_dense.hip; extension, -pn_output_times interpolate).  Extend pn_lincomb: ONE launch
+ *     for all the outputs of a step instead of one lincomb per output.  Coefficients travel as kernel arguments (no copy to
+ *     the device, capturable), at most PN_DENSE_CHUNK outputs per launch; larger m is split into several launches.
+ * ---------------------------------------------------------------------------------------- */
+#define PN_DENSE_CHUNK 32
+#define PN_DENSE_NONTEMPORAL 1      /* flags: the output rows are stored non-temporally */
+/* out[o*ld + e] = u[e] + sum_{j<nk} coef[o*nk + j] * K[j][e]   for o < m, e < n   (nk <= PN_MAX_STAGES)
+ * Replaces m pn_lincomb launches (bytes (nk+1)*m*n -> (nk+1+m)*n).  Summation order of pn_lincomb_kernel: u, then fma in j. */
+int pn_rk_dense_eval(void *stream, int dtype, int64_t n, const void *u, int nk, const void *const *K, int m,
+                     const double *coef, void *out, int64_t ld, int flags);
+/* The transpose, for the reverse sweep:  D[j][e] (+)= sum_{o<m} coef[o*nd + j] * g[o*ld + e]   for j < nd (<= PN_MAX_STAGES),
+ * G[e] (+)= sum_o g[o*ld + e] (G may be NULL).  accumulate: start from the D / G already there (else from the first row).
+ * Fixed order (o ascending, fma), no atomics: bit-reproducible; a split into chunks gives the same bits. */
+int pn_rk_dense_adjoint(void *stream, int dtype, int64_t n, int m, const void *g, int64_t ld, int nd, const double *coef,
+                        void *const *D, void *G, int accumulate);
 
 /* ------------------------------------------------------------------------------------------
  * 3b. GMRES core for the implicit (theta-method) stage solves: the small dense part of

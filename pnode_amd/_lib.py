@@ -46,6 +46,9 @@ PN_WGRAD_MAX_PAIRS = 8
 PN_WGRAD_EXACT_FP32 = 1
 PN_WGRAD_TILE_64 = 2
 PN_ABI_VERSION = 4
+PN_DENSE_MAX_POW = 4          # columns of a continuous extension's P matrix (pn_tableau_dense)
+PN_DENSE_CHUNK = 32           # output rows per launch of pn_rk_dense_eval / pn_rk_dense_adjoint
+PN_DENSE_NONTEMPORAL = 1
 _vp, _i, _i64, _d, _cp = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_char_p
 _pd, _pi, _pi64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)
 _pvp = ctypes.POINTER(ctypes.c_void_p)
@@ -69,6 +72,11 @@ class VecOps(ctypes.Structure):
 PROTOTYPES = {
     "pn_rk_attempt": (_i, [_vp, _i, _i64, _vp, _vp, _d, _d, _vp, _vp, _pvp, _vp, _i, _d, STAGE_CB, _vp, _i, _vp, _vp, _pvp]),
     "pn_rk_adjoint_step": (_i, [_vp, _i, _i64, _vp, _vp, _d, _d, _vp, _vp, _vp, VJP_CB, _vp, _vp]),
+    "pn_rk_adjoint_step_dense": (_i, [_vp, _i, _i64, _vp, _vp, _d, _d, _vp, _vp, _vp, VJP_CB, _vp, _pvp, _vp]),
+    "pn_rk_dense_eval": (_i, [_vp, _i, _i64, _vp, _i, _pvp, _i, _pd, _vp, _i64, _i]),
+    "pn_rk_dense_adjoint": (_i, [_vp, _i, _i64, _i, _vp, _i64, _i, _pd, _pvp, _vp, _i]),
+    "pn_tableau_dense": (_i, [_cp, _pi, _pi, _pd]),
+    "pn_ts_get_tableau_dense": (_i, [_vp, _pi, _pi, _pd]),
     "pn_last_error": (_cp, []),
     "pn_abi_version": (_i, []),
     "pn_tableau_get": (_i, [_cp, ctypes.POINTER(Tableau)]),
@@ -188,6 +196,24 @@ def dtype_code(dtype):
     if dtype == torch.float64:
         return PN_F64
     raise TypeError("pnode_amd supports float32 and float64 states, got %s" % dtype)
+
+
+def _dense(fn, arg):
+    order, npow = ctypes.c_int(), ctypes.c_int()
+    P = (ctypes.c_double * (PN_MAX_STAGES * PN_DENSE_MAX_POW))()
+    check(fn(arg, ctypes.byref(order), ctypes.byref(npow), P))
+    return order.value, [[P[j * PN_DENSE_MAX_POW + p] for p in range(npow.value)] for j in range(PN_MAX_STAGES)]
+
+
+def get_tableau_dense(rk_type):
+    """(order, P) of the continuous extension of `rk_type` (pn_tableau_dense): beta_j(theta) = sum_p P[j][p] theta^(p+1);
+    P has PN_MAX_STAGES rows.  PnError for a tableau without one."""
+    return _dense(load().pn_tableau_dense, rk_type.encode())
+
+
+def ts_tableau_dense(ts):
+    """get_tableau_dense for the RK type a pn_ts handle has (pn_ts_get_tableau_dense)."""
+    return _dense(load().pn_ts_get_tableau_dense, ts)
 
 
 def get_tableau(rk_type):

@@ -395,7 +395,7 @@ class RKSweep(object):
             gp.append(g)
         return gy, gp
 
-    def _adjoint_steps(self, nsteps, forcing):
+    def _adjoint_steps(self, nsteps, forcing, dense_w=None):
         """TSAdjointSolve over `nsteps` steps, newest first (TSAdjointStep_RK per step), then
         add `forcing` (dL/dy at the span point reached; pa.py:938) fused into the last update.
 
@@ -408,7 +408,10 @@ class RKSweep(object):
         (the scale PETSc applies after MatMultTranspose is applied to the cotangent instead).
         A stage whose cotangent is a pure multiple of lambda -- the last non-trivial stage of
         every tableau -- is differentiated with lambda itself and the scalar is folded into
-        the coefficients of everything that consumes its result: no kernel, no extra vector."""
+        the coefficients of everything that consumes its result: no kernel, no extra vector.
+
+        `dense_w` (-pn_output_times interpolate, one step): per stage the cotangent D_i its interpolated outputs send it, or
+        None; added to w_i as the last term (a stage with a D_i is always formed, pn_rk_adjoint_step_dense)."""
         if self._theta is not None:
             return self._theta.adjoint_steps(nsteps, forcing)
         ops, s_eff, A, b = self._ops, self._s_eff, self._A, self._b
@@ -434,10 +437,17 @@ class RKSweep(object):
                     self._make_callbacks()
                 self._rcbs = (Y, tapes, dlam, self._first_stage_time(step))
                 fo = forcing if r == nsteps - 1 else None
-                rc = self._lib.pn_rk_adjoint_step(ops.stream(), ops.code, self.n, self._ts, ops.vec_ops, tn, H, lam.data_ptr(),
-                                                  self._buf("w_a").data_ptr(), self._buf("w_b").data_ptr() if two_w else None,
-                                                  self._vjp_cb_c, None,
-                                                  None if fo is None else fo.data_ptr())
+                if dense_w is not None:
+                    dw = (ctypes.c_void_p * _lib.PN_MAX_STAGES)(*[None if d is None else d.data_ptr() for d in dense_w])
+                    rc = self._lib.pn_rk_adjoint_step_dense(ops.stream(), ops.code, self.n, self._ts, ops.vec_ops, tn, H,
+                                                            lam.data_ptr(), self._buf("w_a").data_ptr(),
+                                                            self._buf("w_b").data_ptr() if two_w else None, self._vjp_cb_c, None,
+                                                            dw, None if fo is None else fo.data_ptr())
+                else:
+                    rc = self._lib.pn_rk_adjoint_step(ops.stream(), ops.code, self.n, self._ts, ops.vec_ops, tn, H, lam.data_ptr(),
+                                                      self._buf("w_a").data_ptr(), self._buf("w_b").data_ptr() if two_w else None,
+                                                      self._vjp_cb_c, None,
+                                                      None if fo is None else fo.data_ptr())
                 self._rcbs = None
                 if rc:
                     self._raise_from_loop(rc)
@@ -453,15 +463,17 @@ class RKSweep(object):
             nw = 0
             for i in range(s_eff - 1, -1, -1):
                 js = [j for j in range(i + 1, s_eff) if A[j][i] != 0.0 and dlam[j] is not None]
-                if b[i] == 0.0 and not js:
+                di = dense_w[i] if dense_w is not None else None
+                if b[i] == 0.0 and not js and di is None:
                     continue                   # structurally zero cotangent
-                if not js:
+                if not js and di is None:
                     w, scale[i] = lam, H * b[i]
                 else:
                     w = self._buf("w_b" if (two_w and nw % 2) else "w_a")
                     nw += 1
                     ops.adj_theta(w, lam if b[i] != 0.0 else None, H * b[i],
-                                  [dlam[j] for j in js], [H * A[j][i] * scale[j] for j in js])
+                                  [dlam[j] for j in js] + ([di] if di is not None else []),
+                                  [H * A[j][i] * scale[j] for j in js] + ([1.0] if di is not None else []))
                 # (stage 0 of a first-same-as-last tableau was evaluated at the previous step's last stage time, which is
                 # t_n only to the last bit: the VJP differentiates f THERE, with and without a tape -- the exact discrete
                 # adjoint, the same bits in every checkpoint mode for a time-dependent f; PETSc passes t_n)
@@ -635,11 +647,85 @@ class RKSweep(object):
             return self._reverse_sweep_impl(g, T)
 
     def _reverse_sweep_impl(self, g, T):
+        if self._dense_active:
+            return self._reverse_sweep_dense(g, T)
         self._begin_adjoint(g[T - 1])
         if T == 1:
             self._adjoint_steps(self._nsteps, None)
         for i in range(T - 1, 0, -1):
             self._adjoint_steps(self.cur_sol_steps[i], g[i - 1])
+        self._flush_param_accum()
+        self._finish_linear_accum()
+
+    def _dense_rows(self, T):
+        """Per step n: (lo, hi, coefficient rows) -- the output times t_n <= t[o] < t_{n+1}, o < T-1, and per output h*beta_j(theta)
+        for every stage (None: the output IS the state at t_n).  From the step log and the output times only, as the forward sweep
+        classified them."""
+        times = self.sol_times.tolist()
+        N = self._nsteps
+        log = [self._step_info(k) for k in range(N)]
+        rows, o = [], 0
+        for k in range(N):
+            tn, h = log[k]
+            tend = log[k + 1][0] if k + 1 < N else times[T - 1]
+            lo = o
+            while o < T - 1 and times[o] < tend:
+                o += 1
+            rows.append((lo, o, [None if times[q] == tn else self._dense_coefs(times[q], tn, h) for q in range(lo, o)]))
+        return log, rows
+
+    def _reverse_sweep_dense(self, g, T):
+        """The reverse sweep of a solve with interpolated outputs: per reversed step n, its outputs' cotangents
+        g_o give D_j = sum_o h beta_j(theta_o) g_o (stage j's extra cotangent) and G = sum_o g_o (added to lambda_n in the closing
+        update, with the g of an output AT t_n).  First same as last: K_{s-1} of step n is K_0 of step n+1, so step n's column s-1
+        goes into D_0 of step n+1; for the last step, one extra VJP at (y_N, t_{N-1} + c_{s-1} h) before the sweep."""
+        ops, s = self._ops, self._s
+        self._begin_adjoint(g[T - 1])
+        log, rows = self._dense_rows(T)
+        N = len(rows)
+        fs = s - 1 if self._fsal else None
+        cols = [j for j in self._dense_cols if j != fs]
+
+        def interior(k):
+            return any(c is not None for c in rows[k][2])
+
+        def fsal_part(k):            # rows of step k and their column s-1
+            lo, hi, cf = rows[k]
+            return g[lo:hi], [[0.0 if c is None else c[fs]] for c in cf]
+
+        if fs is not None and N > 0 and interior(N - 1):
+            d = self._buf("dense_fsal")
+            gk, cf = fsal_part(N - 1)
+            ops.dense_adjoint([d], None, gk, cf)
+            tl, hl = log[N - 1]
+            gy, gp = self._vjp(tl + self._c[fs] * hl, self._buf("dense_yN"), d, None, alpha=1.0)
+            if gy is not None:
+                ops.adj_accum(self.adj_u_flat, self.adj_u_flat, [gy], [1.0], None)
+            if self.np > 0 and any(x is not None for x in gp):
+                if self._accum_mode == "stage":
+                    ops.param_accum(self.adj_p_tensor, 1.0, gp, self._poff, self._plen)
+                else:
+                    self._pend_a.append(1.0)
+                    self._pend_g.append(gp)
+        for k in range(N - 1, -1, -1):
+            lo, hi, cf = rows[k]
+            dw = [None] * _lib.PN_MAX_STAGES
+            G = None
+            if hi > lo:
+                G = self._buf("dense_G")
+                if interior(k):
+                    Ds = [self._buf("dense_d%d" % j) for j in cols]
+                    ops.dense_adjoint(Ds, G, g[lo:hi], [[0.0 if c is None else c[j] for j in cols] for c in cf])
+                    for j, d in zip(cols, Ds):
+                        dw[j] = d
+                else:
+                    ops.dense_adjoint([], G, g[lo:hi], [[] for _ in cf])
+            if fs is not None and k > 0 and interior(k - 1):
+                d0 = self._buf("dense_d0")
+                gk, cfk = fsal_part(k - 1)
+                ops.dense_adjoint([d0], None, gk, cfk, accumulate=dw[0] is not None)
+                dw[0] = d0
+            self._adjoint_steps(1, G, dense_w=dw if any(d is not None for d in dw) else None)
         self._flush_param_accum()
         self._finish_linear_accum()
 

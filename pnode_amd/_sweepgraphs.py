@@ -120,6 +120,11 @@ class SweepGraphs(object):
             if self._theta is None and self._sharded():
                 self._graph_status = "eager (adaptive steps over a batch that is sharded across ranks)"
             return None
+        if self._dense and not self._adaptive:
+            # (the dense-output launches depend on where the steps fall relative to the output times: not part of the captured
+            # fixed-step sweeps; per-evaluation graphs of adaptive sweeps capture func alone and stay available)
+            self._graph_status = "eager (-pn_output_times interpolate: whole-sweep hipGraphs are not built for dense output)"
+            return None
         auto = self._graph_mode == 2
         if auto and self._auto_veto:
             return None

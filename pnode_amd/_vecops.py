@@ -194,6 +194,26 @@ class HipVecOps(object):
         check(self.lib.pn_linear_wgrad_finish(self.stream(), self.code, out_f, in_f, pw.data_ptr(), None if pb is None else pb.data_ptr(),
                                               mu_w.data_ptr(), None if mu_b is None else mu_b.data_ptr()))
 
+    # ---- dense output (-pn_output_times interpolate; csrc/pn_dense.hip)
+    dense_flags = _lib.PN_DENSE_NONTEMPORAL      # output rows are not read again by the sweep: non-temporal stores
+
+    def dense_eval(self, out, u, Ks, coefs):
+        """out[o] = u + sum_j coefs[o][j]*Ks[j] for every row o of the 2-D view `out` (rows of the solution tensor): ONE launch
+        per PN_DENSE_CHUNK rows (pn_rk_dense_eval)."""
+        m, nk = len(coefs), len(Ks)
+        c = (ctypes.c_double * (m * nk))(*[x for row in coefs for x in row])
+        check(self.lib.pn_rk_dense_eval(self.stream(), self.code, self.n, u.data_ptr(), nk, (ctypes.c_void_p * nk)(*[k.data_ptr() for k in Ks]),
+                                        m, c, out.data_ptr(), out.stride(0), self.dense_flags))
+
+    def dense_adjoint(self, Ds, G, g, coefs, accumulate=False):
+        """Ds[j] (+)= sum_o coefs[o][j]*g[o], G (+)= sum_o g[o] (G may be None) over the rows of the 2-D view `g`, o ascending
+        (pn_rk_dense_adjoint)."""
+        m, nd = g.shape[0], len(Ds)
+        c = (ctypes.c_double * max(m * nd, 1))(*[x for row in coefs for x in row])
+        check(self.lib.pn_rk_dense_adjoint(self.stream(), self.code, self.n, m, g.data_ptr(), g.stride(0), nd, c,
+                                           (ctypes.c_void_p * max(nd, 1))(*[d.data_ptr() for d in Ds]),
+                                           None if G is None else G.data_ptr(), 1 if accumulate else 0))
+
     def copy(self, y, x):
         check(self.lib.pn_copy(self.stream(), self.code, self.n, y.data_ptr(), x.data_ptr()))
 

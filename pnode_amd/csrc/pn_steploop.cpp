@@ -92,9 +92,15 @@ int pn_rk_attempt(void *stream, int dtype, int64_t n, const pn_ts *ts, const pn_
   return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
 // TSAdjointStep_RK for one step [t, t+H]: lambda and (through the callback) mu are advanced to the start of the step.
-int pn_rk_adjoint_step(void *stream, int dtype, int64_t n, const pn_ts *ts, const pn_vec_ops *vec_ops, double t, double H,
-                       void *lambda, void *wbuf, void *wbuf2, pn_vjp_cb cb, void *user, const void *forcing) {
+// dense_w (may be NULL): the cotangents the step's interpolated outputs send to its stages, one more source of w_i.
+int adjoint_step(void *stream, int dtype, int64_t n, const pn_ts *ts, const pn_vec_ops *vec_ops, double t, double H,
+                 void *lambda, void *wbuf, void *wbuf2, pn_vjp_cb cb, void *user, const void *const *dense_w,
+                 const void *forcing) {
   if (!ts || !lambda || !wbuf || !cb) return pn::fail("pn_rk_adjoint_step: null argument");
   pn_tableau T;
   if (pn_ts_get_tableau(ts, &T)) return 1;
@@ -103,18 +109,20 @@ int pn_rk_adjoint_step(void *stream, int dtype, int64_t n, const pn_ts *ts, cons
   const void *dl[PN_MAX_STAGES] = {nullptr};              // raw VJP results; the true dlambda_i is scale[i]*dl[i]
   double scale[PN_MAX_STAGES];
   for (int i = 0; i < PN_MAX_STAGES; ++i) scale[i] = 1.0;
-  const void *ptrs[PN_MAX_STAGES];
-  double coef[PN_MAX_STAGES];
+  const void *ptrs[PN_MAX_STAGES + 1];                    // (+1: the dense-output source)
+  double coef[PN_MAX_STAGES + 1];
   int nw = 0;                                             // cotangent buffers written so far in this step
   for (int i = s_eff - 1; i >= 0; --i) {
     int nk = 0;
     for (int j = i + 1; j < s_eff; ++j)
       if (T.A[j][i] != 0.0 && dl[j]) { ptrs[nk] = dl[j]; coef[nk] = H * T.A[j][i] * scale[j]; ++nk; }
-    if (T.b[i] == 0.0 && nk == 0) continue;               // structurally zero cotangent
+    const void *di = dense_w ? dense_w[i] : nullptr;
+    if (T.b[i] == 0.0 && nk == 0 && !di) continue;       // structurally zero cotangent
     int use_w = 0;
-    if (nk == 0) {
+    if (nk == 0 && !di) {
       scale[i] = H * T.b[i];                              // cotangent = lambda itself; the factor goes to the consumers
     } else {
+      if (di) { ptrs[nk] = di; coef[nk] = 1.0; ++nk; }    // the outputs' share comes last
       use_w = (wbuf2 && (nw & 1)) ? 2 : 1;                // the two cotangent buffers in turn
       ++nw;
       if (ops.adj_theta(stream, dtype, n, use_w == 2 ? wbuf2 : wbuf, T.b[i] != 0.0 ? lambda : nullptr, H * T.b[i], nk, ptrs, coef)) return 1;
@@ -127,6 +135,21 @@ int pn_rk_adjoint_step(void *stream, int dtype, int64_t n, const pn_ts *ts, cons
   for (int i = 0; i < s_eff; ++i)
     if (dl[i]) { ptrs[nk] = dl[i]; coef[nk] = scale[i]; ++nk; }
   return ops.adj_accum(stream, dtype, n, lambda, lambda, nk, ptrs, coef, forcing, nullptr, 0.0);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pn_rk_adjoint_step(void *stream, int dtype, int64_t n, const pn_ts *ts, const pn_vec_ops *vec_ops, double t, double H,
+                       void *lambda, void *wbuf, void *wbuf2, pn_vjp_cb cb, void *user, const void *forcing) {
+  return adjoint_step(stream, dtype, n, ts, vec_ops, t, H, lambda, wbuf, wbuf2, cb, user, nullptr, forcing);
+}
+
+int pn_rk_adjoint_step_dense(void *stream, int dtype, int64_t n, const pn_ts *ts, const pn_vec_ops *vec_ops, double t,
+                             double H, void *lambda, void *wbuf, void *wbuf2, pn_vjp_cb cb, void *user,
+                             const void *const *dense_w, const void *forcing) {
+  return adjoint_step(stream, dtype, n, ts, vec_ops, t, H, lambda, wbuf, wbuf2, cb, user, dense_w, forcing);
 }
 
 }  // extern "C"

@@ -112,6 +112,53 @@ bool build_tableau(const std::string &name, pn_tableau &T) {
   return true;
 }
 
+// Continuous extensions (dense output): y(t_n + theta h) = y_n + h sum_j beta_j(theta) K_j with
+// beta_j(theta) = sum_p P[j][p] theta^(p+1).  3bs: Bogacki-Shampine's cubic; 5dp: Shampine's quartic for Dormand-Prince
+// (the published rationals, stage order as the tableaus above); 4: the cubic Hermite extension of classical RK4.
+struct DenseRow {
+  int j, p;
+  double num, den;
+};
+
+bool build_dense(const std::string &name, int *order, int *npow, double P[PN_MAX_STAGES][PN_DENSE_MAX_POW]) {
+  std::memset(P, 0, sizeof(double) * PN_MAX_STAGES * PN_DENSE_MAX_POW);
+  std::vector<DenseRow> rows;
+  if (name == "3bs") {
+    *order = 3; *npow = 3;
+    rows = {{0, 0, 1, 1}, {0, 1, -4, 3}, {0, 2, 5, 9},
+            {1, 1, 1, 1}, {1, 2, -2, 3},
+            {2, 1, 4, 3}, {2, 2, -8, 9},
+            {3, 1, -1, 1}, {3, 2, 1, 1}};
+  } else if (name == "4") {
+    *order = 3; *npow = 3;
+    rows = {{0, 0, 1, 1}, {0, 1, -3, 2}, {0, 2, 2, 3},
+            {1, 1, 1, 1}, {1, 2, -2, 3},
+            {2, 1, 1, 1}, {2, 2, -2, 3},
+            {3, 1, -1, 2}, {3, 2, 2, 3}};
+  } else if (name == "5dp") {
+    *order = 4; *npow = 4;
+    rows = {{0, 0, 1, 1}, {0, 1, -8048581381.0, 2820520608.0}, {0, 2, 8663915743.0, 2820520608.0},
+            {0, 3, -12715105075.0, 11282082432.0},
+            {2, 1, 131558114200.0, 32700410799.0}, {2, 2, -68118460800.0, 10900136933.0},
+            {2, 3, 87487479700.0, 32700410799.0},
+            {3, 1, -1754552775.0, 470086768.0}, {3, 2, 14199869525.0, 1410260304.0},
+            {3, 3, -10690763975.0, 1880347072.0},
+            {4, 1, 127303824393.0, 49829197408.0}, {4, 2, -318862633887.0, 49829197408.0},
+            {4, 3, 701980252875.0, 199316789632.0},
+            {5, 1, -282668133.0, 205662961.0}, {5, 2, 2019193451.0, 616988883.0}, {5, 3, -1453857185.0, 822651844.0},
+            {6, 1, 40617522.0, 29380423.0}, {6, 2, -110615467.0, 29380423.0}, {6, 3, 69997945.0, 29380423.0}};
+  } else {
+    return false;
+  }
+  for (const DenseRow &r : rows) P[r.j][r.p] = r.num / r.den;
+  return true;
+}
+
+int dense_fail(const std::string &name) {
+  return pn::fail("RK type '" + name + "' has no continuous extension here (-pn_output_times interpolate needs 3bs (bosh3), "
+                  "4 (rk4) or 5dp (dopri5))");
+}
+
 constexpr double kEps = std::numeric_limits<double>::epsilon();
 
 }  // namespace
@@ -187,6 +234,16 @@ int pn_ts_set_rk_type(pn_ts *ts, const char *rk_type) {
 int pn_ts_get_tableau(const pn_ts *ts, pn_tableau *out) {
   *out = ts->tab;
   return 0;
+}
+
+int pn_tableau_dense(const char *rk_type, int *order, int *npow, double P[PN_MAX_STAGES][PN_DENSE_MAX_POW]) {
+  if (!rk_type || !order || !npow || !P) return pn::fail("pn_tableau_dense: null argument");
+  if (!build_dense(rk_type, order, npow, P)) return dense_fail(rk_type);
+  return 0;
+}
+int pn_ts_get_tableau_dense(const pn_ts *ts, int *order, int *npow, double P[PN_MAX_STAGES][PN_DENSE_MAX_POW]) {
+  if (!ts) return pn::fail("pn_ts_get_tableau_dense: null argument");
+  return pn_tableau_dense(ts->rk_type.c_str(), order, npow, P);
 }
 
 static bool parse_double(const char *v, double *out) {

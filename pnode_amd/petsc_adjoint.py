@@ -95,6 +95,8 @@ class ODEPetsc(RKSweep, SweepGraphs):
         self._nsteps = 0
         self._tapes = None
         self._init_sweep_graphs()
+        self._dense = False            # -pn_output_times interpolate
+        self._dense_active = False     # ... and the last forward solve had output times inside its steps
         self._lin = None               # engine-side parameter sensitivities of func's nn.Linear layers (_lineargrad.py)
         self._pend_mixed = False
         self._sg = None                # the per-evaluation hipGraphs the sweep in progress replays (pnode_amd/_stagegraphs.py)
@@ -299,6 +301,13 @@ class ODEPetsc(RKSweep, SweepGraphs):
             elif ts_type in ("beuler", "cn", "theta", "rk") and stepper == "imex":
                 raise PnError("-ts_type %s cannot override an IMEX set-up (two functions were given)" % ts_type)
             self._stepper_kind = stepper
+            if self._dense:
+                if stepper:
+                    raise PnError("-pn_output_times interpolate is built for the explicit RK tableaus 3bs (bosh3), 4 (rk4) and 5dp "
+                                  "(dopri5); the theta / IMEX steppers take matched output times only")
+                self._dense_order, P = _lib.ts_tableau_dense(self._ts)        # PnError for a tableau without an extension
+                self._dense_P = P[: self._s]
+                self._dense_cols = [j for j in range(self._s) if any(v != 0.0 for v in P[j])]
             adapt_wanted = str(options.get_all().get("ts_adapt_type", "basic")) != "none"
             if stepper == "imex":
                 from .arkimex import ArkimexStepper
@@ -419,6 +428,14 @@ class ODEPetsc(RKSweep, SweepGraphs):
         self._revalidate_every = int(float(db.get("pn_graph_revalidate", self.GRAPH_REVALIDATE_EVERY)))
         if self._revalidate_every < 0:
             raise PnError("-pn_graph_revalidate must not be negative")
+        # not a PETSc option: how the output times t[1:-1] are produced
+        #   match (default): every output time ends a step (the reference's TSSetTimeSpan / MATCHSTEP)
+        #   interpolate: the stepper sees [t[0], t[-1]] only; outputs inside a step come from the tableau's continuous extension
+        om = str(db.get("pn_output_times", "match"))
+        if om not in ("match", "interpolate"):
+            raise PnError("-pn_output_times must be match or interpolate (got '%s')" % om)
+        self._dense = om == "interpolate"
+        self._dense_P = None
         for key, val in db.items():
             if key.startswith("ts_trajectory") or key in ("ts_monitor", "ts_view") or key.startswith("pn_"):
                 continue
@@ -526,6 +543,7 @@ class ODEPetsc(RKSweep, SweepGraphs):
             raise RuntimeError("setupTS must be called before odeint")
         if u0.size() != self.tensor_size or u0.dtype != self.tensor_dtype or u0.device != self.device:
             raise ValueError("u0 does not match the tensor given to setupTS (shape, dtype, device)")
+        self._dense_active = False
         if self._theta is not None:
             return self._theta.odeint(u0, t, save)
         lib, ops, ts = self._lib, self._ops, self._ts
@@ -533,10 +551,18 @@ class ODEPetsc(RKSweep, SweepGraphs):
         T = int(t.shape[0])
         times = self.sol_times.tolist()
         dt0 = float(self.step_size[0] if isinstance(self.step_size, list) else self.step_size)
-        check(lib.pn_ts_begin(ts, 0.0, dt0, T, (ctypes.c_double * T)(*times)))
-        self._span_begin(T)
+        # -pn_output_times interpolate: the stepper sees the end points only; t[1:-1] are filled by _dense_step
+        dense = self._dense_active = self._dense and T > 2
         solution = ops.empty((T,) + tuple(self.tensor_size))
         sol_flat = solution.view(T, -1)
+        if dense:
+            if any(not (b > a) for a, b in zip(times, times[1:])):
+                raise PnError("-pn_output_times interpolate: the output times must be strictly increasing")
+            full_T, full_times, full_sol = T, times, sol_flat
+            T, times, sol_flat = 2, [times[0], times[-1]], sol_flat[:: T - 1]      # rows 0 and T-1 of the solution
+            self._dense_next = 1
+        check(lib.pn_ts_begin(ts, 0.0, dt0, T, (ctypes.c_double * T)(*times)))
+        self._span_begin(T)
         u0f = u0.detach().contiguous().reshape(-1)
 
         # where the state at the start of step k lives
@@ -626,11 +652,14 @@ class ODEPetsc(RKSweep, SweepGraphs):
                 traj.stage_step[cur_slot] = step
             if traj is not None and cur_slot >= 0:
                 traj.seal(cur_slot)          # the step's checkpoint is complete (a no-op on the HBM tier)
+            u_n = cur[0]
             cur = nxt
             cur_slot = nxt_slot
             stepno = step + 1
             tnew = lib.pn_ts_time(ts)
             self._span_post_step(T, times, hit.value, done.value, stepno, tnew, cur[0], sol_flat)
+            if dense:
+                self._dense_step(tn, h, tnew, u_n, K, cur[0], full_times, full_sol)
             if self._monitor:
                 print("%d TS dt %g time %g" % (stepno, h, tnew))
             finished = bool(done.value)
@@ -641,7 +670,43 @@ class ODEPetsc(RKSweep, SweepGraphs):
             ops.copy(sol_flat[0], cur[0])
         else:
             self._span_end(T)
+        if dense:
+            if self._dense_next != full_T - 1:
+                raise Exception("TSSolve fails to step on all the specified points")
+            if save and self._fsal:
+                ops.copy(self._buf("dense_yN"), cur[0])       # where the last step's FSAL derivative was evaluated (reverse sweep)
         return solution
+
+    # ------------------------------------------------------------------ dense output (-pn_output_times interpolate)
+    def _dense_coefs(self, to, tn, h):
+        """h*beta_j(theta) for every stage j, theta = (to - tn)/h, in double (rounded once to the storage type by the kernels)."""
+        th = (to - tn) / h
+        out = []
+        for row in self._dense_P:
+            v = 0.0
+            for p in reversed(row):
+                v = (v + p) * th
+            out.append(h * v)
+        return out
+
+    def _dense_step(self, tn, h, tnew, u, K, unew, times, sol):
+        """After the accepted step [tn, tnew] (stage derivatives K, start state u, end state unew): the output times inside it
+        from the continuous extension in ONE launch, an output time equal to tnew as a copy of the state."""
+        T = len(times)
+        lo = o = self._dense_next
+        while o < T - 1 and times[o] < tnew:
+            o += 1
+        if o > lo:
+            cols = self._dense_cols
+            coefs = []
+            for q in range(lo, o):
+                c = self._dense_coefs(times[q], tn, h)
+                coefs.append([c[j] for j in cols])
+            self._ops.dense_eval(sol[lo:o], u, [K[j] for j in cols], coefs)
+        if o < T - 1 and times[o] == tnew:
+            self._ops.copy(sol[o], unew)
+            o += 1
+        self._dense_next = o
 
     # ------------------------------------------------------------------ time span (pa.py:518-532, 822-868)
     def _span_begin(self, T):
@@ -734,6 +799,8 @@ class ODEPetsc(RKSweep, SweepGraphs):
                                  "; final time matched exactly (MATCHSTEP)"))
         print("  state: %s %s on %s;  trainable parameters: %d" % (tuple(self.tensor_size), str(self.tensor_dtype).replace("torch.", ""), self.device, self.np))
         print("  launches: %s;  step loop: %s" % (self._graph_status, "C++ (pn_rk_attempt / pn_rk_adjoint_step)" if self._native else "Python"))
+        print("  output times: %s" % ("interpolate (continuous extension of order %d; the steps are those of the end points alone)"
+                                      % self._dense_order if self._dense else "match (a step ends on every output time)"))
         print("  total number of time steps=%d, rejected=%d;  trajectory: %s"
               % (self._nsteps, self._lib.pn_ts_rejections(self._ts), modes[self._tmode] if self._traj is not None else "not saved"))
 
@@ -741,6 +808,9 @@ class ODEPetsc(RKSweep, SweepGraphs):
     def petsc_adjointsolve(self, t, i=1):
         """Reverse one output interval (pa.py:871-890): all steps when `t` has one element,
         else the ``cur_sol_steps[i]`` steps that led to output time i."""
+        if self._dense and t.shape[0] > 1:
+            raise PnError("petsc_adjointsolve by output interval is not available under -pn_output_times interpolate: the output "
+                          "times no longer end steps (odeint_adjoint's backward covers all outputs)")
         if t.shape[0] == 1:
             self._adjoint_steps(self._nsteps, None)
         else:
