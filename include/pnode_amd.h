@@ -382,6 +382,23 @@ int pn_rk_dense_adjoint(void *stream, int dtype, int64_t n, int m, const void *g
                         void *const *D, void *G, int accumulate);
 
 /* ------------------------------------------------------------------------------------------
+ * 3a''. Time-gradient reductions (csrc/pn_tgrad.hip; extension: odeint_adjoint's dL/dt).  The
+ *     reference returns no gradient for the output times (pa.py:947).  Both accumulate in double into slots of a device
+ *     vector, reduce in a fixed order (per-workgroup partials, the last workgroup to arrive adds them in index order; no
+ *     float atomics: bit-reproducible) and never wait for the host (capturable).  `work` needs pn_tgrad_work_bytes(n)
+ *     bytes, ZERO-FILLED once before its first use (arrival counters, as pn_dots); one work area serves every launch of
+ *     one stream.
+ * ---------------------------------------------------------------------------------------- */
+int64_t pn_tgrad_work_bytes(int64_t n);
+/* acc[0] (+)= sum_{p<np} coef[p] * <x[p], y[p]>   (np <= PN_MAX_STAGES; accumulate 0: acc[0] is overwritten) */
+int pn_tgrad_dots(void *stream, int dtype, int64_t n, int np, const void *const *x, const void *const *y, const double *coef,
+                  void *work, double *acc, int accumulate);
+/* acc[o] (+)= sum_{j<nk} coef[o*nk + j] * <g[o*ld ..], K[j]>   for o < m: the derivative of a step's interpolated outputs
+ * with respect to their times (coef = beta'_j(theta_o)), each g row and each K_j read once per PN_DENSE_CHUNK rows. */
+int pn_rk_dense_tgrad(void *stream, int dtype, int64_t n, int m, const void *g, int64_t ld, int nk, const void *const *K,
+                      const double *coef, void *work, double *acc, int accumulate);
+
+/* ------------------------------------------------------------------------------------------
  * 3b. GMRES core for the implicit (theta-method) stage solves: the small dense part of
  *     KSPGMRES -- Hessenberg columns, Givens rotations, residual estimate, back substitution.
  *     The Krylov vectors live in HBM and are orthogonalised with pn_dots + pn_rk_stage-style

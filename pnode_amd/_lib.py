@@ -76,6 +76,9 @@ PROTOTYPES = {
     "pn_rk_dense_eval": (_i, [_vp, _i, _i64, _vp, _i, _pvp, _i, _pd, _vp, _i64, _i]),
     "pn_rk_dense_adjoint": (_i, [_vp, _i, _i64, _i, _vp, _i64, _i, _pd, _pvp, _vp, _i]),
     "pn_tableau_dense": (_i, [_cp, _pi, _pi, _pd]),
+    "pn_tgrad_work_bytes": (_i64, [_i64]),
+    "pn_tgrad_dots": (_i, [_vp, _i, _i64, _i, _pvp, _pvp, _pd, _vp, _vp, _i]),
+    "pn_rk_dense_tgrad": (_i, [_vp, _i, _i64, _i, _vp, _i64, _i, _pvp, _pd, _vp, _vp, _i]),
     "pn_ts_get_tableau_dense": (_i, [_vp, _pi, _pi, _pd]),
     "pn_last_error": (_cp, []),
     "pn_abi_version": (_i, []),

@@ -49,11 +49,13 @@ class RKSweep(object):
         if slot is not None and self._sg is not None:
             return self._sg.evaluate(self, slot, t, y_flat, tape)
         y = self._shaped(y_flat)
+        if self._tgrad:
+            t = self._t_arg(t, tape is not None)      # (every evaluation of such a solve: forward and adjoint see the same f)
         if tape is not None:
             with torch.enable_grad():
                 y = y.detach().requires_grad_(True)
                 k, wrt = self._func_with_grad(t, y)
-            tape.append((y, k, wrt))
+            tape.append((y, k, wrt, t) if self._tgrad else (y, k, wrt))
         else:
             k = self.funcEX(t, y)
         if k.dtype != self.tensor_dtype or k.device != self.device or k.numel() != self.n:
@@ -315,15 +317,24 @@ class RKSweep(object):
         all_params = self._paramsI if which == "IM" else self._paramsE
         # (a tape that belongs to a captured evaluation is differentiated again at every replay of its backward unit)
         keep = True if (self._unit_capture and tape is not None) else None
+        tt = None
         if tape is not None:
-            y, out, wrt = tape
+            y, out, wrt = tape[:3]
+            tt = tape[3] if len(tape) > 3 else None
         else:
             self.nfe_backward += 1
         with torch.enable_grad() if tape is None else contextlib.nullcontext():
             if tape is None:
                 y = self._shaped(y_flat).detach().requires_grad_(True)
-                out, wrt = self._func_with_grad(t, y, which)
+                if self._tgrad and which == "EX":
+                    tt = self._t_arg(t, True)
+                out, wrt = self._func_with_grad(t if tt is None else tt, y, which)
             cot = self._shaped(w_flat).view(out.shape)
+            # dL/dt: t is one more input of this backward pass; <w, K> is taken before anything rewrites w
+            tgx = (tt,) if (tt is not None and self._tg is not None and which == "EX") else ()
+            gt = None
+            if tgx:
+                self._tg_dot(slot, w_flat, out, alpha)
             hooked = lin is not None and len(wrt) != len(all_params)      # this evaluation left the Linear layers to the hooks
             if hooked and not lin.disabled and alpha is not None:
                 capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
@@ -348,9 +359,11 @@ class RKSweep(object):
                     lin.alpha, lin.target = float(alpha), self.adj_p_tensor
                     lin.cot_storage = w_flat.untyped_storage().data_ptr()
                     try:
-                        grads = torch.autograd.grad(out, (y,) + wrt, cot, allow_unused=True, retain_graph=keep)
+                        grads = torch.autograd.grad(out, (y,) + wrt + tgx, cot, allow_unused=True, retain_graph=keep)
                     finally:
                         lin.alpha = None
+                    if tgx:
+                        gt, grads = grads[-1], grads[:-1]
                     grads = (grads[0],) + tuple(lin.expand(grads[1:], len(all_params)))
                     hooked = None
             if hooked:
@@ -361,11 +374,15 @@ class RKSweep(object):
                                   "differentiated by autograd alone inside a hipGraph capture")
                 lin.muted = True
                 try:
-                    grads = torch.autograd.grad(out, (y,) + tuple(all_params), cot, allow_unused=True, retain_graph=keep)
+                    grads = torch.autograd.grad(out, (y,) + tuple(all_params) + tgx, cot, allow_unused=True, retain_graph=keep)
                 finally:
                     lin.muted = False
+                if tgx:
+                    gt, grads = grads[-1], grads[:-1]
             elif hooked is False:
-                grads = torch.autograd.grad(out, (y,) + wrt, cot, allow_unused=True, retain_graph=keep)
+                grads = torch.autograd.grad(out, (y,) + wrt + tgx, cot, allow_unused=True, retain_graph=keep)
+                if tgx:
+                    gt, grads = grads[-1], grads[:-1]
                 if lin is not None:
                     self._pend_mixed = True            # what the caller queues now holds cotangents of parameters the hooks also serve
                     if self._pend_bias:
@@ -374,6 +391,8 @@ class RKSweep(object):
                 # the stage's queued (cotangent, input) pairs: one grouped launch of the fused kernel, beside the next stage; the
                 # launches of earlier stages are waited for (every stage VJP, also one autograd did alone: the buffers turn)
                 lin.flush(self, lam=self.adj_u_flat if last else None)
+            if tgx:
+                self._tg_tbar(slot, gt, alpha)
         gy = grads[0]
         if gy is not None:
             if gy.dtype != self.tensor_dtype:
@@ -424,6 +443,8 @@ class RKSweep(object):
         for r in range(nsteps):
             step = self._rev_next
             tn, H = self._step_info(step)
+            if self._tg is not None:
+                self._tg["cur"] = step
             if self._lin is not None and self._tmode != _lib.PN_TRAJ_ALL:
                 self._lin.join()             # a product still running may read stage values the recomputation below rewrites
             Y = self._stages_of(step)
@@ -647,6 +668,9 @@ class RKSweep(object):
             return self._reverse_sweep_impl(g, T)
 
     def _reverse_sweep_impl(self, g, T):
+        self._tg = None
+        if self._tgrad:
+            self._tg_begin(T)
         if self._dense_active:
             return self._reverse_sweep_dense(g, T)
         self._begin_adjoint(g[T - 1])
@@ -698,7 +722,11 @@ class RKSweep(object):
             gk, cf = fsal_part(N - 1)
             ops.dense_adjoint([d], None, gk, cf)
             tl, hl = log[N - 1]
+            if self._tg is not None:
+                self._tg.update(cur=N - 1, yN=True)
             gy, gp = self._vjp(tl + self._c[fs] * hl, self._buf("dense_yN"), d, None, alpha=1.0)
+            if self._tg is not None:
+                self._tg["yN"] = False
             if gy is not None:
                 ops.adj_accum(self.adj_u_flat, self.adj_u_flat, [gy], [1.0], None)
             if self.np > 0 and any(x is not None for x in gp):
@@ -725,9 +753,153 @@ class RKSweep(object):
                 gk, cfk = fsal_part(k - 1)
                 ops.dense_adjoint([d0], None, gk, cfk, accumulate=dw[0] is not None)
                 dw[0] = d0
+                if self._tg is not None and k == N - 1:
+                    # the part of stage 0's cotangent that step k-1's outputs send to its last stage scales with H_{k-1}, not
+                    # with H_k: <., K> of it is taken off the last step's dL/dH
+                    fp = self._tg["fprev"] = self._buf("dense_tg_fprev")
+                    ops.dense_adjoint([fp], None, gk, cfk)
             self._adjoint_steps(1, G, dense_w=dw if any(d is not None for d in dw) else None)
+            if self._tg is not None:
+                self._tg["fprev"] = None
+                self._tg_dense_step(k, g, log, rows)
         self._flush_param_accum()
         self._finish_linear_accum()
+
+    # ------------------------------------------------------------------ dL/dt
+    def _tgrad_supported(self):
+        """Whether odeint_adjoint's backward returns dL/dt: explicit RK, not under -pn_reference_defaults (the reference's
+        None, pa.py:947).  The theta / IMEX steppers return None too and say so once per solver."""
+        if self._ref_defaults:
+            return False
+        if self._theta is not None:
+            if not self._tg_warned:
+                self._tg_warned = True
+                warnings.warn("pnode_amd: the gradient with respect to the output times t is returned for the explicit RK "
+                              "steppers only; this solver's %s stepper returns None for it" % (self._stepper_kind or "implicit"),
+                              RuntimeWarning, stacklevel=4)
+            return False
+        return True
+
+    def _t_arg(self, t, grad):
+        """The time argument of func in a solve that differentiates with respect to t: a 0-dim float64 tensor on the
+        state's device (the form the per-evaluation graphs hand over), a leaf that requires grad where autograd follows."""
+        tt = torch.full((), float(t), dtype=torch.float64, device=self.device)
+        return tt.requires_grad_(True) if grad else tt
+
+    def _tg_begin(self, T):
+        """Accumulators of one reverse sweep: per output interval i, P[i] = dL/dH of its last step and Q[i] = sum of dL/dtau
+        over its steps; per interpolated output o, E[o] = dL/dt_o.  One fp64 device vector, read once by _tg_finish."""
+        N = self._nsteps
+        dense = self._dense_active
+        counts = [N] if (dense or T == 1) else list(self.cur_sol_steps[1:T])
+        iv, last, k = [0] * N, set(), 0
+        for i, c in enumerate(counts, 1):
+            for _ in range(c):
+                iv[k] = i
+                k += 1
+            if c:
+                last.add(k - 1)
+        ni = len(counts)
+        acc = torch.zeros(2 * (ni + 1) + T, dtype=torch.float64, device=self.device)
+        self._tg = dict(acc=acc, iv=iv, last=last, ni=ni, T=T, dense=dense, cur=0, yN=False, fprev=None, K={}, theta_last=[])
+
+    def _tg_owner(self, slot):
+        """(step whose tau and H the time argument of this stage evaluation depends on, its c)."""
+        tg = self._tg
+        k = tg["cur"]
+        if tg["yN"]:
+            return k, self._c[self._s - 1]
+        if self._fsal and slot == 0 and k > 0:
+            return k - 1, self._c[self._s - 1]       # first same as last: evaluated by the previous step
+        return k, self._c[slot]
+
+    def _tg_dot(self, slot, w_flat, out, alpha):
+        """<w, K>/H of a stage of the last step of an output interval goes to that interval's dL/dH (pn_tgrad_dots)."""
+        tg = self._tg
+        k = tg["cur"]
+        K = out.detach().reshape(-1)
+        if not K.is_contiguous():
+            K = K.contiguous()
+        if tg["dense"]:
+            owner, _ = self._tg_owner(slot)
+            j = self._s - 1 if owner != k or tg["yN"] else slot
+            tg["K"][(owner, j)] = K
+            if owner != k:
+                tg["K"][(k, 0)] = K
+        if k not in tg["last"]:
+            return
+        H = self._step_info(k)[1]
+        a = 1.0 if alpha is None else float(alpha)
+        xs, ys, cs = [w_flat], [K], [a / H]
+        if tg["fprev"] is not None and not tg["yN"] and slot == 0:
+            xs.append(tg["fprev"])
+            ys.append(K)
+            cs.append(-1.0 / H)
+        i = tg["iv"][k]
+        self._ops.tgrad_dots(tg["acc"][i:i + 1], xs, ys, cs)
+
+    def _tg_tbar(self, slot, gt, alpha):
+        """T = <w, df/dt>: dL/dtau of the step that evaluated the stage, and c times it to dL/dH when that step ends an interval."""
+        if gt is None:
+            return                                     # func's output does not reach t (autonomous func)
+        tg = self._tg
+        owner, c = self._tg_owner(slot)
+        a = 1.0 if alpha is None else float(alpha)
+        i = tg["iv"][owner]
+        acc = tg["acc"]
+        acc[tg["ni"] + 1 + i].add_(gt.to(torch.float64), alpha=a)
+        if owner in tg["last"] and c != 0.0:
+            acc[i].add_(gt.to(torch.float64), alpha=a * c)
+
+    def _tg_dense_step(self, k, g, log, rows):
+        """e_o = <g_o, sum_j beta'_j(theta_o) K_j> for the interpolated outputs of step k, once its K_j are known (pn_rk_dense_tgrad)."""
+        tg = self._tg
+        lo, hi, _ = rows[k]
+        Kk = {j: v for (st, j), v in tg["K"].items() if st == k}
+        for key in [key for key in tg["K"] if key[0] == k]:
+            del tg["K"][key]
+        if hi == lo:
+            return
+        times = self.sol_times.tolist()
+        tn, h = log[k]
+        ths = [(times[o] - tn) / h for o in range(lo, hi)]
+        P = self._dense_P
+        dcoef = [[sum((p + 1) * P[j][p] * th ** p for p in range(len(P[j]))) for j in range(self._s)] for th in ths]
+        cols = [j for j in range(self._s) if any(r[j] != 0.0 for r in dcoef)]
+        missing = [j for j in cols if j not in Kk]
+        if missing:
+            raise PnError("pnode_amd: dL/dt of interpolated outputs: stage derivative(s) %s of step %d were not evaluated" % (missing, k))
+        base = 2 * (tg["ni"] + 1)
+        self._ops.dense_tgrad(tg["acc"][base + lo:base + hi], g[lo:hi], [Kk[j] for j in cols],
+                              [[r[j] for j in cols] for r in dcoef])
+        if k in tg["last"]:
+            tg["theta_last"] = list(zip(range(lo, hi), ths))
+
+    def _tg_finish(self, t):
+        """dL/dt from the accumulators (one read): dL/dt_0 = Q_1 - P_1, dL/dt_i = P_i - P_{i+1} + Q_{i+1}, dL/dt_N = P_N; an
+        interpolated output o adds e_o to its own entry and takes it from tau of its step (and theta_o e_o from the last H)."""
+        tg, self._tg = self._tg, None
+        a = tg["acc"].cpu().tolist()
+        ni, T = tg["ni"], tg["T"]
+        P = a[:ni + 1]
+        Q = a[ni + 1:2 * (ni + 1)]
+        E = a[2 * (ni + 1):]
+        out = [0.0] * T
+        if tg["dense"]:
+            for o in range(1, T - 1):
+                out[o] = E[o]
+                Q[1] -= E[o]
+            for o, th in tg["theta_last"]:
+                P[1] -= th * E[o]
+            out[0], out[T - 1] = Q[1] - P[1], P[1]
+        elif T == 1:
+            out[0] = P[1]
+        else:
+            out[0] = Q[1] - P[1]
+            for i in range(1, T - 1):
+                out[i] = P[i] - P[i + 1] + Q[i + 1]
+            out[T - 1] = P[T - 1]
+        return torch.tensor(out, dtype=torch.float64).to(dtype=t.dtype, device=t.device).view_as(t)
 
     def _finish_linear_accum(self):
         """End of a reverse sweep: the partial sums of the fused Linear-sensitivity kernel go into mu (pn_linear_wgrad_finish)."""

@@ -113,6 +113,11 @@ class SweepGraphs(object):
         """Cache entry for this call, or None when the call must run eagerly."""
         if not self._graph_mode or self.device.type != "cuda" or self._traj_disk:
             return None                              # (file I/O of the disk tier is host work inside the sweeps)
+        if self._tgrad:
+            # (the time gradient's accumulators and its per-step scalar products are not part of the captured sweeps, nor of the
+            # per-evaluation graphs, whose time argument is a tensor of their own)
+            self._graph_status = "eager (t requires grad: the sweeps of a solve that differentiates with respect to t are not captured)"
+            return None
         if self._adaptive and (self._theta is not None or not self._native or self._sharded()):
             # adaptive sweeps: per-evaluation graphs (_stagegraphs.py), explicit RK only; not for a batch sharded over ranks -- the
             # ranks meet in the error norm's all-reduce at every attempt, and a rank that validates (two sweeps) beside one that

@@ -214,6 +214,27 @@ class HipVecOps(object):
                                            (ctypes.c_void_p * max(nd, 1))(*[d.data_ptr() for d in Ds]),
                                            None if G is None else G.data_ptr(), 1 if accumulate else 0))
 
+    def _tgrad_work(self):
+        w = getattr(self, "_tg_work", None)
+        if w is None:                               # arrival counters start at zero (pn_tgrad_work_bytes)
+            w = self._tg_work = torch.zeros(self.lib.pn_tgrad_work_bytes(self.n) // 8, dtype=torch.float64, device=self.device)
+        return w
+
+    def tgrad_dots(self, acc, xs, ys, coefs, accumulate=True):
+        """acc[0] (+)= sum_p coefs[p] * <xs[p], ys[p]> in double, fixed order (pn_tgrad_dots); `acc`: a slot of an fp64 tensor."""
+        np_ = len(xs)
+        check(self.lib.pn_tgrad_dots(self.stream(), self.code, self.n, np_, (ctypes.c_void_p * np_)(*[x.data_ptr() for x in xs]),
+                                     (ctypes.c_void_p * np_)(*[y.data_ptr() for y in ys]), (ctypes.c_double * np_)(*coefs),
+                                     self._tgrad_work().data_ptr(), acc.data_ptr(), 1 if accumulate else 0))
+
+    def dense_tgrad(self, acc, g, Ks, coefs, accumulate=True):
+        """acc[o] (+)= sum_j coefs[o][j] * <g[o], Ks[j]> for the rows o of the 2-D view `g` (pn_rk_dense_tgrad)."""
+        m, nk = g.shape[0], len(Ks)
+        c = (ctypes.c_double * (m * nk))(*[x for row in coefs for x in row])
+        check(self.lib.pn_rk_dense_tgrad(self.stream(), self.code, self.n, m, g.data_ptr(), g.stride(0), nk,
+                                         (ctypes.c_void_p * nk)(*[k.data_ptr() for k in Ks]), c, self._tgrad_work().data_ptr(),
+                                         acc.data_ptr(), 1 if accumulate else 0))
+
     def copy(self, y, x):
         check(self.lib.pn_copy(self.stream(), self.code, self.n, y.data_ptr(), x.data_ptr()))
 

@@ -103,6 +103,9 @@ class ODEPetsc(RKSweep, SweepGraphs):
         self._unit_capture = False
         self._lin_sig = None
         self._theta = None
+        self._tgrad = False            # the solve in progress differentiates with respect to t
+        self._tg = None                # ... and the reverse sweep in progress accumulates dL/dt (RKSweep._tg_begin)
+        self._tg_warned = False
         self._theta_method = None
         self._imex_built = False
         self._paramsI = self._paramsE = self._pnamesI = self._pnamesE = ()
@@ -179,14 +182,31 @@ class ODEPetsc(RKSweep, SweepGraphs):
         s, n = v.tolist()
         return (s / n) ** 0.5
 
-    def _allreduce_adj_p(self):
+    def _allreduce_adj_p(self, tgrad=False):
+        """mu summed (and averaged) over the ranks; with `tgrad` (this backward computes dL/dt) the per-rank dL/dt accumulators too."""
         import torch.distributed as dist
-        if not self._sharded() or self.np == 0:
+        tg = self._tg["acc"] if (tgrad and self._tg is not None) else None
+        if not self._sharded() or (self.np == 0 and tg is None):
             return
         w = self._world()
-        dist.all_reduce(self.adj_p_tensor, op=dist.ReduceOp.SUM, group=self._pg)
+        if tg is not None and (self.np == 0 or self.adj_p_tensor.dtype == tg.dtype):
+            # the per-rank partial dL/dt joins the all-reduce of mu (fp64 states); fp32 ones keep it in double, beside
+            v = torch.cat([self.adj_p_tensor, tg]) if self.np else tg
+            dist.all_reduce(v, op=dist.ReduceOp.SUM, group=self._pg)
+            if self.np:
+                self.adj_p_tensor.copy_(v[: self.np])
+                tg.copy_(v[self.np:])
+            tg_done = True
+        else:
+            dist.all_reduce(self.adj_p_tensor, op=dist.ReduceOp.SUM, group=self._pg)
+            tg_done = tg is None
+        if not tg_done:
+            dist.all_reduce(tg, op=dist.ReduceOp.SUM, group=self._pg)
         if self._pg_average and w > 1:
-            self.adj_p_tensor.mul_(1.0 / w)
+            if self.np:
+                self.adj_p_tensor.mul_(1.0 / w)
+            if tg is not None:
+                tg.mul_(1.0 / w)
 
     # ------------------------------------------------------------------ setup (pa.py:534-775)
     def setupTS(self, u_tensor, func, step_size=0.01, enable_adjoint=True, implicit_form=False,
@@ -506,6 +526,7 @@ class ODEPetsc(RKSweep, SweepGraphs):
     def odeint(self, u0, t):
         """Solve du/dt = func(t, u), u(t[0]) = u0; returns the states at the times `t`
         (first dimension), or, when `t` has one element, integrates [0, t[0]] (pa.py:818-820)."""
+        self._tgrad = False
         return self._odeint(u0, t, self.enable_adjoint)
 
     def _device_guard(self):
@@ -836,7 +857,10 @@ class OdeintAdjointMethod(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y0, t, flat_params, ode, *args):
         ctx.ode = ode
-        need = ode.enable_adjoint and ode._grad_mode and (ctx.needs_input_grad[0] or any(ctx.needs_input_grad[4:]))
+        # dL/dt: explicit RK only; -pn_reference_defaults keeps the reference's None (pa.py:947)
+        tg = bool(ctx.needs_input_grad[1]) and ode._tgrad_supported()
+        need = ode.enable_adjoint and ode._grad_mode and (ctx.needs_input_grad[0] or any(ctx.needs_input_grad[4:]) or tg)
+        ode._tgrad = ctx.tgrad = bool(tg and need)
         with torch.no_grad():
             ans, e, warm = ode._sweep_forward(y0, t, need)
         ctx.graph_entry = e
@@ -856,11 +880,16 @@ class OdeintAdjointMethod(torch.autograd.Function):
             g = g.to(ode.tensor_dtype)
         g = g.contiguous().view(T, -1)
         with torch.no_grad():
-            ode._sweep_backward(ctx.graph_entry, getattr(ctx, "warm_entry", None), g, T)
-            ode._allreduce_adj_p()
+            ode._tgrad = ctx.tgrad
+            try:
+                ode._sweep_backward(ctx.graph_entry, getattr(ctx, "warm_entry", None), g, T)
+                ode._allreduce_adj_p(tgrad=ctx.tgrad)
+                adj_t = ode._tg_finish(t) if ctx.tgrad else None
+            finally:
+                ode._tg = None             # (a backward that raised leaves no accumulators behind for a later one)
             if "pnode_amd.logview" in sys.modules:
                 sys.modules["pnode_amd.logview"].note_backward(ode)
             adj_u = ode._shaped(ode.adj_u_flat).detach().clone()
             adj_p = ode.adj_p_tensor.detach().clone()
             gparams = tuple(adj_p[o:o + l].view_as(p).to(p.dtype) for p, o, l in zip(ode._params, ode._poff, ode._plen))
-        return (adj_u, None, None, None) + gparams
+        return (adj_u, adj_t, None, None) + gparams
