@@ -8,6 +8,7 @@ after the script's own, exactly as with the reference:
 
     python examples/spiral_node.py --niters 200 -ts_adapt_type none -ts_trajectory_type memory
     python examples/spiral_node.py --niters 200 --method dopri5            # adaptive steps
+    python examples/spiral_node.py --niters 200 --method dopri5 -pn_adapt_scope sample   # ... one controller per trajectory
     python examples/spiral_node.py --niters 200 -ts_adapt_type none -pn_graph_capture 0   # plain launches (fixed-step
                                             # sweeps are replayed from hipGraphs by default once validated: ode.graph_status)
 """

@@ -292,6 +292,9 @@ int pn_ts_override_next_dt(pn_ts *ts, double dt);
 int64_t pn_ts_steps(const pn_ts *ts);
 int64_t pn_ts_rejections(const pn_ts *ts);
 double pn_ts_time(const pn_ts *ts);
+/* The step size the controller remembers across an output time it cut a step for (0: none); TSSetTimeSpan's bookkeeping
+ * (pa.py:822), read by the per-row controllers of section 3a''' at the start of a solve. */
+double pn_ts_span_cached_dt(const pn_ts *ts);
 /* accepted-step log of the last solve: start time and size of step k, 0 <= k < steps */
 int pn_ts_step_log(const pn_ts *ts, int64_t k, double *t_start, double *h);
 
@@ -397,6 +400,56 @@ int pn_tgrad_dots(void *stream, int dtype, int64_t n, int np, const void *const 
  * with respect to their times (coef = beta'_j(theta_o)), each g row and each K_j read once per PN_DENSE_CHUNK rows. */
 int pn_rk_dense_tgrad(void *stream, int dtype, int64_t n, int m, const void *g, int64_t ld, int nk, const void *const *K,
                       const double *coef, void *work, double *acc, int accumulate);
+
+/* ------------------------------------------------------------------------------------------
+ * 3a'''. Per-sample step control (csrc/pn_rows.hip; extension, -pn_adapt_scope sample).  The
+ *     reference's TSAdapt treats the batch as one vector (one TSErrorWeightedNorm, one step size; ts.solve, pa.py:829).
+ *     Here the state is B rows of d entries (row r at element r*d) and every row has its own time, step size and
+ *     accept / reject decision: per row, these entry points stand for TSStep_RK's stage arithmetic (pn_rows_stage,
+ *     pn_rows_combine_wrms), TSAdaptChoose_Basic + the MATCHSTEP / time-span bookkeeping of TSSolve (pn_rows_control,
+ *     the text of pn_ts_judge compiled for the device) and TSAdjointStep_RK's cotangent arithmetic (pn_rows_adj_theta,
+ *     pn_rows_adj_accum; ts.adjointSolve, pa.py:878).  `h`: B doubles on the device, the row's step size (0 makes the
+ *     row's stage values equal its state and its cotangents zero: the identity).  Tableau coefficients are passed
+ *     WITHOUT the step size; h[r]*coef[j] is formed in double on the device and rounded once.  A row's result never
+ *     depends on B or on the other rows; with equal h a row is the bits of the pn_rk_* / pn_adj_* entry point.
+ * ---------------------------------------------------------------------------------------- */
+/* Y[r] = u[r] + sum_{j<nk} (h[r]*coef[j]) K[j][r]      (coef[j] = a_ij) */
+int pn_rows_stage(void *stream, int dtype, int64_t B, int64_t d, void *y, const void *u, int nk, const void *const *K,
+                  const double *coef, const double *h);
+/* pn_rk_combine_wrms per row: unew[r] = u[r] + sum (h[r]*coef_b[j]) K[j][r] (unew == NULL: u already is the new state),
+ * err = sum (h[r]*coef_e[j]) K[j][r], enorm[r] = sqrt(sum_e (err/(atol + rtol*max(|unew|,|unew+err|)))^2 / d) -- B doubles
+ * on the device, finished in the launch (one row is summed by one group of threads in a fixed order). */
+int pn_rows_combine_wrms(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk,
+                         const void *const *K, const double *coef_b, const double *coef_e, const double *h, double atol,
+                         double rtol, double *enorm);
+/* One judgement per unfinished row with the controller constants of `ts` (TSAdaptChoose_Basic, MATCHSTEP, time span:
+ * pn_ts_judge's arithmetic), one thread per row.  State: sd = doubles [4][B] (t, h, time of the row's next first stage
+ * evaluation, the step remembered across an output time), si = int32 [8][B] (span counter, accepted steps, rejections,
+ * rejections of this step, previous attempt rejected, finished (1 final time, 2 ts_max_steps, 3 failed), failure code
+ * (1 NaN/Inf norm, 2 ts_max_reject), unused).  nspan > 0: the output times span_dev[0..nspan) (on the device), else the row
+ * integrates to max_time.  Written per round: log_d = doubles [3][B] (h_eff = the step size where accepted, else 0; t and
+ * first-stage time at the round's START), log_hit = the index of the output time the row landed on or -1, accept = mask,
+ * summary = int32 [4]: rows still unfinished, first failing row or -1, its failure code, 0.  `work`:
+ * pn_rows_work_bytes(B) bytes, ZERO-FILLED once before first use (arrival counters).  pn_rows_control_host: the same on
+ * host arrays (no device); pn_rows_failure: records the message of a failure code for pn_last_error() and returns 1. */
+int64_t pn_rows_work_bytes(int64_t B);
+int pn_rows_control(void *stream, const pn_ts *ts, int64_t B, int nspan, const double *span_dev, double max_time,
+                    const double *enorm, double *sd, int32_t *si, double *log_d, int32_t *log_hit, int32_t *accept,
+                    int32_t *summary, void *work);
+int pn_rows_control_host(const pn_ts *ts, int64_t B, int nspan, const double *span, double max_time, const double *enorm,
+                         double *sd, int32_t *si, double *log_d, int32_t *log_hit, int32_t *accept, int32_t *summary);
+int pn_rows_failure(int code, int64_t row);
+/* unext[r] = accept[r] ? unew[r] : u[r] (unext may be u: then only accepted rows are written), and where accept[r] and
+ * 0 <= hit[r] < nout: sol[hit[r]*ld + r*d ..] = unew[r] (sol may be NULL).  Replaces getTimeSpanSolutions (pa.py:845). */
+int pn_rows_commit(void *stream, int dtype, int64_t B, int64_t d, void *unext, const void *u, const void *unew,
+                   const int32_t *accept, const int32_t *hit, void *sol, int64_t ld, int nout);
+/* w[r] = (h[r]*c_lam) lambda[r] + sum_{j<nk} (h[r]*coef[j]) dlam[j][r]      (lambda == NULL: no such term; nk <= 6) */
+int pn_rows_adj_theta(void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam, int nk,
+                      const void *const *dlam, const double *coef, const double *h);
+/* lambda_out[r] = lambda[r] + sum_{j<nk} dlam[j][r] (+ g[hit[r]*ld + r*d ..] where 0 <= hit[r] < nout; g may be NULL):
+ * the closing update of a reversed round with the masked forcing (pa.py:938 per row). */
+int pn_rows_adj_accum(void *stream, int dtype, int64_t B, int64_t d, void *lambda_out, const void *lambda, int nk,
+                      const void *const *dlam, const void *g, int64_t ld, const int32_t *hit, int nout);
 
 /* ------------------------------------------------------------------------------------------
  * 3b. GMRES core for the implicit (theta-method) stage solves: the small dense part of

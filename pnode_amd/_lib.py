@@ -80,6 +80,15 @@ PROTOTYPES = {
     "pn_tgrad_dots": (_i, [_vp, _i, _i64, _i, _pvp, _pvp, _pd, _vp, _vp, _i]),
     "pn_rk_dense_tgrad": (_i, [_vp, _i, _i64, _i, _vp, _i64, _i, _pvp, _pd, _vp, _vp, _i]),
     "pn_ts_get_tableau_dense": (_i, [_vp, _pi, _pi, _pd]),
+    "pn_rows_stage": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _vp]),
+    "pn_rows_combine_wrms": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _d, _d, _vp]),
+    "pn_rows_work_bytes": (_i64, [_i64]),
+    "pn_rows_control": (_i, [_vp, _vp, _i64, _i, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_rows_control_host": (_i, [_vp, _i64, _i, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_rows_failure": (_i, [_i, _i64]),
+    "pn_rows_commit": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i]),
+    "pn_rows_adj_theta": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _d, _i, _pvp, _pd, _vp]),
+    "pn_rows_adj_accum": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _vp, _i64, _vp, _i]),
     "pn_last_error": (_cp, []),
     "pn_abi_version": (_i, []),
     "pn_tableau_get": (_i, [_cp, ctypes.POINTER(Tableau)]),
@@ -134,6 +143,7 @@ PROTOTYPES = {
     "pn_ts_steps": (_i64, [_vp]),
     "pn_ts_rejections": (_i64, [_vp]),
     "pn_ts_time": (_d, [_vp]),
+    "pn_ts_span_cached_dt": (_d, [_vp]),
     "pn_ts_step_log": (_i, [_vp, _i64, _pd, _pd]),
     "pn_gmres_create": (_vp, [_i]),
     "pn_gmres_destroy": (None, [_vp]),

@@ -669,6 +669,8 @@ class RKSweep(object):
 
     def _reverse_sweep_impl(self, g, T):
         self._tg = None
+        if self._sample:
+            return self._rows_reverse(g, T)
         if self._tgrad:
             self._tg_begin(T)
         if self._dense_active:

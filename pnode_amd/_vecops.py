@@ -235,6 +235,50 @@ class HipVecOps(object):
                                          (ctypes.c_void_p * nk)(*[k.data_ptr() for k in Ks]), c, self._tgrad_work().data_ptr(),
                                          acc.data_ptr(), 1 if accumulate else 0))
 
+    # ---- per-sample step control (-pn_adapt_scope sample; csrc/pn_rows.hip): the state is B rows of d entries
+    def f64(self, *shape):
+        return torch.zeros(*shape, dtype=torch.float64, device=self.device)
+
+    def i32(self, *shape):
+        return torch.zeros(*shape, dtype=torch.int32, device=self.device)
+
+    def rows_stage(self, B, d, y, u, Ks, coefs, h):
+        check(self.lib.pn_rows_stage(self.stream(), self.code, B, d, y.data_ptr(), u.data_ptr(), len(Ks), self._ptrs(Ks),
+                                     self._dbl(coefs), h.data_ptr()))
+
+    def rows_combine_wrms(self, B, d, unew, u, Ks, cb, ce, h, atol, rtol, enorm):
+        check(self.lib.pn_rows_combine_wrms(self.stream(), self.code, B, d, None if unew is None else unew.data_ptr(), u.data_ptr(),
+                                            len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce), h.data_ptr(), atol, rtol,
+                                            enorm.data_ptr()))
+
+    def rows_control(self, ts, B, nspan, span, max_time, enorm, sd, si, log_d, log_hit, accept, summary):
+        """One judgement per unfinished row (pn_rows_control); `summary` is read by rows_summary."""
+        w = getattr(self, "_rows_work", None)
+        if w is None or w.numel() * 8 < self.lib.pn_rows_work_bytes(B):        # arrival counters start at zero
+            w = self._rows_work = torch.zeros(self.lib.pn_rows_work_bytes(B) // 8, dtype=torch.float64, device=self.device)
+        check(self.lib.pn_rows_control(self.stream(), ts, B, nspan, None if span is None else span.data_ptr(), max_time,
+                                       enorm.data_ptr(), sd.data_ptr(), si.data_ptr(), log_d.data_ptr(), log_hit.data_ptr(),
+                                       accept.data_ptr(), summary.data_ptr(), w.data_ptr()))
+
+    def rows_summary(self, summary):
+        """(rows still unfinished, first failing row or -1, its failure code): the one read-back of a round."""
+        v = summary.tolist()
+        return v[0], v[1], v[2]
+
+    def rows_commit(self, B, d, unext, u, unew, accept, hit, sol, ld, nout):
+        check(self.lib.pn_rows_commit(self.stream(), self.code, B, d, unext.data_ptr(), u.data_ptr(), unew.data_ptr(),
+                                      accept.data_ptr(), None if hit is None else hit.data_ptr(),
+                                      None if sol is None else sol.data_ptr(), ld, nout))
+
+    def rows_adj_theta(self, B, d, w, lam, c_lam, dlams, coefs, h):
+        check(self.lib.pn_rows_adj_theta(self.stream(), self.code, B, d, w.data_ptr(), None if lam is None else lam.data_ptr(),
+                                         c_lam, len(dlams), self._ptrs(dlams), self._dbl(coefs), h.data_ptr()))
+
+    def rows_adj_accum(self, B, d, lam_out, lam, dlams, g, ld, hit, nout):
+        check(self.lib.pn_rows_adj_accum(self.stream(), self.code, B, d, lam_out.data_ptr(), lam.data_ptr(), len(dlams),
+                                         self._ptrs(dlams), None if g is None else g.data_ptr(), ld,
+                                         None if hit is None else hit.data_ptr(), nout))
+
     def copy(self, y, x):
         check(self.lib.pn_copy(self.stream(), self.code, self.n, y.data_ptr(), x.data_ptr()))
 

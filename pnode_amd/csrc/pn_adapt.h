@@ -1,0 +1,204 @@
+// pnode_amd -- the step-size controller as ONE piece of text for the host engine and the device: TSAdaptChoose (none |
+// basic), the MATCHSTEP / time-span adjustment and the bookkeeping TSSolve does after an accepted step, over a small POD
+// state.  pn_ts_judge (pn_ts.cpp) runs it on the solver's own state; -pn_adapt_scope sample runs it once per batch row and
+// round, on the device (pn_rows_control, pn_rows.hip) or on host arrays (pn_rows_control_host, the CPU-only tests).
+// Plain C++ (also read by g++ without HIP).
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define PN_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define PN_HD inline
+#endif
+
+struct pn_ts;
+
+struct PnCtlCfg {
+  double safety, reject_safety, clip_lo, clip_hi;
+  double dt_min, dt_max;
+  double match_stretch, match_halve;
+  double span_reltol, span_abstol;
+  double max_time;
+  int64_t max_steps;
+  int max_reject;
+  int order;        // exponent of the controller
+  int nspan;        // 0: no time span (integrate to max_time)
+};
+
+struct PnCtlState {
+  double ptime, time_step, dt_span_cached;
+  int64_t steps, rejections;
+  int spanctr, rejections_this_step;
+  int prev_attempt_rejected, finished;
+};
+
+enum { PN_CTL_OK = 0, PN_CTL_NAN = 1, PN_CTL_MAX_REJECT = 2 };
+
+#define PN_CTL_EPS 2.220446049250313e-16        /* DBL_EPSILON */
+#define PN_CTL_SQRT_EPS 1.4901161193847656e-08  /* 2^-26, exactly sqrt(DBL_EPSILON) */
+
+PN_HD double pn_ctl_min(double a, double b) { return (b < a) ? b : a; }        // std::min / std::max, argument for argument
+PN_HD double pn_ctl_max(double a, double b) { return (a < b) ? b : a; }
+
+PN_HD double pn_ctl_next_target(const PnCtlCfg &c, const double *span, const PnCtlState &s) {
+  if (c.nspan > 0 && s.spanctr < c.nspan) return span[s.spanctr];
+  return c.max_time;
+}
+
+PN_HD bool pn_ctl_close_rel(double a, double b, double rtol) {
+  return fabs(a - b) <= rtol * pn_ctl_max(fabs(a), fabs(b));
+}
+
+// One judgement of the attempt of size s.time_step from s.ptime.  enorm < 0: no error estimate (fixed step).  Returns
+// PN_CTL_OK, or a failure (the state is then finished).  *accept, *hit_span (index of the span point this step reached, or
+// -1) and *done (1 final time reached, 2 stopped by max_steps) as pn_ts_judge documents them.
+PN_HD int pn_ctl_judge(const PnCtlCfg &c, const double *span, PnCtlState &s, double enorm, int *accept_out, int *hit_span,
+                       int *done) {
+  const double h = s.time_step;
+  bool accept = true;
+  double hnew = h;
+  *hit_span = -1;
+  *done = 0;
+  *accept_out = 0;
+  if (enorm >= 0 || enorm != enorm) {
+    if (!(enorm == enorm) || std::isinf(enorm)) {
+      s.finished = 1;
+      return PN_CTL_NAN;
+    }
+    double safety = c.safety;
+    if (enorm > 1.0) {
+      if (s.prev_attempt_rejected) safety *= c.reject_safety;
+      accept = h < (1 + PN_CTL_SQRT_EPS) * c.dt_min;
+    }
+    double hfac = enorm > 0 ? safety * pow(enorm, -1.0 / (double)c.order) : (double)INFINITY;
+    hfac = pn_ctl_min(pn_ctl_max(hfac, c.clip_lo), c.clip_hi);
+    hnew = pn_ctl_min(pn_ctl_max(h * hfac, c.dt_min), c.dt_max);
+  }
+  if (!accept) {
+    s.time_step = hnew;
+    s.rejections++;
+    s.prev_attempt_rejected = 1;
+    if (++s.rejections_this_step > c.max_reject && c.max_reject >= 0) {
+      s.finished = 1;
+      return PN_CTL_MAX_REJECT;
+    }
+    return PN_CTL_OK;
+  }
+  // --- accepted: choose the next step so that every target time is hit exactly
+  double t = s.ptime + h;
+  {
+    double tend;
+    if (c.nspan > 0) {
+      const bool hit = s.spanctr < c.nspan && fabs(t - span[s.spanctr]) <= c.span_reltol * fabs(h) + c.span_abstol;
+      if (hit) {
+        tend = s.spanctr + 1 < c.nspan ? span[s.spanctr + 1] : c.max_time;
+        if (s.dt_span_cached > 0) {
+          // the steps that approached this point were cut (or stretched) to land on it: go back to the step that was
+          // wanted before the first of those adjustments -- unless the controller has chosen a new one meanwhile
+          if (hnew == h) hnew = s.dt_span_cached;
+          s.dt_span_cached = 0;
+        }
+      } else {
+        tend = pn_ctl_next_target(c, span, s);
+      }
+    } else {
+      tend = c.max_time;
+    }
+    if (t < tend) {
+      const double hmax = tend - t, wanted = hnew;
+      if (wanted * c.match_halve > hmax) hnew = hmax / 2;
+      if (wanted * (1.0 + c.match_stretch) > hmax) hnew = hmax;
+      // remember the unadjusted step ONCE per approach: a halved step that is later stretched onto the point must
+      // not replace the user's step in the cache (it would never come back)
+      if (c.nspan > 0 && hnew != wanted && !(s.dt_span_cached > 0)) s.dt_span_cached = wanted;
+    }
+  }
+  // land exactly on the target when the matched step is within round-off of it
+  const double tgt = pn_ctl_next_target(c, span, s);
+  if (t != tgt && pn_ctl_close_rel(t, tgt, 16 * PN_CTL_EPS)) t = tgt;
+  const double tprev = s.ptime;
+  s.ptime = t;
+  s.time_step = hnew;
+  s.steps++;
+  s.prev_attempt_rejected = 0;
+  s.rejections_this_step = 0;
+  if (c.nspan > 0 && s.spanctr < c.nspan && fabs(t - span[s.spanctr]) <= c.span_reltol * fabs(t - tprev) + c.span_abstol) {
+    *hit_span = s.spanctr;
+    s.spanctr++;
+  }
+  *accept_out = 1;
+  if (s.ptime >= c.max_time) {
+    s.finished = 1;
+    *done = 1;
+  } else if (s.steps >= c.max_steps) {
+    s.finished = 1;
+    *done = 2;                         // TS_CONVERGED_ITS: stopped by ts_max_steps
+  }
+  return PN_CTL_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// -pn_adapt_scope sample: the state of B controllers as device (or host) arrays, one row each.
+//   sd: doubles [4][B]   t, h, t_first (where the row's next first stage derivative is evaluated), dt_span_cached
+//   si: int32   [8][B]   spanctr, steps, rejections, rejections_this_step, prev_attempt_rejected, finished, failure, -
+// and one row's judgement of a round.  Writes the round's log (h_eff, t and t_first at the round's start, hit index) and
+// the accept mask; returns 1 when the row is still unfinished afterwards.
+// ------------------------------------------------------------------------------------------
+enum { PN_ROWS_T = 0, PN_ROWS_H = 1, PN_ROWS_TFIRST = 2, PN_ROWS_CACHED = 3, PN_ROWS_ND = 4 };
+enum { PN_ROWS_SPANCTR = 0, PN_ROWS_STEPS, PN_ROWS_REJ, PN_ROWS_REJ_STEP, PN_ROWS_PREV_REJ, PN_ROWS_FINISHED, PN_ROWS_FAIL,
+       PN_ROWS_NI = 8 };
+
+struct PnRowsCtl {
+  PnCtlCfg cfg;
+  double c_last;     // c of the last stage of a first-same-as-last tableau
+  int fsal;
+};
+
+PN_HD int pn_rows_judge_row(const PnRowsCtl &rc, const double *span, int64_t B, int64_t r, const double *enorm, double *sd,
+                            int32_t *si, double *log_d, int32_t *log_hit, int32_t *accept) {
+  const double t0 = sd[PN_ROWS_T * B + r], h0 = sd[PN_ROWS_H * B + r], tf0 = sd[PN_ROWS_TFIRST * B + r];
+  log_d[B + r] = t0;
+  log_d[2 * B + r] = tf0;
+  if (si[PN_ROWS_FINISHED * B + r]) {
+    log_d[r] = 0.0;
+    log_hit[r] = -1;
+    accept[r] = 0;
+    return 0;
+  }
+  PnCtlState s;
+  s.ptime = t0;
+  s.time_step = h0;
+  s.dt_span_cached = sd[PN_ROWS_CACHED * B + r];
+  s.spanctr = si[PN_ROWS_SPANCTR * B + r];
+  s.steps = si[PN_ROWS_STEPS * B + r];
+  s.rejections = si[PN_ROWS_REJ * B + r];
+  s.rejections_this_step = si[PN_ROWS_REJ_STEP * B + r];
+  s.prev_attempt_rejected = si[PN_ROWS_PREV_REJ * B + r];
+  s.finished = 0;
+  int acc = 0, hit = -1, done = 0;
+  const int fail = pn_ctl_judge(rc.cfg, span, s, enorm[r], &acc, &hit, &done);
+  if (done && rc.cfg.nspan == 0) hit = 0;              // no time span: the final state is the one output
+  if (s.finished) s.time_step = 0.0;                   // later rounds are the identity on this row
+  sd[PN_ROWS_T * B + r] = s.ptime;
+  sd[PN_ROWS_H * B + r] = s.time_step;
+  sd[PN_ROWS_CACHED * B + r] = s.dt_span_cached;
+  if (acc) sd[PN_ROWS_TFIRST * B + r] = rc.fsal ? t0 + rc.c_last * h0 : s.ptime;
+  si[PN_ROWS_SPANCTR * B + r] = s.spanctr;
+  si[PN_ROWS_STEPS * B + r] = (int32_t)s.steps;
+  si[PN_ROWS_REJ * B + r] = (int32_t)s.rejections;
+  si[PN_ROWS_REJ_STEP * B + r] = s.rejections_this_step;
+  si[PN_ROWS_PREV_REJ * B + r] = s.prev_attempt_rejected;
+  si[PN_ROWS_FINISHED * B + r] = s.finished ? (done ? done : 3) : 0;
+  si[PN_ROWS_FAIL * B + r] = fail;
+  log_d[r] = acc ? h0 : 0.0;
+  log_hit[r] = acc ? hit : -1;
+  accept[r] = acc;
+  return s.finished ? 0 : 1;
+}
+
+namespace pn {
+// the controller constants of `ts` and what the row controllers need of its tableau (pn_ts.cpp)
+void rows_ctl_config(const pn_ts *ts, int nspan, double max_time, PnRowsCtl *out);
+}  // namespace pn

@@ -39,6 +39,28 @@ __device__ __forceinline__ void pn_store(V *p, const V &v) {
   }
 }
 
+// one term of TSErrorWeightedNorm (pn_combine_wrms_kernel, pn_rows_combine_wrms_kernel)
+template <typename T>
+__device__ __forceinline__ double wrms_term(T unew, T err, double atol, double rtol) {
+  // the reference measures |u - uhat| between the two STORED solutions (TSErrorWeightedNorm
+  // takes the vectors, not the increment), so uhat is rounded to the storage type first
+  const double un = (double)unew;
+  const double uh = (double)(T)(unew + err);
+  const double tol = atol + rtol * fmax(fabs(un), fabs(uh));
+  const double q = (un - uh) / tol;
+  return q * q;
+}
+// fp32 states: the ratio in fp32 (as a single-precision PETSc computes all of TSErrorWeightedNorm), the sum of squares
+// in double.  u - uhat is exact in fp32 (the two are within a factor of two of each other); tol and the quotient carry
+// one fp32 rounding each.  The double-precision division of the generic form was a visible share of the kernel at 4096 x 512.
+template <>
+__device__ __forceinline__ double wrms_term<float>(float unew, float err, double atol, double rtol) {
+  const float uh = unew + err;
+  const float tol = (float)atol + (float)rtol * fmaxf(fabsf(unew), fabsf(uh));
+  const float q = (unew - uh) / tol;
+  return (double)q * (double)q;
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);

@@ -126,27 +126,6 @@ struct ErrArgs {
   T ce[NK];
 };
 
-template <typename T>
-__device__ __forceinline__ double wrms_term(T unew, T err, double atol, double rtol) {
-  // the reference measures |u - uhat| between the two STORED solutions (TSErrorWeightedNorm
-  // takes the vectors, not the increment), so uhat is rounded to the storage type first
-  const double un = (double)unew;
-  const double uh = (double)(T)(unew + err);
-  const double tol = atol + rtol * fmax(fabs(un), fabs(uh));
-  const double q = (un - uh) / tol;
-  return q * q;
-}
-// fp32 states: the ratio in fp32 (as a single-precision PETSc computes all of TSErrorWeightedNorm), the sum of squares
-// in double.  u - uhat is exact in fp32 (the two are within a factor of two of each other); tol and the quotient carry
-// one fp32 rounding each.  The double-precision division of the generic form was a visible share of the kernel at 4096 x 512.
-template <>
-__device__ __forceinline__ double wrms_term<float>(float unew, float err, double atol, double rtol) {
-  const float uh = unew + err;
-  const float tol = (float)atol + (float)rtol * fmaxf(fabsf(unew), fabsf(uh));
-  const float q = (unew - uh) / tol;
-  return (double)q * (double)q;
-}
-
 // FIN: where the norm is finished.  0 (default): on the HOST -- every block stores its partial into the caller's pinned
 // block (result[1 + block]; result[0] = number of blocks) and pn_stream_wait_wrms, which has to wait for the stream anyway,
 // adds them in index order: the kernel ends with its last load.  1: in the launch (arrival counters, pn_device.h): the

@@ -1,0 +1,574 @@
+// pnode_amd -- per-sample adaptive step control (-pn_adapt_scope sample): the state is B rows of d entries and every row
+// carries its own time, step size and accept / reject decision.  The kernels here are the row-scaled forms of
+// pn_lincomb_kernel / pn_combine_wrms_kernel (pn_kernels.hip) plus the per-row controller.  See include/pnode_amd.h,
+// section 3a'''.
+//
+// Geometry.  A row is cut into chunks of 16 bytes (VW = 16 / sizeof(T) elements); a GROUP of G threads, G the smallest
+// power of two >= the number of chunks (at most the 256 threads of a workgroup), owns a row: thread g of the group takes
+// chunks g, g + G, ...  A workgroup holds 256 / G rows; the grid is capped and block-strides over the rows.  G depends on
+// d alone -- never on B or on where a row sits in its workgroup -- and so does every summation order: a row's result is
+// the same bits whatever batch it is part of.  Vector path (all bases 16-byte aligned and d % VW == 0): one
+// global_load_dwordx4 / global_store_dwordx4 per chunk, lane-contiguous.  Otherwise the scalar form of the same kernel
+// walks the same chunks element by element (the ragged last chunk is bounds-checked), so both give the same bits.
+// Coefficients h_r * a_ij are formed in double and rounded once to the storage type, then used in pn_lincomb_kernel's
+// order (first term, then fused multiply-adds in j order).  Per-row step sizes, masks and hit indices are read from
+// device vectors (double / int32); tableau coefficients are kernel arguments.  No float atomics.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "pnode_amd.h"
+#include "pn_internal.h"
+#include "pn_device.h"
+#include "pn_adapt.h"
+
+namespace {
+
+constexpr int kRowsMaxBlocks = 4096;
+
+template <typename T>
+struct RowsLinArgs {
+  T *out;
+  const T *base;                 // u (stage), or null (cotangent: the first term is a product)
+  const T *x[PN_MAX_TERMS];
+  double c[PN_MAX_TERMS];        // tableau coefficients, multiplied by h[r] in double
+  const double *h;               // null: every row uses 1
+};
+
+template <typename T>
+struct RowsErrArgs {
+  T *unew;                       // null: `u` already is the new state (first same as last)
+  const T *u;
+  const T *k[PN_MAX_STAGES];
+  double cb[PN_MAX_STAGES], ce[PN_MAX_STAGES];
+  const double *h;
+  double *enorm;
+  double atol, rtol;
+};
+
+template <typename T>
+struct RowsCommitArgs {
+  T *unext;                      // may be `u` itself: then only accepted rows are written
+  const T *u, *unew;
+  T *sol;                        // [T][B*d] with row stride ld; may be null
+  const int32_t *accept, *hit;
+  int64_t ld;
+  int nout;
+};
+
+template <typename T>
+struct RowsAccumArgs {
+  T *out;
+  const T *lam;
+  const T *x[PN_MAX_TERMS];
+  const T *g;                    // [T][.] with row stride ld; may be null
+  const int32_t *hit;
+  int64_t ld;
+  int nout;
+};
+
+struct RowsGeom {
+  int64_t B, d, nch;
+  int lgG;
+};
+
+template <typename T, bool VEC>
+__device__ __forceinline__ void load_chunk(const T *row, int64_t c, int64_t d, T (&v)[16 / sizeof(T)]) {
+  constexpr int VW = 16 / sizeof(T);
+  if (VEC) {
+    const Vec<T, VW> x = reinterpret_cast<const Vec<T, VW> *>(row)[c];
+#pragma unroll
+    for (int e = 0; e < VW; ++e) v[e] = x[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < VW; ++e) {
+      const int64_t i = c * VW + e;
+      v[e] = i < d ? row[i] : (T)0;
+    }
+  }
+}
+// (vector path: stored non-temporally, the policy pn_lincomb_kernel / pn_combine_wrms_kernel run with by default -- the
+// outputs are not read again before func has run)
+template <typename T, bool VEC>
+__device__ __forceinline__ void store_chunk(T *row, int64_t c, int64_t d, const T (&v)[16 / sizeof(T)]) {
+  constexpr int VW = 16 / sizeof(T);
+  if (VEC) {
+    Vec<T, VW> x;
+#pragma unroll
+    for (int e = 0; e < VW; ++e) x[e] = v[e];
+    pn_store<1>(reinterpret_cast<Vec<T, VW> *>(row) + c, x);
+  } else {
+#pragma unroll
+    for (int e = 0; e < VW; ++e) {
+      const int64_t i = c * VW + e;
+      if (i < d) row[i] = v[e];
+    }
+  }
+}
+
+// out[r] = base[r] + sum_j (h_r c_j) x_j[r]   (HAS_BASE: pn_rk_stage's order -- u, then fma in j)
+// out[r] = (h_r c_0) x_0[r] + sum_{j>0} ...   (!HAS_BASE: pn_adj_theta's order -- the first product, then fma)
+template <typename T, int NK, bool VEC, bool HAS_BASE>
+__global__ __launch_bounds__(kBlock) void pn_rows_lin_kernel(RowsLinArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r = (int64_t)blockIdx.x * rpb + sub; r < q.B; r += (int64_t)gridDim.x * rpb) {
+    const double h = a.h ? a.h[r] : 1.0;
+    T c[NK];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) c[j] = (T)(h * a.c[j]);
+    const int64_t off = r * q.d;
+    for (int64_t ch = g; ch < q.nch; ch += G) {
+      T b[VW], x[NK][VW], o[VW];
+      if (HAS_BASE) load_chunk<T, VEC>(a.base + off, ch, q.d, b);
+#pragma unroll
+      for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.x[j] + off, ch, q.d, x[j]);
+#pragma unroll
+      for (int e = 0; e < VW; ++e) {
+        T acc = HAS_BASE ? b[e] : c[0] * x[0][e];
+#pragma unroll
+        for (int j = HAS_BASE ? 0 : 1; j < NK; ++j) acc = fma(c[j], x[j][e], acc);
+        o[e] = acc;
+      }
+      store_chunk<T, VEC>(a.out + off, ch, q.d, o);
+    }
+  }
+}
+
+// unew[r] = u[r] + sum_j (h_r cb_j) K_j[r], err = sum_j (h_r ce_j) K_j[r], enorm[r] = sqrt(sum_e term^2 / d): one pass.
+// Per-thread sums in double over the thread's chunks in ascending order, then the group's tree: shuffles inside a wave
+// (width G), and for G > 64 the waves of the group through LDS in wave order.
+template <typename T, int NK, bool VEC, bool WRITE>
+__global__ __launch_bounds__(kBlock) void pn_rows_combine_wrms_kernel(RowsErrArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  __shared__ double lds[kBlock / kWave];
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < q.B; r0 += (int64_t)gridDim.x * rpb) {
+    const int64_t r = r0 + sub;
+    const bool live = r < q.B;
+    double sum = 0;
+    if (live) {
+      const double h = a.h[r];
+      T cb[NK], ce[NK];
+#pragma unroll
+      for (int j = 0; j < NK; ++j) {
+        cb[j] = (T)(h * a.cb[j]);
+        ce[j] = (T)(h * a.ce[j]);
+      }
+      const int64_t off = r * q.d;
+      for (int64_t ch = g; ch < q.nch; ch += G) {
+        T u[VW], k[NK][VW], o[VW];
+        load_chunk<T, VEC>(a.u + off, ch, q.d, u);
+#pragma unroll
+        for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.k[j] + off, ch, q.d, k[j]);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+          T un = u[e], er = (T)0;
+#pragma unroll
+          for (int j = 0; j < NK; ++j) {
+            if (WRITE) un = fma(cb[j], k[j][e], un);
+            er = fma(ce[j], k[j][e], er);
+          }
+          o[e] = un;
+          if (VEC || ch * VW + e < q.d) sum += wrms_term<T>(un, er, a.atol, a.rtol);
+        }
+        if (WRITE) store_chunk<T, VEC>(a.unew + off, ch, q.d, o);
+      }
+    }
+    if (G <= kWave) {
+      for (int o = G >> 1; o > 0; o >>= 1) sum += __shfl_down(sum, o, G);
+    } else {
+      sum = wave_sum(sum);
+      const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+      if (lane == 0) lds[wid] = sum;
+      __syncthreads();
+      if (g == 0) {
+        const int w0 = sub * (G / kWave);
+        sum = 0;
+        for (int w = 0; w < G / kWave; ++w) sum += lds[w0 + w];
+      }
+      __syncthreads();
+    }
+    if (live && g == 0) a.enorm[r] = sqrt(sum / (double)q.d);
+  }
+}
+
+// unext[r] = accept[r] ? unew[r] : u[r];  sol[hit[r]][r] = unew[r] where hit[r] >= 0
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void pn_rows_commit_kernel(RowsCommitArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  const bool inplace = a.unext == a.u;
+  for (int64_t r = (int64_t)blockIdx.x * rpb + sub; r < q.B; r += (int64_t)gridDim.x * rpb) {
+    const int acc = a.accept[r];
+    int hit = (acc && a.sol && a.hit) ? a.hit[r] : -1;
+    if (hit >= a.nout) hit = -1;
+    if (!acc && inplace) continue;
+    const int64_t off = r * q.d;
+    const T *src = acc ? a.unew : a.u;
+    for (int64_t ch = g; ch < q.nch; ch += G) {
+      T v[VW];
+      load_chunk<T, VEC>(src + off, ch, q.d, v);
+      store_chunk<T, VEC>(a.unext + off, ch, q.d, v);
+      if (hit >= 0) store_chunk<T, VEC>(a.sol + (int64_t)hit * a.ld + off, ch, q.d, v);
+    }
+  }
+}
+
+// out[r] = lam[r] + sum_j x_j[r] (+ g[hit[r]][r] where hit[r] >= 0): pn_adj_accum's order (every coefficient is one)
+template <typename T, int NK, bool VEC>
+__global__ __launch_bounds__(kBlock) void pn_rows_adj_accum_kernel(RowsAccumArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r = (int64_t)blockIdx.x * rpb + sub; r < q.B; r += (int64_t)gridDim.x * rpb) {
+    int hit = (a.g && a.hit) ? a.hit[r] : -1;
+    if (hit >= a.nout) hit = -1;
+    const int64_t off = r * q.d;
+    for (int64_t ch = g; ch < q.nch; ch += G) {
+      T l[VW], x[NK > 0 ? NK : 1][VW], f[VW];
+      load_chunk<T, VEC>(a.lam + off, ch, q.d, l);
+#pragma unroll
+      for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.x[j] + off, ch, q.d, x[j]);
+      if (hit >= 0) load_chunk<T, VEC>(a.g + (int64_t)hit * a.ld + off, ch, q.d, f);
+#pragma unroll
+      for (int e = 0; e < VW; ++e) {
+        T acc = l[e];
+#pragma unroll
+        for (int j = 0; j < NK; ++j) acc += x[j][e];
+        if (hit >= 0) acc += f[e];
+        l[e] = acc;
+      }
+      store_chunk<T, VEC>(a.out + off, ch, q.d, l);
+    }
+  }
+}
+
+// One thread per row runs the shared controller (pn_adapt.h).  Every workgroup publishes (unfinished rows, first failing
+// row) and draws a ticket; the last to arrive adds / compares them in index order and writes the summary.
+__global__ __launch_bounds__(kBlock) void pn_rows_control_kernel(PnRowsCtl rc, const double *span, int64_t B, const double *enorm,
+                                                                 double *sd, int32_t *si, double *log_d, int32_t *log_hit,
+                                                                 int32_t *accept, int32_t *summary, double *work) {
+  __shared__ int s_open[kBlock / kWave];
+  __shared__ long long s_fail[kBlock / kWave];
+  constexpr long long kNone = 1ll << 62;
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  int open = 0;
+  long long key = kNone;                       // 4 * row + failure code of the first failing row
+  if (r < B) {
+    open = pn_rows_judge_row(rc, span, B, r, enorm, sd, si, log_d, log_hit, accept);
+    const int f = si[PN_ROWS_FAIL * B + r];
+    if (f) key = 4 * (long long)r + f;
+  }
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    open += __shfl_down(open, o, kWave);
+    const long long other = __shfl_down(key, o, kWave);
+    key = other < key ? other : key;
+  }
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  if (lane == 0) {
+    s_open[wid] = open;
+    s_fail[wid] = key;
+  }
+  __syncthreads();
+  double *partial = work + kTicketDoubles;
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kBlock / kWave; ++w) {
+      open += s_open[w];
+      key = s_fail[w] < key ? s_fail[w] : key;
+    }
+    publish_partial(partial + 2 * blockIdx.x, (double)open);
+    publish_partial(partial + 2 * blockIdx.x + 1, (double)key);
+  }
+  if (draw_ticket(work, gridDim.x, blockIdx.x)) {
+    // the last workgroup: every thread takes the partials b = tid, tid + 256, ... (loads issued side by side), then the
+    // block's tree; an integer sum and a minimum do not depend on the order
+    double tot = 0, first = (double)kNone;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += kBlock) {
+      const double c = read_partial(partial + 2 * b), f = read_partial(partial + 2 * b + 1);
+      tot += c;
+      first = f < first ? f : first;
+    }
+    int cnt = (int)tot;
+    long long k = (long long)first;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+      cnt += __shfl_down(cnt, o, kWave);
+      const long long other = __shfl_down(k, o, kWave);
+      k = other < k ? other : k;
+    }
+    __syncthreads();                      // s_open / s_fail were read by thread 0 above
+    if (lane == 0) {
+      s_open[wid] = cnt;
+      s_fail[wid] = k;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 1; w < kBlock / kWave; ++w) {
+        cnt += s_open[w];
+        k = s_fail[w] < k ? s_fail[w] : k;
+      }
+      summary[0] = cnt;
+      summary[1] = k < kNone ? (int32_t)(k >> 2) : -1;
+      summary[2] = k < kNone ? (int32_t)(k & 3) : 0;
+      summary[3] = 0;
+    }
+  }
+}
+
+inline bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+
+template <typename T>
+RowsGeom geom(int64_t B, int64_t d) {
+  constexpr int VW = 16 / sizeof(T);
+  RowsGeom q;
+  q.B = B;
+  q.d = d;
+  q.nch = (d + VW - 1) / VW;
+  q.lgG = 0;
+  while (((int64_t)1 << q.lgG) < q.nch && (1 << q.lgG) < kBlock) ++q.lgG;
+  return q;
+}
+
+unsigned grid_for(const RowsGeom &q) {
+  const int64_t rpb = kBlock >> q.lgG;
+  int64_t nb = (q.B + rpb - 1) / rpb;
+  if (nb < 1) nb = 1;
+  return (unsigned)(nb > kRowsMaxBlocks ? kRowsMaxBlocks : nb);
+}
+
+int check_launch(const char *name) {
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return pn::fail(std::string(name) + ": " + hipGetErrorString(err));
+  return 0;
+}
+
+#define PN_ROWS_NK_SWITCH(nk, LO, CALL)                      \
+  switch (nk) {                                              \
+    case 0: if (LO == 0) { CALL(0); break; } return 1;       \
+    case 1: CALL(1); break;                                  \
+    case 2: CALL(2); break;                                  \
+    case 3: CALL(3); break;                                  \
+    case 4: CALL(4); break;                                  \
+    case 5: CALL(5); break;                                  \
+    case 6: CALL(6); break;                                  \
+    case 7: CALL(7); break;                                  \
+    default: return 1;                                       \
+  }
+
+template <typename T, bool VEC, bool HAS_BASE>
+int lin_launch(hipStream_t st, int nk, const RowsLinArgs<T> &a, const RowsGeom &q) {
+#define CALL(N) hipLaunchKernelGGL((pn_rows_lin_kernel<T, (N < 1 ? 1 : N), VEC, HAS_BASE>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q)
+  PN_ROWS_NK_SWITCH(nk, 1, CALL)
+#undef CALL
+  return 0;
+}
+
+template <typename T>
+int rows_lin(hipStream_t st, int64_t B, int64_t d, void *out, const void *base, int nk, const void *const *x, const double *c,
+             const double *h, const char *name) {
+  constexpr int VW = 16 / sizeof(T);
+  RowsLinArgs<T> a = {};
+  a.out = (T *)out;
+  a.base = (const T *)base;
+  a.h = h;
+  bool vec = (d % VW) == 0 && al16(out) && (!base || al16(base));
+  for (int j = 0; j < nk; ++j) {
+    a.x[j] = (const T *)x[j];
+    a.c[j] = c[j];
+    vec = vec && al16(x[j]);
+  }
+  const RowsGeom q = geom<T>(B, d);
+  int rc;
+  if (base) rc = vec ? lin_launch<T, true, true>(st, nk, a, q) : lin_launch<T, false, true>(st, nk, a, q);
+  else rc = vec ? lin_launch<T, true, false>(st, nk, a, q) : lin_launch<T, false, false>(st, nk, a, q);
+  if (rc) return pn::fail(std::string(name) + ": nk out of range");
+  return check_launch(name);
+}
+
+template <typename T, bool VEC, bool WRITE>
+int err_launch(hipStream_t st, int nk, const RowsErrArgs<T> &a, const RowsGeom &q) {
+#define CALL(N) hipLaunchKernelGGL((pn_rows_combine_wrms_kernel<T, (N < 1 ? 1 : N), VEC, WRITE>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q)
+  PN_ROWS_NK_SWITCH(nk, 1, CALL)
+#undef CALL
+  return 0;
+}
+
+template <typename T>
+int rows_combine(hipStream_t st, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K, const double *cb,
+                 const double *ce, const double *h, double atol, double rtol, double *enorm) {
+  constexpr int VW = 16 / sizeof(T);
+  RowsErrArgs<T> a = {};
+  a.unew = (T *)unew;
+  a.u = (const T *)u;
+  a.h = h;
+  a.enorm = enorm;
+  a.atol = atol;
+  a.rtol = rtol;
+  bool vec = (d % VW) == 0 && al16(u) && (!unew || al16(unew));
+  for (int j = 0; j < nk; ++j) {
+    a.k[j] = (const T *)K[j];
+    a.cb[j] = cb ? cb[j] : 0.0;
+    a.ce[j] = ce[j];
+    vec = vec && al16(K[j]);
+  }
+  const RowsGeom q = geom<T>(B, d);
+  int rc;
+  if (unew) rc = vec ? err_launch<T, true, true>(st, nk, a, q) : err_launch<T, false, true>(st, nk, a, q);
+  else rc = vec ? err_launch<T, true, false>(st, nk, a, q) : err_launch<T, false, false>(st, nk, a, q);
+  if (rc) return pn::fail("pn_rows_combine_wrms: nk out of range");
+  return check_launch("pn_rows_combine_wrms");
+}
+
+template <typename T>
+int rows_commit(hipStream_t st, int64_t B, int64_t d, void *unext, const void *u, const void *unew, const int32_t *accept,
+                const int32_t *hit, void *sol, int64_t ld, int nout) {
+  constexpr int VW = 16 / sizeof(T);
+  RowsCommitArgs<T> a = {};
+  a.unext = (T *)unext;
+  a.u = (const T *)u;
+  a.unew = (const T *)unew;
+  a.sol = (T *)sol;
+  a.accept = accept;
+  a.hit = hit;
+  a.ld = ld;
+  a.nout = nout;
+  const bool vec = (d % VW) == 0 && al16(unext) && al16(u) && al16(unew) && (!sol || (al16(sol) && (ld % VW) == 0));
+  const RowsGeom q = geom<T>(B, d);
+  if (vec) hipLaunchKernelGGL((pn_rows_commit_kernel<T, true>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q);
+  else hipLaunchKernelGGL((pn_rows_commit_kernel<T, false>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q);
+  return check_launch("pn_rows_commit");
+}
+
+template <typename T, bool VEC>
+int accum_launch(hipStream_t st, int nk, const RowsAccumArgs<T> &a, const RowsGeom &q) {
+#define CALL(N) hipLaunchKernelGGL((pn_rows_adj_accum_kernel<T, N, VEC>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q)
+  PN_ROWS_NK_SWITCH(nk, 0, CALL)
+#undef CALL
+  return 0;
+}
+
+template <typename T>
+int rows_accum(hipStream_t st, int64_t B, int64_t d, void *out, const void *lam, int nk, const void *const *x, const void *g,
+               int64_t ld, const int32_t *hit, int nout) {
+  constexpr int VW = 16 / sizeof(T);
+  RowsAccumArgs<T> a = {};
+  a.out = (T *)out;
+  a.lam = (const T *)lam;
+  a.g = (const T *)g;
+  a.hit = hit;
+  a.ld = ld;
+  a.nout = nout;
+  bool vec = (d % VW) == 0 && al16(out) && al16(lam) && (!g || (al16(g) && (ld % VW) == 0));
+  for (int j = 0; j < nk; ++j) {
+    a.x[j] = (const T *)x[j];
+    vec = vec && al16(x[j]);
+  }
+  const RowsGeom q = geom<T>(B, d);
+  const int rc = vec ? accum_launch<T, true>(st, nk, a, q) : accum_launch<T, false>(st, nk, a, q);
+  if (rc) return pn::fail("pn_rows_adj_accum: nk out of range");
+  return check_launch("pn_rows_adj_accum");
+}
+
+int bad_shape(const char *name, int64_t B, int64_t d) {
+  if (B < 1 || d < 1 || B > ((int64_t)1 << 40) / d) return pn::fail(std::string(name) + ": B and d must be positive");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pn_rows_stage(void *stream, int dtype, int64_t B, int64_t d, void *y, const void *u, int nk, const void *const *K,
+                  const double *coef, const double *h) {
+  if (bad_shape("pn_rows_stage", B, d)) return 1;
+  if (!y || !u || !h || nk < 1 || nk > PN_MAX_STAGES || !K || !coef) return pn::fail("pn_rows_stage: null argument or nk outside 1..7");
+  for (int j = 0; j < nk; ++j)
+    if (!K[j]) return pn::fail("pn_rows_stage: null stage derivative");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PN_F32) return rows_lin<float>(st, B, d, y, u, nk, K, coef, h, "pn_rows_stage");
+  if (dtype == PN_F64) return rows_lin<double>(st, B, d, y, u, nk, K, coef, h, "pn_rows_stage");
+  return pn::fail("pn_rows_stage: unknown dtype");
+}
+
+int pn_rows_combine_wrms(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K,
+                         const double *coef_b, const double *coef_e, const double *h, double atol, double rtol, double *enorm) {
+  if (bad_shape("pn_rows_combine_wrms", B, d)) return 1;
+  if (!u || !h || !enorm || nk < 1 || nk > PN_MAX_STAGES || !K || !coef_e || (unew && !coef_b))
+    return pn::fail("pn_rows_combine_wrms: null argument or nk outside 1..7");
+  for (int j = 0; j < nk; ++j)
+    if (!K[j]) return pn::fail("pn_rows_combine_wrms: null stage derivative");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PN_F32) return rows_combine<float>(st, B, d, unew, u, nk, K, coef_b, coef_e, h, atol, rtol, enorm);
+  if (dtype == PN_F64) return rows_combine<double>(st, B, d, unew, u, nk, K, coef_b, coef_e, h, atol, rtol, enorm);
+  return pn::fail("pn_rows_combine_wrms: unknown dtype");
+}
+
+int64_t pn_rows_work_bytes(int64_t B) {
+  const int64_t nb = (B + kBlock - 1) / kBlock;
+  return (int64_t)sizeof(double) * (kTicketDoubles + 2 * (nb < 1 ? 1 : nb));
+}
+
+int pn_rows_control(void *stream, const pn_ts *ts, int64_t B, int nspan, const double *span_dev, double max_time,
+                    const double *enorm, double *sd, int32_t *si, double *log_d, int32_t *log_hit, int32_t *accept,
+                    int32_t *summary, void *work) {
+  if (!ts || B < 1 || B > 0x7fffff00 || !enorm || !sd || !si || !log_d || !log_hit || !accept || !summary || !work ||
+      (nspan > 0 && !span_dev))
+    return pn::fail("pn_rows_control: null argument");
+  PnRowsCtl rc;
+  pn::rows_ctl_config(ts, nspan, max_time, &rc);
+  const unsigned nb = (unsigned)((B + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(pn_rows_control_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, rc, span_dev, B, enorm, sd, si,
+                     log_d, log_hit, accept, summary, (double *)work);
+  return check_launch("pn_rows_control");
+}
+
+int pn_rows_commit(void *stream, int dtype, int64_t B, int64_t d, void *unext, const void *u, const void *unew,
+                   const int32_t *accept, const int32_t *hit, void *sol, int64_t ld, int nout) {
+  if (bad_shape("pn_rows_commit", B, d)) return 1;
+  if (!unext || !u || !unew || !accept || (sol && (!hit || nout < 1 || ld < B * d)))
+    return pn::fail("pn_rows_commit: null argument or an output stride shorter than a state");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PN_F32) return rows_commit<float>(st, B, d, unext, u, unew, accept, hit, sol, ld, nout);
+  if (dtype == PN_F64) return rows_commit<double>(st, B, d, unext, u, unew, accept, hit, sol, ld, nout);
+  return pn::fail("pn_rows_commit: unknown dtype");
+}
+
+int pn_rows_adj_theta(void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam, int nk,
+                      const void *const *dlam, const double *coef, const double *h) {
+  if (bad_shape("pn_rows_adj_theta", B, d)) return 1;
+  if (!w || !h || nk < 0 || nk > PN_MAX_STAGES - 1 || (nk > 0 && (!dlam || !coef)) || (!lambda && nk == 0))
+    return pn::fail("pn_rows_adj_theta: null argument or nk outside 0..6");
+  const void *x[PN_MAX_TERMS];
+  double c[PN_MAX_TERMS];
+  int n = 0;
+  if (lambda) {
+    x[n] = lambda;
+    c[n++] = c_lam;
+  }
+  for (int j = 0; j < nk; ++j) {
+    if (!dlam[j]) return pn::fail("pn_rows_adj_theta: null vector");
+    x[n] = dlam[j];
+    c[n++] = coef[j];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PN_F32) return rows_lin<float>(st, B, d, w, nullptr, n, x, c, h, "pn_rows_adj_theta");
+  if (dtype == PN_F64) return rows_lin<double>(st, B, d, w, nullptr, n, x, c, h, "pn_rows_adj_theta");
+  return pn::fail("pn_rows_adj_theta: unknown dtype");
+}
+
+int pn_rows_adj_accum(void *stream, int dtype, int64_t B, int64_t d, void *lambda_out, const void *lambda, int nk,
+                      const void *const *dlam, const void *g, int64_t ld, const int32_t *hit, int nout) {
+  if (bad_shape("pn_rows_adj_accum", B, d)) return 1;
+  if (!lambda_out || !lambda || nk < 0 || nk > PN_MAX_STAGES || (nk > 0 && !dlam) || (g && (!hit || nout < 1 || ld < B * d)))
+    return pn::fail("pn_rows_adj_accum: null argument, nk outside 0..7 or a cotangent stride shorter than a state");
+  for (int j = 0; j < nk; ++j)
+    if (!dlam[j]) return pn::fail("pn_rows_adj_accum: null vector");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == PN_F32) return rows_accum<float>(st, B, d, lambda_out, lambda, nk, dlam, g, ld, hit, nout);
+  if (dtype == PN_F64) return rows_accum<double>(st, B, d, lambda_out, lambda, nk, dlam, g, ld, hit, nout);
+  return pn::fail("pn_rows_adj_accum: unknown dtype");
+}
+
+}  // extern "C"

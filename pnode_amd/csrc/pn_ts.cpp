@@ -21,6 +21,7 @@
 
 #include "pnode_amd.h"
 #include "pn_internal.h"
+#include "pn_adapt.h"
 
 namespace pn {
 static thread_local std::string g_last_error;
@@ -195,6 +196,30 @@ struct pn_ts {
   bool ext_embed = false;
 };
 
+static PnCtlCfg ctl_cfg(const pn_ts *ts) {
+  PnCtlCfg c;
+  c.safety = ts->safety; c.reject_safety = ts->reject_safety; c.clip_lo = ts->clip_lo; c.clip_hi = ts->clip_hi;
+  c.dt_min = ts->dt_min; c.dt_max = ts->dt_max;
+  c.match_stretch = ts->match_stretch; c.match_halve = ts->match_halve;
+  c.span_reltol = ts->span_reltol; c.span_abstol = ts->span_abstol;
+  c.max_time = ts->max_time;
+  c.max_steps = ts->max_steps;
+  c.max_reject = ts->max_reject;
+  c.order = ts->ext_order > 0 ? ts->ext_order : ts->tab.order;
+  c.nspan = (int)ts->span.size();
+  return c;
+}
+
+namespace pn {
+void rows_ctl_config(const pn_ts *ts, int nspan, double max_time, PnRowsCtl *out) {
+  out->cfg = ctl_cfg(ts);                // the solver's own constants; the rows' span lives on the device
+  out->cfg.max_time = max_time;
+  out->cfg.nspan = nspan;
+  out->fsal = ts->tab.fsal;
+  out->c_last = ts->tab.c[ts->tab.s - 1];
+}
+}  // namespace pn
+
 extern "C" {
 
 const char *pn_last_error(void) { return pn::g_last_error.c_str(); }
@@ -350,98 +375,55 @@ int pn_ts_attempt(const pn_ts *ts, double *t, double *h) {
 }
 
 // TSAdaptChoose (none | basic) followed by the MATCHSTEP / time-span adjustment, then the
-// bookkeeping TSSolve does after an accepted step.
+// bookkeeping TSSolve does after an accepted step: pn_ctl_judge (pn_adapt.h, the text the per-row
+// controllers of -pn_adapt_scope sample compile too) on this solver's state.
+static int ctl_fail(int code, int64_t row) {
+  const std::string where = row >= 0 ? " (-pn_adapt_scope sample: row " + std::to_string(row) + ")" : "";
+  if (code == PN_CTL_NAN) return pn::fail("Infinite or not-a-number generated in the error norm" + where);
+  return pn::fail("TS diverged: step rejected more than ts_max_reject times" + where);
+}
+
 int pn_ts_judge(pn_ts *ts, double enorm, int *accept_out, int *hit_span, int *done) {
   if (ts->finished) return pn::fail("pn_ts_judge: solve already finished");
-  const pn_tableau &T = ts->tab;
-  const double h = ts->time_step;
-  bool accept = true;
-  double hnew = h;
-  *hit_span = -1;
-  *done = 0;
-  if (enorm >= 0 || enorm != enorm) {
-    if (!(enorm == enorm) || std::isinf(enorm)) {
-      ts->finished = true;
-      return pn::fail("Infinite or not-a-number generated in the error norm");
-    }
-    double safety = ts->safety;
-    if (enorm > 1.0) {
-      if (ts->prev_attempt_rejected) safety *= ts->reject_safety;
-      accept = h < (1 + std::sqrt(kEps)) * ts->dt_min;
-    }
-    const int order = ts->ext_order > 0 ? ts->ext_order : T.order;
-    double hfac = enorm > 0 ? safety * std::pow(enorm, -1.0 / (double)order)
-                            : std::numeric_limits<double>::infinity();
-    hfac = std::min(std::max(hfac, ts->clip_lo), ts->clip_hi);
-    hnew = std::min(std::max(h * hfac, ts->dt_min), ts->dt_max);
-  }
-  if (!accept) {
-    ts->time_step = hnew;
-    ts->rejections++;
-    ts->prev_attempt_rejected = true;
-    *accept_out = 0;
-    if (++ts->rejections_this_step > ts->max_reject && ts->max_reject >= 0) {
-      ts->finished = true;
-      return pn::fail("TS diverged: step rejected more than ts_max_reject times");
-    }
-    return 0;
-  }
-  // --- accepted: choose the next step so that every target time is hit exactly
-  double t = ts->ptime + h;
-  {
-    double tend;
-    if (!ts->span.empty()) {
-      const bool hit = ts->spanctr < (int)ts->span.size() &&
-                       std::fabs(t - ts->span[ts->spanctr]) <= ts->span_reltol * std::fabs(h) + ts->span_abstol;
-      if (hit) {
-        tend = ts->spanctr + 1 < (int)ts->span.size() ? ts->span[ts->spanctr + 1] : ts->max_time;
-        if (ts->dt_span_cached > 0) {
-          // the steps that approached this point were cut (or stretched) to land on it: go back to the step that was
-          // wanted before the first of those adjustments -- unless the controller has chosen a new one meanwhile
-          if (hnew == h) hnew = ts->dt_span_cached;
-          ts->dt_span_cached = 0;
-        }
-      } else {
-        tend = next_target(ts);
-      }
-    } else {
-      tend = ts->max_time;
-    }
-    if (t < tend) {
-      const double hmax = tend - t, wanted = hnew;
-      if (wanted * ts->match_halve > hmax) hnew = hmax / 2;
-      if (wanted * (1.0 + ts->match_stretch) > hmax) hnew = hmax;
-      // remember the unadjusted step ONCE per approach: a halved step that is later stretched onto the point must
-      // not replace the user's step in the cache (it would never come back)
-      if (!ts->span.empty() && hnew != wanted && !(ts->dt_span_cached > 0)) ts->dt_span_cached = wanted;
-    }
-  }
-  ts->log_t.push_back(ts->ptime);
-  ts->log_h.push_back(h);
-  // land exactly on the target when the matched step is within round-off of it
-  const double tgt = next_target(ts);
-  if (t != tgt && close_rel(t, tgt, 16 * kEps)) t = tgt;
-  const double tprev = ts->ptime;
-  ts->ptime = t;
-  ts->time_step = hnew;
-  ts->steps++;
-  ts->prev_attempt_rejected = false;
-  ts->rejections_this_step = 0;
-  if (!ts->span.empty() && ts->spanctr < (int)ts->span.size() &&
-      std::fabs(t - ts->span[ts->spanctr]) <= ts->span_reltol * std::fabs(t - tprev) + ts->span_abstol) {
-    *hit_span = ts->spanctr;
-    ts->spanctr++;
-  }
-  *accept_out = 1;
-  if (ts->ptime >= ts->max_time) {
-    ts->finished = true;
-    *done = 1;
-  } else if (ts->steps >= ts->max_steps) {
-    ts->finished = true;
-    *done = 2;                         // TS_CONVERGED_ITS: stopped by ts_max_steps
+  const PnCtlCfg c = ctl_cfg(ts);
+  PnCtlState s;
+  s.ptime = ts->ptime; s.time_step = ts->time_step; s.dt_span_cached = ts->dt_span_cached;
+  s.steps = ts->steps; s.rejections = ts->rejections;
+  s.spanctr = ts->spanctr; s.rejections_this_step = ts->rejections_this_step;
+  s.prev_attempt_rejected = ts->prev_attempt_rejected ? 1 : 0;
+  s.finished = 0;
+  const double t0 = s.ptime, h0 = s.time_step;
+  const int rc = pn_ctl_judge(c, ts->span.data(), s, enorm, accept_out, hit_span, done);
+  ts->ptime = s.ptime; ts->time_step = s.time_step; ts->dt_span_cached = s.dt_span_cached;
+  ts->steps = s.steps; ts->rejections = s.rejections;
+  ts->spanctr = s.spanctr; ts->rejections_this_step = s.rejections_this_step;
+  ts->prev_attempt_rejected = s.prev_attempt_rejected != 0;
+  ts->finished = s.finished != 0;
+  if (rc) return ctl_fail(rc, -1);
+  if (*accept_out) {
+    ts->log_t.push_back(t0);
+    ts->log_h.push_back(h0);
   }
   return 0;
 }
+
+// -pn_adapt_scope sample on host arrays (the CPU-only tests' stand-in of pn_rows_control): one judgement per row.
+int pn_rows_control_host(const pn_ts *ts, int64_t B, int nspan, const double *span, double max_time, const double *enorm,
+                         double *sd, int32_t *si, double *log_d, int32_t *log_hit, int32_t *accept, int32_t *summary) {
+  if (!ts || B <= 0 || !enorm || !sd || !si || !log_d || !log_hit || !accept || !summary || (nspan > 0 && !span))
+    return pn::fail("pn_rows_control_host: null argument");
+  PnRowsCtl rc;
+  pn::rows_ctl_config(ts, nspan, max_time, &rc);
+  int32_t open = 0, frow = -1, fcode = 0;
+  for (int64_t r = 0; r < B; ++r) {
+    open += pn_rows_judge_row(rc, span, B, r, enorm, sd, si, log_d, log_hit, accept);
+    if (frow < 0 && si[PN_ROWS_FAIL * B + r]) { frow = (int32_t)r; fcode = si[PN_ROWS_FAIL * B + r]; }
+  }
+  summary[0] = open; summary[1] = frow; summary[2] = fcode; summary[3] = 0;
+  return 0;
+}
+
+int pn_rows_failure(int code, int64_t row) { return ctl_fail(code, row); }
 
 int64_t pn_ts_count_fixed_steps(const pn_ts *ts) {
   if (pn_ts_is_adaptive(ts)) return -1;
@@ -461,6 +443,7 @@ int pn_ts_override_next_dt(pn_ts *ts, double dt) {
 int64_t pn_ts_steps(const pn_ts *ts) { return ts->steps; }
 int64_t pn_ts_rejections(const pn_ts *ts) { return ts->rejections; }
 double pn_ts_time(const pn_ts *ts) { return ts->ptime; }
+double pn_ts_span_cached_dt(const pn_ts *ts) { return ts->dt_span_cached; }
 int pn_ts_step_log(const pn_ts *ts, int64_t k, double *t_start, double *h) {
   if (k < 0 || k >= (int64_t)ts->log_t.size()) return pn::fail("pn_ts_step_log: step out of range");
   *t_start = ts->log_t[k];

@@ -26,6 +26,7 @@ from . import _lib, options
 from ._lib import PnError, check  # noqa: F401
 from .misc import flat_parameters
 from ._rk_sweep import RKSweep
+from ._rowsweep import RowSweep
 from ._sweepgraphs import SweepGraphs
 from ._trajectory import _DiskTrajectory, _Trajectory, _TwoLevelTrajectory  # noqa: F401
 from ._vecops import HipVecOps, _KrylovBuffers  # noqa: F401
@@ -64,7 +65,7 @@ def _mem_now(device):
         return torch.cuda.memory_allocated(device), torch.cuda.memory_reserved(device)
 
 
-class ODEPetsc(RKSweep, SweepGraphs):
+class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
     """Explicit-RK neural-ODE solver with discrete adjoint (drop-in for pa.py:366-900).  How its sweeps are launched
     (eagerly, or replayed from hipGraphs) lives in the SweepGraphs mixin, pnode_amd/_sweepgraphs.py."""
 
@@ -364,6 +365,8 @@ class ODEPetsc(RKSweep, SweepGraphs):
             else:
                 check(self._lib.pn_ts_set_scheme(self._ts, 0, 0))          # the RK tableau drives the controller
             self._options_sig = sig
+        if self._sample:
+            self._rows_refusals()
         self._setup_linear_grads()
 
     def _set_from_options(self):
@@ -456,6 +459,15 @@ class ODEPetsc(RKSweep, SweepGraphs):
             raise PnError("-pn_output_times must be match or interpolate (got '%s')" % om)
         self._dense = om == "interpolate"
         self._dense_P = None
+        # not a PETSc option: what one step-size controller spans
+        #   batch (default): the whole flattened state -- one WRMS norm, one step size, the reference's behaviour
+        #   sample: every row of the state's first dimension has its own norm, time, step size and accept / reject
+        sc = str(db.get("pn_adapt_scope", "batch"))
+        if sc not in ("batch", "sample"):
+            raise PnError("-pn_adapt_scope must be batch or sample (got '%s')" % sc)
+        self._sample = sc == "sample"
+        if self._sample:
+            self._graph_status = "eager (-pn_adapt_scope sample: the rounds of a per-sample solve are launched eagerly)"
         for key, val in db.items():
             if key.startswith("ts_trajectory") or key in ("ts_monitor", "ts_view") or key.startswith("pn_"):
                 continue
@@ -567,6 +579,8 @@ class ODEPetsc(RKSweep, SweepGraphs):
         self._dense_active = False
         if self._theta is not None:
             return self._theta.odeint(u0, t, save)
+        if self._sample:
+            return self._rows_odeint(u0, t, save)
         lib, ops, ts = self._lib, self._ops, self._ts
         self.sol_times = t.detach().cpu().to(dtype=torch.float64)
         T = int(t.shape[0])
@@ -829,6 +843,9 @@ class ODEPetsc(RKSweep, SweepGraphs):
     def petsc_adjointsolve(self, t, i=1):
         """Reverse one output interval (pa.py:871-890): all steps when `t` has one element,
         else the ``cur_sol_steps[i]`` steps that led to output time i."""
+        if self._sample:
+            raise PnError("petsc_adjointsolve by output interval is not available under -pn_adapt_scope sample: the rows reach the "
+                          "output times in different rounds (odeint_adjoint's backward covers all outputs)")
         if self._dense and t.shape[0] > 1:
             raise PnError("petsc_adjointsolve by output interval is not available under -pn_output_times interpolate: the output "
                           "times no longer end steps (odeint_adjoint's backward covers all outputs)")
