@@ -24,6 +24,9 @@ def _ops(n, dtype):
 @pytest.mark.parametrize("m,nk", [(1, 1), (7, 4), (32, 6), (65, 7)])
 @pytest.mark.parametrize("misaligned", [False, True])
 def test_dense_kernels_against_fp64_sums(dtype, n, m, nk, misaligned):
+    """Both kernels against fp64 sums in the SCALAR form: every n here is odd, so the row stride ld = n is no multiple of the
+    vector width and the launchers' `vec` predicate is false with and without the one-element offset (asserted below).  The
+    16-byte form is tested in test_gpu_kernel_variants.py."""
     g = torch.Generator(device="cpu").manual_seed(n * 7 + m)
     off = 1 if misaligned else 0
     ops = _ops(n, dtype)
@@ -33,6 +36,8 @@ def test_dense_kernels_against_fp64_sums(dtype, n, m, nk, misaligned):
     coefs = torch.randn(m, nk, generator=g, dtype=torch.float64) * 0.1
     out_store = torch.full((off + m * n,), float("nan"), dtype=dtype, device=DEV)
     out = out_store[off:].view(m, n)
+    vw = 16 // store.element_size()
+    assert out.stride(0) % vw != 0                     # dense_eval: vec = al16(...) && ld % VW == 0 is false
     ops.dense_eval(out, u, Ks, coefs.tolist())
     cq = coefs.to(dtype).double()                      # coefficients rounded once to the storage type
     ref = u.double().cpu()[None, :] + cq @ torch.stack([k.double().cpu() for k in Ks])
@@ -45,6 +50,7 @@ def test_dense_kernels_against_fp64_sums(dtype, n, m, nk, misaligned):
     # the transpose: D_j = sum_o c_oj g_o, G = sum_o g_o (+ accumulate)
     gst = torch.randn(off + m * n, generator=g, dtype=torch.float64).to(dtype).to(DEV)
     gr = gst[off:].view(m, n)
+    assert gr.stride(0) % vw != 0                      # dense_adjoint likewise
     dst = torch.full((off + (nk + 1) * n,), float("nan"), dtype=dtype, device=DEV)
     Ds = [dst[off + j * n: off + (j + 1) * n] for j in range(nk)]
     G = dst[off + nk * n: off + (nk + 1) * n]
