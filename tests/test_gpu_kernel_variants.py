@@ -14,10 +14,12 @@ import math
 import os
 import re
 
+import numpy as np
 import pytest
 import torch
 
 from conftest import require_gpu
+from oracle import ts_oracle
 from pnode_amd import _lib
 from pnode_amd._vecops import HipVecOps
 
@@ -434,6 +436,15 @@ def test_combine_wrms_store_policy_and_vectors_per_thread(dtype, n, nk):
     ref = u.double().cpu() + sum(c * k.double().cpu() for c, k in zip(cb, K))
     assert torch.allclose(base_u.double().cpu(), ref, rtol=4 * _tol(dtype), atol=4 * _tol(dtype))
     assert math.isfinite(base_v) and base_v > 0
+    # the norm against fp64 from the STORED unew and the stored uhat (err as the kernel's fma chain forms it: fp32 products are
+    # exact in fp64, one rounding per step): what is left for fp32 states is the rounding of tol and of the quotient, 5e-7
+    npd = np.float32 if dtype == torch.float32 else np.float64
+    un = base_u.cpu().numpy()
+    err = np.zeros(n, dtype=npd)
+    for c, k in zip(ce, K):
+        err = (np.float64(npd(c)) * k.cpu().numpy().astype(np.float64) + err.astype(np.float64)).astype(npd)
+    want = ts_oracle.wrms(un, (un + err).astype(npd), 1e-4, 1e-4)
+    assert base_v == pytest.approx(want, rel=1e-6 if dtype == torch.float32 else 1e-9)
     try:
         for st in ("", ",st=0"):
             for wvpt in (1, 2, 4):
@@ -578,11 +589,15 @@ def test_rows_combine_wrms_every_nk(dtype, B, d, nk):
     for c, k in zip(cb, K):
         un = un + (hb * c) * k.double().view(B, d)
     assert _rows_close(unew.view(B, d), un, dtype)
+    # the STORED unew, and the stored uhat: err as the kernel's chain forms it, fma((T)(h_r ce_j), K_j, err) -- fp32 products are
+    # exact in fp64, one rounding per step -- so for fp32 states only the rounding of tol and of the quotient is left (5e-7)
     un = unew.double().view(B, d)
-    err = sum((hb * c) * k.double().view(B, d) for c, k in zip(ce, K))
+    err = torch.zeros_like(un)
+    for c, k in zip(ce, K):
+        err = ((hb * c).to(dtype).double() * k.double().view(B, d) + err).to(dtype).double()
     uh = (un + err).to(dtype).double()
     ref = ((((un - uh) / (atol + rtol * torch.maximum(un.abs(), uh.abs()))) ** 2).sum(1) / d).sqrt()
-    assert torch.allclose(enorm, ref, rtol=2e-3 if dtype == torch.float32 else 1e-9, atol=1e-12)
+    assert torch.allclose(enorm, ref, rtol=1e-6 if dtype == torch.float32 else 1e-9, atol=1e-12)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
