@@ -13,7 +13,7 @@
 #include <string>
 
 #include "pnode_amd.h"
-#include "pn_internal.h"
+#include "pn_launch.h"
 #include "pn_device.h"
 
 namespace {
@@ -149,52 +149,11 @@ __global__ __launch_bounds__(kBlock) void pn_rk_dense_adjoint_kernel(DenseAdjArg
   }
 }
 
-inline bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-int64_t grid_for(int64_t nvec) {
-  int64_t nb = (nvec + kBlock - 1) / kBlock;
-  if (nb < 1) nb = 1;
-  return nb > kDenseMaxBlocks ? kDenseMaxBlocks : nb;
-}
-
-int check_launch(const char *name) {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pn::fail(std::string(name) + ": " + hipGetErrorString(err));
-  return 0;
-}
-
-template <typename T, int NK, int ST>
-int eval_nk(hipStream_t st, const DenseEvalArgs<T> &a, int64_t n, bool vec) {
-  constexpr int VW = 16 / sizeof(T);
-  if (vec) {
-    const int64_t nvec = n / VW;
-    hipLaunchKernelGGL((pn_rk_dense_eval_kernel<T, NK, VW, ST>), dim3((unsigned)grid_for(nvec)), dim3(kBlock), 0, st, a, nvec, n);
-  } else {
-    hipLaunchKernelGGL((pn_rk_dense_eval_kernel<T, NK, 1, ST>), dim3((unsigned)grid_for(n)), dim3(kBlock), 0, st, a, n, n);
-  }
-  return check_launch("pn_rk_dense_eval");
-}
-
-template <typename T, int ST>
-int eval_t(hipStream_t st, int nk, const DenseEvalArgs<T> &a, int64_t n, bool vec) {
-  switch (nk) {
-    case 1: return eval_nk<T, 1, ST>(st, a, n, vec);
-    case 2: return eval_nk<T, 2, ST>(st, a, n, vec);
-    case 3: return eval_nk<T, 3, ST>(st, a, n, vec);
-    case 4: return eval_nk<T, 4, ST>(st, a, n, vec);
-    case 5: return eval_nk<T, 5, ST>(st, a, n, vec);
-    case 6: return eval_nk<T, 6, ST>(st, a, n, vec);
-    case 7: return eval_nk<T, 7, ST>(st, a, n, vec);
-  }
-  return pn::fail("pn_rk_dense_eval: nk out of range");
-}
-
 template <typename T>
 int dense_eval(hipStream_t st, int64_t n, const void *u, int nk, const void *const *K, int m, const double *coef, void *out,
                int64_t ld, int flags) {
   constexpr int VW = 16 / sizeof(T);
-  bool vec = al16(u) && al16(out) && (ld % VW) == 0;
-  for (int j = 0; j < nk; ++j) vec = vec && al16(K[j]);
+  const bool vec = pn::aligned16(u, out) && (ld % VW) == 0 && pn::aligned16(K, nk), nt = (flags & PN_DENSE_NONTEMPORAL) != 0;
   for (int o0 = 0; o0 < m; o0 += PN_DENSE_CHUNK) {
     DenseEvalArgs<T> a = {};
     a.u = (const T *)u;
@@ -204,45 +163,25 @@ int dense_eval(hipStream_t st, int64_t n, const void *u, int nk, const void *con
     a.m = m - o0 < PN_DENSE_CHUNK ? m - o0 : PN_DENSE_CHUNK;
     for (int o = 0; o < a.m; ++o)
       for (int j = 0; j < nk; ++j) a.c[o][j] = (T)coef[(int64_t)(o0 + o) * nk + j];
-    const int rc = (flags & PN_DENSE_NONTEMPORAL) ? eval_t<T, 1>(st, nk, a, n, vec) : eval_t<T, 0>(st, nk, a, n, vec);
-    if (rc) return rc;
+    const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+      return pn::with_width<T>(vec, [&](auto W) {
+        constexpr int NK = decltype(N)::value, VW = decltype(W)::value;
+        const int64_t nvec = n / VW;
+        const dim3 grid((unsigned)pn::blocks_for(nvec, kBlock, kDenseMaxBlocks));
+        return nt ? pn::launch("pn_rk_dense_eval", pn_rk_dense_eval_kernel<T, NK, VW, 1>, grid, dim3(kBlock), st, a, nvec, n)
+                  : pn::launch("pn_rk_dense_eval", pn_rk_dense_eval_kernel<T, NK, VW, 0>, grid, dim3(kBlock), st, a, nvec, n);
+      });
+    });
+    if (rc) return pn::or_fail(rc, "pn_rk_dense_eval: nk out of range");
   }
   return 0;
-}
-
-template <typename T, int ND, bool WG>
-int adj_nd(hipStream_t st, const DenseAdjArgs<T> &a, int64_t n, bool vec) {
-  constexpr int VW = 16 / sizeof(T);
-  if (vec) {
-    const int64_t nvec = n / VW;
-    hipLaunchKernelGGL((pn_rk_dense_adjoint_kernel<T, ND, VW, WG>), dim3((unsigned)grid_for(nvec)), dim3(kBlock), 0, st, a, nvec, n);
-  } else {
-    hipLaunchKernelGGL((pn_rk_dense_adjoint_kernel<T, ND, 1, WG>), dim3((unsigned)grid_for(n)), dim3(kBlock), 0, st, a, n, n);
-  }
-  return check_launch("pn_rk_dense_adjoint");
-}
-
-template <typename T, bool WG>
-int adj_t(hipStream_t st, int nd, const DenseAdjArgs<T> &a, int64_t n, bool vec) {
-  switch (nd) {
-    case 0: return WG ? adj_nd<T, 0, WG>(st, a, n, vec) : pn::fail("pn_rk_dense_adjoint: nothing to compute");
-    case 1: return adj_nd<T, 1, WG>(st, a, n, vec);
-    case 2: return adj_nd<T, 2, WG>(st, a, n, vec);
-    case 3: return adj_nd<T, 3, WG>(st, a, n, vec);
-    case 4: return adj_nd<T, 4, WG>(st, a, n, vec);
-    case 5: return adj_nd<T, 5, WG>(st, a, n, vec);
-    case 6: return adj_nd<T, 6, WG>(st, a, n, vec);
-    case 7: return adj_nd<T, 7, WG>(st, a, n, vec);
-  }
-  return pn::fail("pn_rk_dense_adjoint: nd out of range");
 }
 
 template <typename T>
 int dense_adjoint(hipStream_t st, int64_t n, int m, const void *g, int64_t ld, int nd, const double *coef, void *const *D,
                   void *G, int accumulate) {
   constexpr int VW = 16 / sizeof(T);
-  bool vec = al16(g) && (ld % VW) == 0 && (!G || al16(G));
-  for (int j = 0; j < nd; ++j) vec = vec && al16(D[j]);
+  const bool vec = pn::aligned16(g, G) && (ld % VW) == 0 && pn::aligned16(D, nd);
   for (int o0 = 0; o0 < m; o0 += PN_DENSE_CHUNK) {
     DenseAdjArgs<T> a = {};
     a.g = (const T *)g + (int64_t)o0 * ld;
@@ -253,8 +192,18 @@ int dense_adjoint(hipStream_t st, int64_t n, int m, const void *g, int64_t ld, i
     a.G = (T *)G;
     for (int o = 0; o < a.m; ++o)
       for (int j = 0; j < nd; ++j) a.c[o][j] = (T)coef[(int64_t)(o0 + o) * nd + j];
-    const int rc = G ? adj_t<T, true>(st, nd, a, n, vec) : adj_t<T, false>(st, nd, a, n, vec);
-    if (rc) return rc;
+    const int rc = pn::with_count<0, PN_MAX_STAGES>(nd, [&](auto N) {
+      return pn::with_width<T>(vec, [&](auto W) {
+        constexpr int ND = decltype(N)::value, VW = decltype(W)::value;
+        const int64_t nvec = n / VW;
+        const dim3 grid((unsigned)pn::blocks_for(nvec, kBlock, kDenseMaxBlocks));
+        if (G) return pn::launch("pn_rk_dense_adjoint", pn_rk_dense_adjoint_kernel<T, ND, VW, true>, grid, dim3(kBlock), st, a, nvec, n);
+        // (no stage cotangent and no G: there is no such kernel)
+        if constexpr (ND == 0) return pn::fail("pn_rk_dense_adjoint: nothing to compute");
+        else return pn::launch("pn_rk_dense_adjoint", pn_rk_dense_adjoint_kernel<T, ND, VW, false>, grid, dim3(kBlock), st, a, nvec, n);
+      });
+    });
+    if (rc) return pn::or_fail(rc, "pn_rk_dense_adjoint: nd out of range");
   }
   return 0;
 }
@@ -272,9 +221,8 @@ int pn_rk_dense_eval(void *stream, int dtype, int64_t n, const void *u, int nk, 
   for (int j = 0; j < nk; ++j)
     if (!K[j]) return pn::fail("pn_rk_dense_eval: null stage derivative");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return dense_eval<float>(st, n, u, nk, K, m, coef, out, ld, flags);
-  if (dtype == PN_F64) return dense_eval<double>(st, n, u, nk, K, m, coef, out, ld, flags);
-  return pn::fail("pn_rk_dense_eval: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return dense_eval<decltype(t)>(st, n, u, nk, K, m, coef, out, ld, flags); });
+  return pn::or_fail(rc, "pn_rk_dense_eval: unknown dtype");
 }
 
 int pn_rk_dense_adjoint(void *stream, int dtype, int64_t n, int m, const void *g, int64_t ld, int nd, const double *coef,
@@ -287,9 +235,8 @@ int pn_rk_dense_adjoint(void *stream, int dtype, int64_t n, int m, const void *g
   for (int j = 0; j < nd; ++j)
     if (!D[j]) return pn::fail("pn_rk_dense_adjoint: null output vector");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return dense_adjoint<float>(st, n, m, g, ld, nd, coef, D, G, accumulate);
-  if (dtype == PN_F64) return dense_adjoint<double>(st, n, m, g, ld, nd, coef, D, G, accumulate);
-  return pn::fail("pn_rk_dense_adjoint: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return dense_adjoint<decltype(t)>(st, n, m, g, ld, nd, coef, D, G, accumulate); });
+  return pn::or_fail(rc, "pn_rk_dense_adjoint: unknown dtype");
 }
 
 }  // extern "C"

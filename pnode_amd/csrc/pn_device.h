@@ -1,5 +1,6 @@
-// pnode_amd -- device-side helpers shared by the kernel files (pn_kernels.hip, pn_krylov.hip): register vectors,
-// cache-policy loads/stores, the wave/block reduction tree and the in-launch finish of a grid-wide reduction.
+// pnode_amd -- device-side helpers shared by the kernel files (every .hip of this directory but pn_linear.hip): register
+// vectors, cache-policy loads/stores, the wave/block reduction tree and the in-launch finish of a grid-wide reduction.
+// The host side of a launch -- alignment, grid size, run-time value to template argument, profiling -- is pn_launch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

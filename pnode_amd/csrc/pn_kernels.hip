@@ -16,7 +16,6 @@
 // LDS is used only for the cross-wave step of the WRMS error-norm reduction; the in-wave
 // step is a 64-lane shuffle tree.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include <cmath>
 #include <cstdint>
@@ -28,7 +27,7 @@
 #include <vector>
 
 #include "pnode_amd.h"
-#include "pn_internal.h"
+#include "pn_launch.h"
 #include "pn_device.h"
 
 namespace {
@@ -550,7 +549,7 @@ __global__ __launch_bounds__(kBlock) void pn_colsum_finish_kernel(const ColfinAr
 }
 
 // ---------------------------------------------------------------------------------------
-// host side: profiling events, launch helpers
+// host side: profiling events (the launches reach them through pn::prof_events, pn_launch.h), launch geometry
 // ---------------------------------------------------------------------------------------
 struct ProfRec {
   int kid;
@@ -591,30 +590,8 @@ int prof_drain_locked() {
   return 0;
 }
 
-template <typename Kern, typename... Args>
-int launch_b(int kid, double bytes, Kern kern, dim3 grid, dim3 block, hipStream_t st, Args... args) {
-  if (g_prof_on) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (g_prof_recs.size() >= 8192 && prof_drain_locked()) return 1;
-    hipEvent_t e0 = take_event(), e1 = take_event();
-    if (!e0 || !e1) return pn::fail("prof: hipEventCreate failed");
-    hipExtLaunchKernelGGL(kern, grid, block, 0, st, e0, e1, 0, args...);
-    g_prof_recs.push_back({kid, bytes, e0, e1});
-  } else {
-    hipLaunchKernelGGL(kern, grid, block, 0, st, args...);
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pn::fail(std::string(pn_kernel_name(kid)) + ": " + hipGetErrorString(err));
-  return 0;
-}
-
-template <typename Kern, typename... Args>
-int launch(int kid, double bytes, Kern kern, dim3 grid, hipStream_t st, Args... args) {
-  return launch_b(kid, bytes, kern, grid, dim3(kBlock), st, args...);
-}
-
-inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 template <typename T> constexpr int vec_width() { return 16 / sizeof(T); }
+constexpr const char *kBadDtype = "dtype must be PN_F32 or PN_F64";
 
 
 // Launch geometry of the streaming kernels: BLOCK threads per workgroup, VPT 16-byte vectors
@@ -687,14 +664,11 @@ int launch_lincomb_geo(int kid, hipStream_t st, double bytes, const LinArgs<T, N
                        double c2, int64_t nvec, int64_t n) {
   constexpr int VW = vec_width<T>();
   const int64_t per = (int64_t)BLOCK * VPT;
-  int64_t nb = (nvec + per - 1) / per, stride = 0;
-  if (nb < 1) nb = 1;
-  const int cap = tune().cap;
-  if (cap > 0 && nb > cap) {
-    nb = cap;
-    stride = (int64_t)cap * per;
-  }
-  return launch_b(kid, bytes, pn_lincomb_kernel<T, NIN, VW, VPT, OUT2, BLOCK, LD, ST>, dim3((unsigned)nb), dim3(BLOCK), st,
+  const int64_t full = pn::blocks_for(nvec, per), cap = tune().cap;
+  const bool capped = cap > 0 && full > cap;
+  const int64_t nb = capped ? cap : full;
+  const int64_t stride = capped ? cap * per : 0;   // capped: every block walks the vector
+  return pn::launch(kid, bytes, pn_lincomb_kernel<T, NIN, VW, VPT, OUT2, BLOCK, LD, ST>, dim3((unsigned)nb), dim3(BLOCK), st,
                   a, (T *)out, (T *)out2, (T)c2, nvec, n, stride, stride == 0 ? tune().xcd : 0);
 }
 
@@ -702,11 +676,10 @@ template <typename T, int NIN, bool OUT2>
 int launch_lincomb_n(int kid, hipStream_t st, int64_t n, const void *const *x, const double *c, void *out,
                      void *out2, double c2) {
   LinArgs<T, NIN> a;
-  bool al = aligned16(out) && (!OUT2 || aligned16(out2));
+  const bool al = pn::aligned16(out, out2) && pn::aligned16(x, NIN);
   for (int j = 0; j < NIN; ++j) {
     a.x[j] = (const T *)x[j];
     a.c[j] = (T)c[j];
-    al = al && aligned16(x[j]);
   }
   const double bytes = (double)n * sizeof(T) * (NIN + 1 + (OUT2 ? 1 : 0));
   if (al) {
@@ -729,36 +702,29 @@ int launch_lincomb_n(int kid, hipStream_t st, int64_t n, const void *const *x, c
 #undef PN_GEO
     return pn::fail("PN_TUNE: unsupported (vpt, ld, st) combination");
   }
-  dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-  return launch(kid, bytes, pn_lincomb_kernel<T, NIN, 1, 1, OUT2, kBlock>, grid, st, a, (T *)out, (T *)out2, (T)c2, n, n,
-                (int64_t)0, 0);
+  return pn::launch(kid, bytes, pn_lincomb_kernel<T, NIN, 1, 1, OUT2, kBlock>, dim3((unsigned)pn::blocks_for(n, kBlock)), dim3(kBlock),
+                    st, a, (T *)out, (T *)out2, (T)c2, n, n, (int64_t)0, 0);
 }
 
 template <typename T, bool OUT2>
 int launch_lincomb(int kid, hipStream_t st, int64_t n, int nin, const void *const *x, const double *c, void *out,
                    void *out2, double c2) {
-  switch (nin) {
-#define PN_CASE(N) \
-  case N:          \
-    return launch_lincomb_n<T, N, OUT2>(kid, st, n, x, c, out, out2, c2);
-    PN_CASE(1) PN_CASE(2) PN_CASE(3) PN_CASE(4) PN_CASE(5) PN_CASE(6) PN_CASE(7) PN_CASE(8)
-#undef PN_CASE
-    default:
-      return pn::fail("lincomb: between 1 and 8 input vectors supported");
-  }
+  const int rc = pn::with_count<1, PN_MAX_TERMS>(nin, [&](auto N) {
+    return launch_lincomb_n<T, decltype(N)::value, OUT2>(kid, st, n, x, c, out, out2, c2);
+  });
+  return pn::or_fail(rc, "lincomb: between 1 and 8 input vectors supported");
 }
 
 int lincomb(int kid, void *stream, int dtype, int64_t n, int nin, const void *const *x, const double *c, void *out,
             void *out2, double c2) {
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32)
-    return out2 ? launch_lincomb<float, true>(kid, st, n, nin, x, c, out, out2, c2)
-                : launch_lincomb<float, false>(kid, st, n, nin, x, c, out, nullptr, 0);
-  if (dtype == PN_F64)
-    return out2 ? launch_lincomb<double, true>(kid, st, n, nin, x, c, out, out2, c2)
-                : launch_lincomb<double, false>(kid, st, n, nin, x, c, out, nullptr, 0);
-  return pn::fail("dtype must be PN_F32 or PN_F64");
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return out2 ? launch_lincomb<T, true>(kid, st, n, nin, x, c, out, out2, c2)
+                : launch_lincomb<T, false>(kid, st, n, nin, x, c, out, nullptr, 0);
+  });
+  return pn::or_fail(rc, kBadDtype);
 }
 
 inline int pick_vpt_wrms(int64_t nvec) {
@@ -773,12 +739,11 @@ template <typename T, int NK, bool WRITE>
 int launch_wrms_n(hipStream_t st, int64_t n, void *unew, const void *u, const void *const *K, const double *cb,
                   const double *ce, double atol, double rtol, double *work, double *result) {
   ErrArgs<T, NK> a;
-  bool al = aligned16(u) && (!WRITE || aligned16(unew));
+  const bool al = pn::aligned16(u, unew) && pn::aligned16(K, NK);
   for (int j = 0; j < NK; ++j) {
     a.k[j] = (const T *)K[j];
     a.cb[j] = (T)(cb ? cb[j] : 0.0);
     a.ce[j] = (T)ce[j];
-    al = al && aligned16(K[j]);
   }
   const double bytes = (double)n * sizeof(T) * (NK + 1 + (WRITE ? 1 : 0));
   const double inv_n = 1.0 / (double)n;
@@ -786,69 +751,49 @@ int launch_wrms_n(hipStream_t st, int64_t n, void *unew, const void *u, const vo
     constexpr int VW = vec_width<T>();
     const int64_t nvec = n / VW;
     const int vpt = pick_vpt_wrms(nvec), stp = tune().st[PN_K_COMBINE_WRMS] != 0 ? 1 : 0;
-    const int64_t per = (int64_t)kBlock * vpt;
-    int nblocks = (int)((nvec + per - 1) / per);
-    if (nblocks < 1) nblocks = 1;
+    const int nblocks = (int)pn::blocks_for(nvec, (int64_t)kBlock * vpt);
     const int fin = tune().wfin != 0 ? 1 : 0;
 #define PN_WGEO(V, S, F)                                                                                              \
   if (vpt == V && stp == S && fin == F)                                                                               \
-    return launch(PN_K_COMBINE_WRMS, bytes, pn_combine_wrms_kernel<T, NK, VW, V, WRITE, S, F>, dim3(nblocks), st, (const T *)u, \
-                  a, (T *)unew, atol, rtol, work, nvec, n, inv_n, result);
+    return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_wrms_kernel<T, NK, VW, V, WRITE, S, F>, dim3(nblocks), dim3(kBlock), st, \
+                      (const T *)u, a, (T *)unew, atol, rtol, work, nvec, n, inv_n, result);
     PN_WGEO(1, 0, 0) PN_WGEO(1, 1, 0) PN_WGEO(2, 0, 0) PN_WGEO(2, 1, 0) PN_WGEO(4, 0, 0) PN_WGEO(4, 1, 0)
     PN_WGEO(1, 1, 1) PN_WGEO(2, 1, 1) PN_WGEO(4, 1, 1)
 #undef PN_WGEO
     return pn::fail("PN_TUNE: wvpt must be 1, 2 or 4 (wfin=1 needs the default store policy)");
   }
-  const int nblocks = (int)((n + kBlock - 1) / kBlock);
-  return launch(PN_K_COMBINE_WRMS, bytes, pn_combine_wrms_kernel<T, NK, 1, 1, WRITE, 0, 0>, dim3(nblocks), st, (const T *)u, a,
-                (T *)unew, atol, rtol, work, n, n, inv_n, result);
+  return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_wrms_kernel<T, NK, 1, 1, WRITE, 0, 0>, dim3((unsigned)pn::blocks_for(n, kBlock)),
+                    dim3(kBlock), st, (const T *)u, a, (T *)unew, atol, rtol, work, n, n, inv_n, result);
 }
 
 template <typename T, bool WRITE>
 int launch_wrms(hipStream_t st, int64_t n, int nk, void *unew, const void *u, const void *const *K, const double *cb,
                 const double *ce, double atol, double rtol, double *partial, double *result) {
-  switch (nk) {
-#define PN_CASE(N) \
-  case N:          \
-    return launch_wrms_n<T, N, WRITE>(st, n, unew, u, K, cb, ce, atol, rtol, partial, result);
-    PN_CASE(1) PN_CASE(2) PN_CASE(3) PN_CASE(4) PN_CASE(5) PN_CASE(6) PN_CASE(7)
-#undef PN_CASE
-    default:
-      return pn::fail("combine_wrms: between 1 and 7 stage derivatives supported");
-  }
+  const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+    return launch_wrms_n<T, decltype(N)::value, WRITE>(st, n, unew, u, K, cb, ce, atol, rtol, partial, result);
+  });
+  return pn::or_fail(rc, "combine_wrms: between 1 and 7 stage derivatives supported");
 }
 
 template <typename T, int NK>
 int launch_dots_n(hipStream_t st, int64_t n, const void *x, const void *const *y, double *work, double *result) {
   DotArgs<T, NK> a;
-  bool al = aligned16(x);
-  for (int j = 0; j < NK; ++j) {
-    a.y[j] = (const T *)y[j];
-    al = al && aligned16(y[j]);
-  }
+  for (int j = 0; j < NK; ++j) a.y[j] = (const T *)y[j];
   const double bytes = (double)n * sizeof(T) * (NK + 1);
-  if (al) {
-    constexpr int VW = vec_width<T>();
+  return pn::with_width<T>(pn::aligned16(x) && pn::aligned16(y, NK), [&](auto vw) {
+    constexpr int VW = decltype(vw)::value;
     const int64_t nvec = n / VW;
-    int nblocks = (int)((nvec + kBlock - 1) / kBlock);
-    if (nblocks < 1) nblocks = 1;
-    return launch(PN_K_DOTS, bytes, pn_dots_kernel<T, NK, VW>, dim3(nblocks), st, (const T *)x, a, work, nvec, n, result);
-  }
-  const int nblocks = (int)((n + kBlock - 1) / kBlock);
-  return launch(PN_K_DOTS, bytes, pn_dots_kernel<T, NK, 1>, dim3(nblocks), st, (const T *)x, a, work, n, n, result);
+    return pn::launch(PN_K_DOTS, bytes, pn_dots_kernel<T, NK, VW>, dim3((unsigned)pn::blocks_for(nvec, kBlock)), dim3(kBlock), st,
+                      (const T *)x, a, work, nvec, n, result);
+  });
 }
 
 template <typename T>
 int launch_dots(hipStream_t st, int64_t n, int nk, const void *x, const void *const *y, double *partial, double *result) {
-  switch (nk) {
-#define PN_CASE(N) \
-  case N:          \
-    return launch_dots_n<T, N>(st, n, x, y, partial, result);
-    PN_CASE(1) PN_CASE(2) PN_CASE(3) PN_CASE(4) PN_CASE(5) PN_CASE(6) PN_CASE(7) PN_CASE(8)
-#undef PN_CASE
-    default:
-      return pn::fail("pn_dots: between 1 and 8 vectors per call");
-  }
+  const int rc = pn::with_count<1, PN_MAX_TERMS>(nk, [&](auto N) {
+    return launch_dots_n<T, decltype(N)::value>(st, n, x, y, partial, result);
+  });
+  return pn::or_fail(rc, "pn_dots: between 1 and 8 vectors per call");
 }
 
 }  // namespace
@@ -871,9 +816,37 @@ int pn::prof_events(int kid, double bytes, void **e0, void **e1) {
 // =========================================================================================
 // C ABI
 // =========================================================================================
-template <typename T, int VW, int P, bool NT>
+template <typename T>
+static int param_accum_t(hipStream_t st, T *mu, double alpha, int nseg, const void *const *g, const int64_t *offset,
+                         const int64_t *len) {
+  constexpr int VW = vec_width<T>();
+  const int64_t per_block = (int64_t)kBlock * VW * 2;
+  int k = 0;
+  while (k < nseg) {
+    SegArgs<T> a;
+    int m = 0, blocks = 0;
+    double bytes = 0;
+    while (k < nseg && m < kMaxSeg) {
+      if (g[k] && len[k] > 0) {
+        a.g[m] = (const T *)g[k]; a.off[m] = offset[k]; a.len[m] = len[k]; a.first_block[m] = blocks;
+        blocks += (int)((len[k] + per_block - 1) / per_block);
+        bytes += 3.0 * (double)len[k] * sizeof(T);
+        ++m;
+      }
+      ++k;
+    }
+    if (m == 0) break;
+    a.first_block[m] = blocks; a.nseg = m;
+    int rc = pn::launch(PN_K_PARAM_ACCUM, bytes, pn_param_accum_kernel<T, VW>, dim3(blocks), dim3(kBlock), st, a, mu, (T)alpha);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+template <typename T, int P, bool NT>
 static int param_accum_multi_t(hipStream_t st, T *mu, int nsrc, const double *alpha, int nseg, const void *const *g,
                                const int64_t *offset, const int64_t *len) {
+  constexpr int VW = vec_width<T>();
   const int64_t per_block = (int64_t)kBlock * VW * P;
   int k = 0;
   while (k < nseg) {
@@ -901,7 +874,7 @@ static int param_accum_multi_t(hipStream_t st, T *mu, int nsrc, const double *al
     }
     a.first_block[m] = blocks; a.nseg = m;
     for (int j = 0; j < nsrc; ++j) a.alpha[j] = (T)alpha[j];
-    int rc = launch(PN_K_PARAM_ACCUM, bytes, pn_param_accum_multi_kernel<T, VW, P, NT>, dim3(blocks), st, a, mu);
+    int rc = pn::launch(PN_K_PARAM_ACCUM, bytes, pn_param_accum_multi_kernel<T, VW, P, NT>, dim3(blocks), dim3(kBlock), st, a, mu);
     if (rc) return rc;
   }
   return 0;
@@ -918,9 +891,10 @@ static int colsum_chunks(int64_t rows) {
   return (int)(c < 1 ? 1 : c);
 }
 
-template <typename T, int VW>
+template <typename T>
 static int colsum_multi_t(hipStream_t st, int nsrc, const int64_t *rows, const int64_t *cols, const void *const *g, void *const *mu,
                           const double *alpha, double *work) {
+  constexpr int VW = vec_width<T>();
   ColsumArgs<T> a;
   ColfinArgs<T> f;
   a.nsrc = nsrc;
@@ -959,12 +933,10 @@ static int colsum_multi_t(hipStream_t st, int nsrc, const int64_t *rows, const i
   }
   f.first_block[nt] = fblocks; f.src_begin[nt] = filled; f.nt = nt;
   if (blocks == 0) return 0;
-  int rc = launch(PN_K_PARAM_ACCUM, bytes, pn_colsum_partial_kernel<T, VW>, dim3((unsigned)blocks), st, a, work);
+  int rc = pn::launch(PN_K_PARAM_ACCUM, bytes, pn_colsum_partial_kernel<T, VW>, dim3((unsigned)blocks), dim3(kBlock), st, a, work);
   if (rc) return rc;
-  hipLaunchKernelGGL(pn_colsum_finish_kernel<T>, dim3((unsigned)fblocks), dim3(kBlock), 0, st, f, (const double *)work);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pn::fail(std::string("pn_colsum_accum_multi: ") + hipGetErrorString(err));
-  return 0;
+  return pn::launch("pn_colsum_accum_multi", pn_colsum_finish_kernel<T>, dim3((unsigned)fblocks), dim3(kBlock), st, f,
+                    (const double *)work);
 }
 
 }  // namespace
@@ -1001,13 +973,12 @@ int pn_rk_combine_wrms(void *stream, int dtype, int64_t n, void *unew, const voi
   if (!work || !result_dev) return pn::fail("pn_rk_combine_wrms: work/result buffers required");
   hipStream_t st = (hipStream_t)stream;
   double *w = (double *)work;
-  if (dtype == PN_F32)
-    return unew ? launch_wrms<float, true>(st, n, nk, unew, u, K, coef_b, coef_e, atol, rtol, w, result_dev)
-                : launch_wrms<float, false>(st, n, nk, nullptr, u, K, nullptr, coef_e, atol, rtol, w, result_dev);
-  if (dtype == PN_F64)
-    return unew ? launch_wrms<double, true>(st, n, nk, unew, u, K, coef_b, coef_e, atol, rtol, w, result_dev)
-                : launch_wrms<double, false>(st, n, nk, nullptr, u, K, nullptr, coef_e, atol, rtol, w, result_dev);
-  return pn::fail("dtype must be PN_F32 or PN_F64");
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return unew ? launch_wrms<T, true>(st, n, nk, unew, u, K, coef_b, coef_e, atol, rtol, w, result_dev)
+                : launch_wrms<T, false>(st, n, nk, nullptr, u, K, nullptr, coef_e, atol, rtol, w, result_dev);
+  });
+  return pn::or_fail(rc, kBadDtype);
 }
 
 int pn_pinned_scalar(double **host_ptr, double **dev_ptr) {
@@ -1107,9 +1078,8 @@ int pn_dots(void *stream, int dtype, int64_t n, const void *x, int nk, const voi
   if (n <= 0) return pn::fail("pn_dots: empty vector");
   if (!work || !result_dev) return pn::fail("pn_dots: work/result buffers required");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return launch_dots<float>(st, n, nk, x, y, (double *)work, result_dev);
-  if (dtype == PN_F64) return launch_dots<double>(st, n, nk, x, y, (double *)work, result_dev);
-  return pn::fail("dtype must be PN_F32 or PN_F64");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return launch_dots<decltype(t)>(st, n, nk, x, y, (double *)work, result_dev); });
+  return pn::or_fail(rc, kBadDtype);
 }
 
 int pn_stream_wait_scalars(void *stream, const double *host_ptr, int count, double *values) {
@@ -1171,44 +1141,8 @@ int pn_zero(void *stream, int dtype, int64_t n, void *y) {
 
 int pn_param_accum(void *stream, int dtype, void *mu, double alpha, int nseg, const void *const *g,
                    const int64_t *offset, const int64_t *len) {
-  hipStream_t st = (hipStream_t)stream;
-  const int esize = dtype == PN_F32 ? 4 : 8;
-  const int vw = 16 / esize;
-  const int64_t per_block = (int64_t)kBlock * vw * 2;
-  int k = 0;
-  while (k < nseg) {
-    SegArgs<float> af;
-    SegArgs<double> ad;
-    int m = 0, blocks = 0;
-    double bytes = 0;
-    while (k < nseg && m < kMaxSeg) {
-      if (g[k] && len[k] > 0) {
-        const int nb = (int)((len[k] + per_block - 1) / per_block);
-        if (dtype == PN_F32) {
-          af.g[m] = (const float *)g[k]; af.off[m] = offset[k]; af.len[m] = len[k]; af.first_block[m] = blocks;
-        } else {
-          ad.g[m] = (const double *)g[k]; ad.off[m] = offset[k]; ad.len[m] = len[k]; ad.first_block[m] = blocks;
-        }
-        blocks += nb;
-        bytes += 3.0 * (double)len[k] * esize;
-        ++m;
-      }
-      ++k;
-    }
-    if (m == 0) break;
-    int rc;
-    if (dtype == PN_F32) {
-      af.first_block[m] = blocks; af.nseg = m;
-      rc = launch(PN_K_PARAM_ACCUM, bytes, pn_param_accum_kernel<float, 4>, dim3(blocks), st, af, (float *)mu, (float)alpha);
-    } else if (dtype == PN_F64) {
-      ad.first_block[m] = blocks; ad.nseg = m;
-      rc = launch(PN_K_PARAM_ACCUM, bytes, pn_param_accum_kernel<double, 2>, dim3(blocks), st, ad, (double *)mu, alpha);
-    } else {
-      return pn::fail("dtype must be PN_F32 or PN_F64");
-    }
-    if (rc) return rc;
-  }
-  return 0;
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return param_accum_t((hipStream_t)stream, (decltype(t) *)mu, alpha, nseg, g, offset, len); });
+  return pn::or_fail(rc, kBadDtype);
 }
 
 int pn_param_accum_multi(void *stream, int dtype, void *mu, int nsrc, const double *alpha, int nseg,
@@ -1218,15 +1152,15 @@ int pn_param_accum_multi(void *stream, int dtype, void *mu, int nsrc, const doub
   hipStream_t st = (hipStream_t)stream;
   const bool two = tune().pvec == 2;          // experiment: two vectors per thread (PN_TUNE "pvec=2")
   const bool nt = tune().pnt != 0;            // non-temporal loads of the gradient tensors (PN_TUNE "pnt=0|1")
-#define PN_ACC(T, VW)                                                                                          \
-  return two ? (nt ? param_accum_multi_t<T, VW, 2, true>(st, (T *)mu, nsrc, alpha, nseg, g, offset, len)       \
-                   : param_accum_multi_t<T, VW, 2, false>(st, (T *)mu, nsrc, alpha, nseg, g, offset, len))     \
-             : (nt ? param_accum_multi_t<T, VW, 1, true>(st, (T *)mu, nsrc, alpha, nseg, g, offset, len)       \
-                   : param_accum_multi_t<T, VW, 1, false>(st, (T *)mu, nsrc, alpha, nseg, g, offset, len));
-  if (dtype == PN_F32) { PN_ACC(float, 4) }
-  if (dtype == PN_F64) { PN_ACC(double, 2) }
-#undef PN_ACC
-  return pn::fail("dtype must be PN_F32 or PN_F64");
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    T *m = (T *)mu;
+    return two ? (nt ? param_accum_multi_t<T, 2, true>(st, m, nsrc, alpha, nseg, g, offset, len)
+                     : param_accum_multi_t<T, 2, false>(st, m, nsrc, alpha, nseg, g, offset, len))
+               : (nt ? param_accum_multi_t<T, 1, true>(st, m, nsrc, alpha, nseg, g, offset, len)
+                     : param_accum_multi_t<T, 1, false>(st, m, nsrc, alpha, nseg, g, offset, len));
+  });
+  return pn::or_fail(rc, kBadDtype);
 }
 
 int64_t pn_colsum_work_bytes(int nsrc, const int64_t *rows, const int64_t *cols) {
@@ -1241,9 +1175,8 @@ int pn_colsum_accum_multi(void *stream, int dtype, int nsrc, const int64_t *rows
   for (int j = 0; j < nsrc; ++j)
     if (rows[j] <= 0 || cols[j] <= 0) return pn::fail("pn_colsum_accum_multi: empty source");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return colsum_multi_t<float, 4>(st, nsrc, rows, cols, g, mu, alpha, (double *)work);
-  if (dtype == PN_F64) return colsum_multi_t<double, 2>(st, nsrc, rows, cols, g, mu, alpha, (double *)work);
-  return pn::fail("dtype must be PN_F32 or PN_F64");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return colsum_multi_t<decltype(t)>(st, nsrc, rows, cols, g, mu, alpha, (double *)work); });
+  return pn::or_fail(rc, kBadDtype);
 }
 
 int pn_colsum_accum(void *stream, int dtype, int64_t rows, int64_t cols, const void *g, void *mu, double alpha, void *work) {

@@ -30,7 +30,7 @@
 #include <string>
 
 #include "pnode_amd.h"
-#include "pn_internal.h"
+#include "pn_launch.h"
 #include "pn_device.h"
 
 namespace {
@@ -462,14 +462,6 @@ __global__ __launch_bounds__(kBlock) void kr_close_kernel(double *S, int m, doub
   }
 }
 
-inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-inline int check_launch(const char *what) {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pn::fail(std::string(what) + ": " + hipGetErrorString(err));
-  return 0;
-}
-
 struct Geo {
   bool vec;
   int64_t nvec;
@@ -479,59 +471,63 @@ template <typename T>
 Geo geometry(int64_t n, const void *a, const void *b, int64_t ldv, const void *c) {
   Geo g;
   constexpr int VW = 16 / sizeof(T);
-  g.vec = aligned16(a) && aligned16(b) && (c == nullptr || aligned16(c)) && (ldv * (int64_t)sizeof(T)) % 16 == 0;
+  g.vec = pn::aligned16(a, b, c) && (ldv * (int64_t)sizeof(T)) % 16 == 0;
   g.nvec = g.vec ? n / VW : n;
-  int64_t nb = (g.nvec + kBlock - 1) / kBlock;
-  g.nbx = (unsigned)(nb < 1 ? 1 : nb);
+  g.nbx = (unsigned)pn::blocks_for(g.nvec, kBlock);
   return g;
 }
 
 template <typename T>
 int launch_dots(hipStream_t st, double *S, int m, int mode, int k, const void *w, const void *V, int64_t ldv, int64_t n,
                 int defer, int first, double rtol, double atol, double maxit, double *status) {
-  constexpr int VW = 16 / sizeof(T);
   const Geo g = geometry<T>(n, w, V, ldv, nullptr);
   const int nv = mode == 0 ? 1 : (k < 0 ? m : k) + 2;       // k < 0: any column of the cycle
-  const dim3 grid(g.nbx, (unsigned)((nv + kDotGroup - 1) / kDotGroup));
-  if (g.vec)
-    hipLaunchKernelGGL((kr_dots_kernel<T, VW>), grid, dim3(kBlock), 0, st, S, m, mode, k, (const T *)w, (const T *)V, ldv,
-                       g.nvec, n, defer, first, rtol, atol, maxit, status);
-  else
-    hipLaunchKernelGGL((kr_dots_kernel<T, 1>), grid, dim3(kBlock), 0, st, S, m, mode, k, (const T *)w, (const T *)V, ldv,
-                       g.nvec, n, defer, first, rtol, atol, maxit, status);
-  return check_launch("pn_krylov (products)");
+  const dim3 grid(g.nbx, (unsigned)pn::blocks_for(nv, kDotGroup));
+  return pn::with_width<T>(g.vec, [&](auto W) {
+    return pn::launch("pn_krylov (products)", kr_dots_kernel<T, decltype(W)::value>, grid, dim3(kBlock), st, S, m, mode, k, (const T *)w,
+                      (const T *)V, ldv, g.nvec, n, defer, first, rtol, atol, maxit, status);
+  });
 }
 
 template <typename T>
 int launch_update(hipStream_t st, const double *S, int m, int mode, int k, void *w, void *V, int64_t ldv, void *vin, int64_t n) {
-  constexpr int VW = 16 / sizeof(T);
   const Geo g = geometry<T>(n, w, V, ldv, vin);
-  if (g.vec)
-    hipLaunchKernelGGL((kr_update_kernel<T, VW>), dim3(g.nbx), dim3(kBlock), 0, st, S, m, mode, k, (T *)w, (T *)V, ldv, (T *)vin,
-                       g.nvec, n);
-  else
-    hipLaunchKernelGGL((kr_update_kernel<T, 1>), dim3(g.nbx), dim3(kBlock), 0, st, S, m, mode, k, (T *)w, (T *)V, ldv, (T *)vin,
-                       g.nvec, n);
-  return check_launch("pn_krylov (update)");
+  return pn::with_width<T>(g.vec, [&](auto W) {
+    return pn::launch("pn_krylov (update)", kr_update_kernel<T, decltype(W)::value>, dim3(g.nbx), dim3(kBlock), st, S, m, mode, k, (T *)w,
+                      (T *)V, ldv, (T *)vin, g.nvec, n);
+  });
 }
 
 int launch_decide(hipStream_t st, double *S, int m, int mode, int k, int first, double rtol, double atol, double maxit,
                   double *status) {
-  hipLaunchKernelGGL(kr_decide_kernel, dim3(1), dim3(kBlock), 0, st, S, m, mode, k, first, rtol, atol, maxit, status);
-  return check_launch("pn_krylov (decision)");
+  return pn::launch("pn_krylov (decision)", kr_decide_kernel, dim3(1), dim3(kBlock), st, S, m, mode, k, first, rtol, atol, maxit, status);
 }
 
+constexpr const char *kBadDtype = "pn_krylov: dtype must be PN_F32 or PN_F64";
+
 int bad_args(int dtype, int64_t n, int restart, const void *state, const void *status) {
-  if (dtype != PN_F32 && dtype != PN_F64) return pn::fail("pn_krylov: dtype must be PN_F32 or PN_F64");
+  if (dtype != PN_F32 && dtype != PN_F64) return pn::fail(kBadDtype);
   if (n <= 0) return pn::fail("pn_krylov: empty vector");
   if (restart < 1 || restart > kMaxRestart) return pn::fail("pn_krylov: restart length must be in 1..126");
   if (!state || !status) return pn::fail("pn_krylov: state and status blocks required");
   return 0;
 }
 
-}  // namespace
+// the products / the update of one step in the vectors' dtype (refused like bad_args does, should it ever get here)
+int dots(int dtype, hipStream_t st, double *S, int m, int mode, int k, const void *w, const void *V, int64_t ldv, int64_t n, int defer,
+         int first, double rtol, double atol, double maxit, double *status) {
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    return launch_dots<decltype(t)>(st, S, m, mode, k, w, V, ldv, n, defer, first, rtol, atol, maxit, status);
+  });
+  return pn::or_fail(rc, kBadDtype);
+}
 
-#define PN_BY_DTYPE(CALL_F32, CALL_F64) (dtype == PN_F32 ? (CALL_F32) : (CALL_F64))
+int update(int dtype, hipStream_t st, const double *S, int m, int mode, int k, void *w, void *V, int64_t ldv, void *vin, int64_t n) {
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return launch_update<decltype(t)>(st, S, m, mode, k, w, V, ldv, vin, n); });
+  return pn::or_fail(rc, kBadDtype);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -550,14 +546,11 @@ int pn_krylov_begin(void *stream, int dtype, int64_t n, int restart, double *sta
   const int defer = part != 0;
   int rc = 0;
   if (part == 0 || part == 1)
-    rc = PN_BY_DTYPE(launch_dots<float>(st, state, restart, 0, 0, r, V, ldv, n, defer, first_cycle, rtol, atol, (double)maxit, status_dev),
-                     launch_dots<double>(st, state, restart, 0, 0, r, V, ldv, n, defer, first_cycle, rtol, atol, (double)maxit, status_dev));
+    rc = dots(dtype, st, state, restart, 0, 0, r, V, ldv, n, defer, first_cycle, rtol, atol, (double)maxit, status_dev);
   if (rc) return rc;
   if (part == 2) rc = launch_decide(st, state, restart, 0, 0, first_cycle, rtol, atol, (double)maxit, status_dev);
   if (rc) return rc;
-  if (part == 0 || part == 2)
-    rc = PN_BY_DTYPE(launch_update<float>(st, state, restart, 0, 0, const_cast<void *>(r), V, ldv, vin, n),
-                     launch_update<double>(st, state, restart, 0, 0, const_cast<void *>(r), V, ldv, vin, n));
+  if (part == 0 || part == 2) rc = update(dtype, st, state, restart, 0, 0, const_cast<void *>(r), V, ldv, vin, n);
   return rc;
 }
 
@@ -568,36 +561,28 @@ int pn_krylov_step(void *stream, int dtype, int64_t n, int restart, double *stat
   hipStream_t st = (hipStream_t)stream;
   const int defer = part != 0;
   int rc = 0;
-#define PN_DOTS(MODE)                                                                                              \
-  PN_BY_DTYPE(launch_dots<float>(st, state, restart, MODE, k, w, V, ldv, n, defer, 0, 0.0, 0.0, 0.0, status_dev),  \
-              launch_dots<double>(st, state, restart, MODE, k, w, V, ldv, n, defer, 0, 0.0, 0.0, 0.0, status_dev))
-#define PN_UPD(MODE)                                                             \
-  PN_BY_DTYPE(launch_update<float>(st, state, restart, MODE, k, w, V, ldv, vin, n), \
-              launch_update<double>(st, state, restart, MODE, k, w, V, ldv, vin, n))
-  if (part == 0 || part == 1) rc = PN_DOTS(1);                                      // pass 1 (+ decision unless deferred)
+  auto pass = [&](int mode) { return dots(dtype, st, state, restart, mode, k, w, V, ldv, n, defer, 0, 0.0, 0.0, 0.0, status_dev); };
+  auto upd = [&](int mode) { return update(dtype, st, state, restart, mode, k, w, V, ldv, vin, n); };
+  if (part == 0 || part == 1) rc = pass(1);                                        // pass 1 (+ decision unless deferred)
   if (rc || part == 1) return rc;
   if (part == 2) rc = launch_decide(st, state, restart, 1, k, 0, 0.0, 0.0, 0.0, status_dev);
   if (rc) return rc;
   if (part == 0 || part == 2) {
-    rc = PN_UPD(1);                                                                 // V_{k+1}, or w orthogonalised in place
-    if (!rc) rc = PN_DOTS(2);                                                       // pass 2: returns at entry unless due
+    rc = upd(1);                                                                    // V_{k+1}, or w orthogonalised in place
+    if (!rc) rc = pass(2);                                                          // pass 2: returns at entry unless due
   }
   if (rc || part == 2) return rc;
   if (part == 3) rc = launch_decide(st, state, restart, 2, k, 0, 0.0, 0.0, 0.0, status_dev);
   if (rc) return rc;
-  return PN_UPD(2);
-#undef PN_DOTS
-#undef PN_UPD
+  return upd(2);
 }
 
 int pn_krylov_close(void *stream, int dtype, int64_t n, int restart, double *state, double *status_dev, void *x, void *V,
                     int64_t ldv) {
   if (bad_args(dtype, n, restart, state, status_dev)) return 1;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(kr_close_kernel, dim3(1), dim3(kBlock), 0, st, state, restart, status_dev);
-  if (check_launch("pn_krylov_close")) return 1;
-  return PN_BY_DTYPE(launch_update<float>(st, state, restart, 3, 0, x, V, ldv, nullptr, n),
-                     launch_update<double>(st, state, restart, 3, 0, x, V, ldv, nullptr, n));
+  if (pn::launch("pn_krylov_close", kr_close_kernel, dim3(1), dim3(kBlock), st, state, restart, status_dev)) return 1;
+  return update(dtype, st, state, restart, 3, 0, x, V, ldv, nullptr, n);
 }
 
 }  // extern "C"

@@ -28,13 +28,12 @@
 // rows >= 256 (any number: a ragged last slab is zero-filled), out % 64 == 0, in % 64 == 0, out * in <= 2^22; everything else takes the general path (torch GEMM +
 // pn_colsum_accum_multi).
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include <cstdint>
 #include <string>
 #include <type_traits>
 
-#include "pn_internal.h"
+#include "pn_launch.h"
 #include "pnode_amd.h"
 
 namespace {
@@ -673,11 +672,12 @@ template <typename T>
 int finish_t(hipStream_t st, int64_t out_f, int64_t in_f, void *pw, void *pb, void *mu_w, void *mu_b) {
   const size_t mn = (size_t)out_f * (size_t)in_f;
   constexpr int VEC = 16 / (int)sizeof(T);
-  hipLaunchKernelGGL(pn_linear_wgrad_finish_kernel<T>, dim3((unsigned)((mn / VEC + 255) / 256)), dim3(256), 0, st, (T *)pw, mn, (T *)mu_w);
-  if (pb != nullptr && mu_b != nullptr)
-    hipLaunchKernelGGL(pn_linear_bgrad_finish_kernel<T>, dim3((unsigned)((out_f + 255) / 256)), dim3(256), 0, st, (double *)pb, (int)out_f,
-                       (int)(kSplit * (in_f / BN)), (T *)mu_b);
-  return 0;
+  const char *name = "pn_linear_wgrad_finish";
+  int rc = pn::launch(name, pn_linear_wgrad_finish_kernel<T>, dim3((unsigned)((mn / VEC + 255) / 256)), dim3(256), st, (T *)pw, mn, (T *)mu_w);
+  if (!rc && pb != nullptr && mu_b != nullptr)
+    rc = pn::launch(name, pn_linear_bgrad_finish_kernel<T>, dim3((unsigned)((out_f + 255) / 256)), dim3(256), st, (double *)pb, (int)out_f,
+                    (int)(kSplit * (in_f / BN)), (T *)mu_b);
+  return rc;
 }
 
 }  // namespace
@@ -709,7 +709,7 @@ int pn_linear_wgrad_group(void *stream, int dtype, int64_t rows, int npairs, con
     if (p < npairs) {
       if (!pn_linear_wgrad_supported(dtype, rows, q.out_f, q.in_f))
         return pn::fail("pn_linear_wgrad: unsupported dtype or shape (see pn_linear_wgrad_supported)");
-      if ((((uintptr_t)q.g) | ((uintptr_t)q.x) | ((uintptr_t)q.pw)) & 15) return pn::fail("pn_linear_wgrad: operands must be 16-byte aligned");
+      if (!pn::aligned16(q.g, q.x, q.pw)) return pn::fail("pn_linear_wgrad: operands must be 16-byte aligned");
       if (q.g == nullptr || q.x == nullptr || q.pw == nullptr) return pn::fail("pn_linear_wgrad: null operand");
     }
     a.g[p] = q.g, a.x[p] = q.x, a.pw[p] = q.pw, a.pb[p] = (double *)q.pb, a.alpha[p] = q.alpha;
@@ -734,32 +734,16 @@ int pn_linear_wgrad_group(void *stream, int dtype, int64_t rows, int npairs, con
   a.first[kMaxPairs] = (int)blocks;
   for (int p = npairs; p < kMaxPairs; ++p) a.first[p] = (int)blocks;
   if (blocks > (int64_t)1 << 30) return pn::fail("pn_linear_wgrad_group: too many workgroups");
-  void *v0 = nullptr, *v1 = nullptr;
-  const int prof = pn::prof_events(PN_K_LINEAR_WGRAD, flops, &v0, &v1);
-  hipEvent_t e0 = (hipEvent_t)v0, e1 = (hipEvent_t)v1;
-  if (prof < 0) return 1;
   hipStream_t st = (hipStream_t)stream;
   const bool ragged = rows % (kSplit * 32) != 0;
   if (wide) {
     auto kw = ragged ? pn_linear_wgrad_kernel_f32x3w_ragged : pn_linear_wgrad_kernel_f32x3w;
-    if (prof)
-      hipExtLaunchKernelGGL(kw, dim3((unsigned)blocks), dim3(1024), 0, st, e0, e1, 0, a);
-    else
-      hipLaunchKernelGGL(kw, dim3((unsigned)blocks), dim3(1024), 0, st, a);
-    hipError_t werr = hipGetLastError();
-    if (werr != hipSuccess) return pn::fail(std::string("pn_linear_wgrad: ") + hipGetErrorString(werr));
-    return 0;
+    return pn::launch(PN_K_LINEAR_WGRAD, flops, kw, dim3((unsigned)blocks), dim3(1024), st, a);
   }
   auto kern = dtype == PN_F64 ? (ragged ? pn_linear_wgrad_kernel_f64_ragged : pn_linear_wgrad_kernel_f64)
                               : ((flags & PN_WGRAD_EXACT_FP32) ? (ragged ? pn_linear_wgrad_kernel_f32_ragged : pn_linear_wgrad_kernel_f32)
                                                                : (ragged ? pn_linear_wgrad_kernel_f32x3_ragged : pn_linear_wgrad_kernel_f32x3));
-  if (prof)
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kThreads), 0, st, e0, e1, 0, a);
-  else
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pn::fail(std::string("pn_linear_wgrad: ") + hipGetErrorString(err));
-  return 0;
+  return pn::launch(PN_K_LINEAR_WGRAD, flops, kern, dim3((unsigned)blocks), dim3(kThreads), st, a);
 }
 
 int pn_linear_wgrad(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *x, double alpha,
@@ -771,14 +755,8 @@ int pn_linear_wgrad(void *stream, int dtype, int64_t rows, int64_t out_f, int64_
 
 int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f, void *pw, void *pb, void *mu_w, void *mu_b) {
   if (dtype != PN_F32 && dtype != PN_F64) return pn::fail("pn_linear_wgrad_finish: fp32 or fp64");
-  if ((((uintptr_t)pw) | ((uintptr_t)mu_w)) & 15) return pn::fail("pn_linear_wgrad_finish: operands must be 16-byte aligned");
-  if (dtype == PN_F32)
-    finish_t<float>((hipStream_t)stream, out_f, in_f, pw, pb, mu_w, mu_b);
-  else
-    finish_t<double>((hipStream_t)stream, out_f, in_f, pw, pb, mu_w, mu_b);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pn::fail(std::string("pn_linear_wgrad_finish: ") + hipGetErrorString(err));
-  return 0;
+  if (!pn::aligned16(pw, mu_w)) return pn::fail("pn_linear_wgrad_finish: operands must be 16-byte aligned");
+  return pn::with_dtype(dtype, [&](auto t) { return finish_t<decltype(t)>((hipStream_t)stream, out_f, in_f, pw, pb, mu_w, mu_b); });
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 #include <string>
 
 #include "pnode_amd.h"
-#include "pn_internal.h"
+#include "pn_launch.h"
 #include "pn_device.h"
 #include "pn_adapt.h"
 
@@ -317,8 +317,6 @@ __global__ __launch_bounds__(kBlock) void pn_rows_control_kernel(PnRowsCtl rc, c
   }
 }
 
-inline bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
 template <typename T>
 RowsGeom geom(int64_t B, int64_t d) {
   constexpr int VW = 16 / sizeof(T);
@@ -331,39 +329,7 @@ RowsGeom geom(int64_t B, int64_t d) {
   return q;
 }
 
-unsigned grid_for(const RowsGeom &q) {
-  const int64_t rpb = kBlock >> q.lgG;
-  int64_t nb = (q.B + rpb - 1) / rpb;
-  if (nb < 1) nb = 1;
-  return (unsigned)(nb > kRowsMaxBlocks ? kRowsMaxBlocks : nb);
-}
-
-int check_launch(const char *name) {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pn::fail(std::string(name) + ": " + hipGetErrorString(err));
-  return 0;
-}
-
-#define PN_ROWS_NK_SWITCH(nk, LO, CALL)                      \
-  switch (nk) {                                              \
-    case 0: if (LO == 0) { CALL(0); break; } return 1;       \
-    case 1: CALL(1); break;                                  \
-    case 2: CALL(2); break;                                  \
-    case 3: CALL(3); break;                                  \
-    case 4: CALL(4); break;                                  \
-    case 5: CALL(5); break;                                  \
-    case 6: CALL(6); break;                                  \
-    case 7: CALL(7); break;                                  \
-    default: return 1;                                       \
-  }
-
-template <typename T, bool VEC, bool HAS_BASE>
-int lin_launch(hipStream_t st, int nk, const RowsLinArgs<T> &a, const RowsGeom &q) {
-#define CALL(N) hipLaunchKernelGGL((pn_rows_lin_kernel<T, (N < 1 ? 1 : N), VEC, HAS_BASE>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q)
-  PN_ROWS_NK_SWITCH(nk, 1, CALL)
-#undef CALL
-  return 0;
-}
+dim3 grid_for(const RowsGeom &q) { return dim3((unsigned)pn::blocks_for(q.B, kBlock >> q.lgG, kRowsMaxBlocks)); }
 
 template <typename T>
 int rows_lin(hipStream_t st, int64_t B, int64_t d, void *out, const void *base, int nk, const void *const *x, const double *c,
@@ -373,26 +339,20 @@ int rows_lin(hipStream_t st, int64_t B, int64_t d, void *out, const void *base, 
   a.out = (T *)out;
   a.base = (const T *)base;
   a.h = h;
-  bool vec = (d % VW) == 0 && al16(out) && (!base || al16(base));
+  const bool vec = (d % VW) == 0 && pn::aligned16(out, base) && pn::aligned16(x, nk);
   for (int j = 0; j < nk; ++j) {
     a.x[j] = (const T *)x[j];
     a.c[j] = c[j];
-    vec = vec && al16(x[j]);
   }
   const RowsGeom q = geom<T>(B, d);
-  int rc;
-  if (base) rc = vec ? lin_launch<T, true, true>(st, nk, a, q) : lin_launch<T, false, true>(st, nk, a, q);
-  else rc = vec ? lin_launch<T, true, false>(st, nk, a, q) : lin_launch<T, false, false>(st, nk, a, q);
-  if (rc) return pn::fail(std::string(name) + ": nk out of range");
-  return check_launch(name);
-}
-
-template <typename T, bool VEC, bool WRITE>
-int err_launch(hipStream_t st, int nk, const RowsErrArgs<T> &a, const RowsGeom &q) {
-#define CALL(N) hipLaunchKernelGGL((pn_rows_combine_wrms_kernel<T, (N < 1 ? 1 : N), VEC, WRITE>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q)
-  PN_ROWS_NK_SWITCH(nk, 1, CALL)
-#undef CALL
-  return 0;
+  const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+    constexpr int NK = decltype(N)::value;
+    auto kern = base ? (vec ? pn_rows_lin_kernel<T, NK, true, true> : pn_rows_lin_kernel<T, NK, false, true>)
+                     : (vec ? pn_rows_lin_kernel<T, NK, true, false> : pn_rows_lin_kernel<T, NK, false, false>);
+    return pn::launch(name, kern, grid_for(q), dim3(kBlock), st, a, q);
+  });
+  if (rc == pn::kNoCase) return pn::fail(std::string(name) + ": nk out of range");
+  return rc;
 }
 
 template <typename T>
@@ -406,19 +366,20 @@ int rows_combine(hipStream_t st, int64_t B, int64_t d, void *unew, const void *u
   a.enorm = enorm;
   a.atol = atol;
   a.rtol = rtol;
-  bool vec = (d % VW) == 0 && al16(u) && (!unew || al16(unew));
+  const bool vec = (d % VW) == 0 && pn::aligned16(u, unew) && pn::aligned16(K, nk);
   for (int j = 0; j < nk; ++j) {
     a.k[j] = (const T *)K[j];
     a.cb[j] = cb ? cb[j] : 0.0;
     a.ce[j] = ce[j];
-    vec = vec && al16(K[j]);
   }
   const RowsGeom q = geom<T>(B, d);
-  int rc;
-  if (unew) rc = vec ? err_launch<T, true, true>(st, nk, a, q) : err_launch<T, false, true>(st, nk, a, q);
-  else rc = vec ? err_launch<T, true, false>(st, nk, a, q) : err_launch<T, false, false>(st, nk, a, q);
-  if (rc) return pn::fail("pn_rows_combine_wrms: nk out of range");
-  return check_launch("pn_rows_combine_wrms");
+  const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+    constexpr int NK = decltype(N)::value;
+    auto kern = unew ? (vec ? pn_rows_combine_wrms_kernel<T, NK, true, true> : pn_rows_combine_wrms_kernel<T, NK, false, true>)
+                     : (vec ? pn_rows_combine_wrms_kernel<T, NK, true, false> : pn_rows_combine_wrms_kernel<T, NK, false, false>);
+    return pn::launch("pn_rows_combine_wrms", kern, grid_for(q), dim3(kBlock), st, a, q);
+  });
+  return pn::or_fail(rc, "pn_rows_combine_wrms: nk out of range");
 }
 
 template <typename T>
@@ -434,19 +395,10 @@ int rows_commit(hipStream_t st, int64_t B, int64_t d, void *unext, const void *u
   a.hit = hit;
   a.ld = ld;
   a.nout = nout;
-  const bool vec = (d % VW) == 0 && al16(unext) && al16(u) && al16(unew) && (!sol || (al16(sol) && (ld % VW) == 0));
+  const bool vec = (d % VW) == 0 && pn::aligned16(unext, u, unew, sol) && (!sol || (ld % VW) == 0);
   const RowsGeom q = geom<T>(B, d);
-  if (vec) hipLaunchKernelGGL((pn_rows_commit_kernel<T, true>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q);
-  else hipLaunchKernelGGL((pn_rows_commit_kernel<T, false>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q);
-  return check_launch("pn_rows_commit");
-}
-
-template <typename T, bool VEC>
-int accum_launch(hipStream_t st, int nk, const RowsAccumArgs<T> &a, const RowsGeom &q) {
-#define CALL(N) hipLaunchKernelGGL((pn_rows_adj_accum_kernel<T, N, VEC>), dim3(grid_for(q)), dim3(kBlock), 0, st, a, q)
-  PN_ROWS_NK_SWITCH(nk, 0, CALL)
-#undef CALL
-  return 0;
+  return pn::launch("pn_rows_commit", vec ? pn_rows_commit_kernel<T, true> : pn_rows_commit_kernel<T, false>, grid_for(q), dim3(kBlock), st,
+                    a, q);
 }
 
 template <typename T>
@@ -460,15 +412,15 @@ int rows_accum(hipStream_t st, int64_t B, int64_t d, void *out, const void *lam,
   a.hit = hit;
   a.ld = ld;
   a.nout = nout;
-  bool vec = (d % VW) == 0 && al16(out) && al16(lam) && (!g || (al16(g) && (ld % VW) == 0));
-  for (int j = 0; j < nk; ++j) {
-    a.x[j] = (const T *)x[j];
-    vec = vec && al16(x[j]);
-  }
+  const bool vec = (d % VW) == 0 && pn::aligned16(out, lam, g) && (!g || (ld % VW) == 0) && pn::aligned16(x, nk);
+  for (int j = 0; j < nk; ++j) a.x[j] = (const T *)x[j];
   const RowsGeom q = geom<T>(B, d);
-  const int rc = vec ? accum_launch<T, true>(st, nk, a, q) : accum_launch<T, false>(st, nk, a, q);
-  if (rc) return pn::fail("pn_rows_adj_accum: nk out of range");
-  return check_launch("pn_rows_adj_accum");
+  const int rc = pn::with_count<0, PN_MAX_STAGES>(nk, [&](auto N) {
+    constexpr int NK = decltype(N)::value;
+    return pn::launch("pn_rows_adj_accum", vec ? pn_rows_adj_accum_kernel<T, NK, true> : pn_rows_adj_accum_kernel<T, NK, false>, grid_for(q),
+                      dim3(kBlock), st, a, q);
+  });
+  return pn::or_fail(rc, "pn_rows_adj_accum: nk out of range");
 }
 
 int bad_shape(const char *name, int64_t B, int64_t d) {
@@ -487,9 +439,8 @@ int pn_rows_stage(void *stream, int dtype, int64_t B, int64_t d, void *y, const 
   for (int j = 0; j < nk; ++j)
     if (!K[j]) return pn::fail("pn_rows_stage: null stage derivative");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return rows_lin<float>(st, B, d, y, u, nk, K, coef, h, "pn_rows_stage");
-  if (dtype == PN_F64) return rows_lin<double>(st, B, d, y, u, nk, K, coef, h, "pn_rows_stage");
-  return pn::fail("pn_rows_stage: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_lin<decltype(t)>(st, B, d, y, u, nk, K, coef, h, "pn_rows_stage"); });
+  return pn::or_fail(rc, "pn_rows_stage: unknown dtype");
 }
 
 int pn_rows_combine_wrms(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K,
@@ -500,9 +451,8 @@ int pn_rows_combine_wrms(void *stream, int dtype, int64_t B, int64_t d, void *un
   for (int j = 0; j < nk; ++j)
     if (!K[j]) return pn::fail("pn_rows_combine_wrms: null stage derivative");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return rows_combine<float>(st, B, d, unew, u, nk, K, coef_b, coef_e, h, atol, rtol, enorm);
-  if (dtype == PN_F64) return rows_combine<double>(st, B, d, unew, u, nk, K, coef_b, coef_e, h, atol, rtol, enorm);
-  return pn::fail("pn_rows_combine_wrms: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_combine<decltype(t)>(st, B, d, unew, u, nk, K, coef_b, coef_e, h, atol, rtol, enorm); });
+  return pn::or_fail(rc, "pn_rows_combine_wrms: unknown dtype");
 }
 
 int64_t pn_rows_work_bytes(int64_t B) {
@@ -518,10 +468,8 @@ int pn_rows_control(void *stream, const pn_ts *ts, int64_t B, int nspan, const d
     return pn::fail("pn_rows_control: null argument");
   PnRowsCtl rc;
   pn::rows_ctl_config(ts, nspan, max_time, &rc);
-  const unsigned nb = (unsigned)((B + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(pn_rows_control_kernel, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, rc, span_dev, B, enorm, sd, si,
-                     log_d, log_hit, accept, summary, (double *)work);
-  return check_launch("pn_rows_control");
+  return pn::launch("pn_rows_control", pn_rows_control_kernel, dim3((unsigned)pn::blocks_for(B, kBlock)), dim3(kBlock), (hipStream_t)stream,
+                    rc, span_dev, B, enorm, sd, si, log_d, log_hit, accept, summary, (double *)work);
 }
 
 int pn_rows_commit(void *stream, int dtype, int64_t B, int64_t d, void *unext, const void *u, const void *unew,
@@ -530,9 +478,8 @@ int pn_rows_commit(void *stream, int dtype, int64_t B, int64_t d, void *unext, c
   if (!unext || !u || !unew || !accept || (sol && (!hit || nout < 1 || ld < B * d)))
     return pn::fail("pn_rows_commit: null argument or an output stride shorter than a state");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return rows_commit<float>(st, B, d, unext, u, unew, accept, hit, sol, ld, nout);
-  if (dtype == PN_F64) return rows_commit<double>(st, B, d, unext, u, unew, accept, hit, sol, ld, nout);
-  return pn::fail("pn_rows_commit: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_commit<decltype(t)>(st, B, d, unext, u, unew, accept, hit, sol, ld, nout); });
+  return pn::or_fail(rc, "pn_rows_commit: unknown dtype");
 }
 
 int pn_rows_adj_theta(void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam, int nk,
@@ -553,9 +500,8 @@ int pn_rows_adj_theta(void *stream, int dtype, int64_t B, int64_t d, void *w, co
     c[n++] = coef[j];
   }
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return rows_lin<float>(st, B, d, w, nullptr, n, x, c, h, "pn_rows_adj_theta");
-  if (dtype == PN_F64) return rows_lin<double>(st, B, d, w, nullptr, n, x, c, h, "pn_rows_adj_theta");
-  return pn::fail("pn_rows_adj_theta: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_lin<decltype(t)>(st, B, d, w, nullptr, n, x, c, h, "pn_rows_adj_theta"); });
+  return pn::or_fail(rc, "pn_rows_adj_theta: unknown dtype");
 }
 
 int pn_rows_adj_accum(void *stream, int dtype, int64_t B, int64_t d, void *lambda_out, const void *lambda, int nk,
@@ -566,9 +512,8 @@ int pn_rows_adj_accum(void *stream, int dtype, int64_t B, int64_t d, void *lambd
   for (int j = 0; j < nk; ++j)
     if (!dlam[j]) return pn::fail("pn_rows_adj_accum: null vector");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return rows_accum<float>(st, B, d, lambda_out, lambda, nk, dlam, g, ld, hit, nout);
-  if (dtype == PN_F64) return rows_accum<double>(st, B, d, lambda_out, lambda, nk, dlam, g, ld, hit, nout);
-  return pn::fail("pn_rows_adj_accum: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_accum<decltype(t)>(st, B, d, lambda_out, lambda, nk, dlam, g, ld, hit, nout); });
+  return pn::or_fail(rc, "pn_rows_adj_accum: unknown dtype");
 }
 
 }  // extern "C"

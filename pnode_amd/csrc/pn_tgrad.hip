@@ -14,7 +14,7 @@
 #include <string>
 
 #include "pnode_amd.h"
-#include "pn_internal.h"
+#include "pn_launch.h"
 #include "pn_device.h"
 
 namespace {
@@ -153,76 +153,36 @@ __global__ __launch_bounds__(kBlock) void pn_rk_dense_tgrad_kernel(TgDenseArgs<T
   }
 }
 
-inline bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-int64_t grid_for(int64_t nvec) {
-  int64_t nb = (nvec + kBlock - 1) / kBlock;
-  if (nb < 1) nb = 1;
-  return nb > kTgMaxBlocks ? kTgMaxBlocks : nb;
-}
-
-int check_launch(const char *name) {
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return pn::fail(std::string(name) + ": " + hipGetErrorString(err));
-  return 0;
-}
-
-template <typename T, int NP>
-int dots_np(hipStream_t st, const TgDotArgs<T> &a, double *work, int64_t n, bool vec) {
-  constexpr int VW = 16 / sizeof(T);
-  if (vec) {
-    const int64_t nvec = n / VW;
-    hipLaunchKernelGGL((pn_tgrad_dots_kernel<T, NP, VW>), dim3((unsigned)grid_for(nvec)), dim3(kBlock), 0, st, a, work, nvec, n);
-  } else {
-    hipLaunchKernelGGL((pn_tgrad_dots_kernel<T, NP, 1>), dim3((unsigned)grid_for(n)), dim3(kBlock), 0, st, a, work, n, n);
-  }
-  return check_launch("pn_tgrad_dots");
-}
-
 template <typename T>
 int tgrad_dots(hipStream_t st, int64_t n, int np, const void *const *x, const void *const *y, const double *coef, void *work,
                double *acc, int accumulate) {
   TgDotArgs<T> a = {};
-  bool vec = true;
+  const bool vec = pn::aligned16(x, np) && pn::aligned16(y, np);
   for (int p = 0; p < np; ++p) {
     a.x[p] = (const T *)x[p];
     a.y[p] = (const T *)y[p];
     a.c[p] = coef[p];
-    vec = vec && al16(x[p]) && al16(y[p]);
   }
   a.acc = acc;
   a.accumulate = accumulate ? 1 : 0;
   double *w = (double *)work;
-  switch (np) {
-    case 1: return dots_np<T, 1>(st, a, w, n, vec);
-    case 2: return dots_np<T, 2>(st, a, w, n, vec);
-    case 3: return dots_np<T, 3>(st, a, w, n, vec);
-    case 4: return dots_np<T, 4>(st, a, w, n, vec);
-    case 5: return dots_np<T, 5>(st, a, w, n, vec);
-    case 6: return dots_np<T, 6>(st, a, w, n, vec);
-    case 7: return dots_np<T, 7>(st, a, w, n, vec);
-  }
-  return pn::fail("pn_tgrad_dots: np must be 1..7");
-}
-
-template <typename T, int NK>
-int dense_nk(hipStream_t st, const TgDenseArgs<T> &a, double *work, int64_t n, bool vec) {
-  constexpr int VW = 16 / sizeof(T);
-  if (vec) {
-    const int64_t nvec = n / VW;
-    hipLaunchKernelGGL((pn_rk_dense_tgrad_kernel<T, NK, VW>), dim3((unsigned)grid_for(nvec)), dim3(kBlock), 0, st, a, work, nvec, n);
-  } else {
-    hipLaunchKernelGGL((pn_rk_dense_tgrad_kernel<T, NK, 1>), dim3((unsigned)grid_for(n)), dim3(kBlock), 0, st, a, work, n, n);
-  }
-  return check_launch("pn_rk_dense_tgrad");
+  const int rc = pn::with_count<1, PN_MAX_STAGES>(np, [&](auto N) {
+    return pn::with_width<T>(vec, [&](auto W) {
+      constexpr int NP = decltype(N)::value, VW = decltype(W)::value;
+      const int64_t nvec = n / VW;
+      return pn::launch("pn_tgrad_dots", pn_tgrad_dots_kernel<T, NP, VW>, dim3((unsigned)pn::blocks_for(nvec, kBlock, kTgMaxBlocks)),
+                        dim3(kBlock), st, a, w, nvec, n);
+    });
+  });
+  return pn::or_fail(rc, "pn_tgrad_dots: np must be 1..7");
 }
 
 template <typename T>
 int dense_tgrad(hipStream_t st, int64_t n, int m, const void *g, int64_t ld, int nk, const void *const *K, const double *coef,
                 void *work, double *acc, int accumulate) {
   constexpr int VW = 16 / sizeof(T);
-  bool vec = al16(g) && (ld % VW) == 0;
-  for (int j = 0; j < nk; ++j) vec = vec && al16(K[j]);
+  const bool vec = pn::aligned16(g) && (ld % VW) == 0 && pn::aligned16(K, nk);
+  double *w = (double *)work;
   for (int o0 = 0; o0 < m; o0 += PN_DENSE_CHUNK) {
     TgDenseArgs<T> a = {};
     a.g = (const T *)g + (int64_t)o0 * ld;
@@ -233,19 +193,15 @@ int dense_tgrad(hipStream_t st, int64_t n, int m, const void *g, int64_t ld, int
     for (int j = 0; j < nk; ++j) a.k[j] = (const T *)K[j];
     for (int o = 0; o < a.m; ++o)
       for (int j = 0; j < nk; ++j) a.c[o][j] = coef[(int64_t)(o0 + o) * nk + j];
-    int rc = 1;
-    double *w = (double *)work;
-    switch (nk) {
-      case 1: rc = dense_nk<T, 1>(st, a, w, n, vec); break;
-      case 2: rc = dense_nk<T, 2>(st, a, w, n, vec); break;
-      case 3: rc = dense_nk<T, 3>(st, a, w, n, vec); break;
-      case 4: rc = dense_nk<T, 4>(st, a, w, n, vec); break;
-      case 5: rc = dense_nk<T, 5>(st, a, w, n, vec); break;
-      case 6: rc = dense_nk<T, 6>(st, a, w, n, vec); break;
-      case 7: rc = dense_nk<T, 7>(st, a, w, n, vec); break;
-      default: return pn::fail("pn_rk_dense_tgrad: nk must be 1..7");
-    }
-    if (rc) return rc;
+    const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+      return pn::with_width<T>(vec, [&](auto W) {
+        constexpr int NK = decltype(N)::value, VW = decltype(W)::value;
+        const int64_t nvec = n / VW;
+        return pn::launch("pn_rk_dense_tgrad", pn_rk_dense_tgrad_kernel<T, NK, VW>, dim3((unsigned)pn::blocks_for(nvec, kBlock, kTgMaxBlocks)),
+                          dim3(kBlock), st, a, w, nvec, n);
+      });
+    });
+    if (rc) return pn::or_fail(rc, "pn_rk_dense_tgrad: nk must be 1..7");
   }
   return 0;
 }
@@ -267,9 +223,8 @@ int pn_tgrad_dots(void *stream, int dtype, int64_t n, int np, const void *const 
     if (!x[p] || !y[p]) return pn::fail("pn_tgrad_dots: null vector");
   if (n < 0) return pn::fail("pn_tgrad_dots: negative length");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return tgrad_dots<float>(st, n, np, x, y, coef, work, acc, accumulate);
-  if (dtype == PN_F64) return tgrad_dots<double>(st, n, np, x, y, coef, work, acc, accumulate);
-  return pn::fail("pn_tgrad_dots: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return tgrad_dots<decltype(t)>(st, n, np, x, y, coef, work, acc, accumulate); });
+  return pn::or_fail(rc, "pn_tgrad_dots: unknown dtype");
 }
 
 int pn_rk_dense_tgrad(void *stream, int dtype, int64_t n, int m, const void *g, int64_t ld, int nk, const void *const *K,
@@ -282,9 +237,8 @@ int pn_rk_dense_tgrad(void *stream, int dtype, int64_t n, int m, const void *g, 
   for (int j = 0; j < nk; ++j)
     if (!K[j]) return pn::fail("pn_rk_dense_tgrad: null stage derivative");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == PN_F32) return dense_tgrad<float>(st, n, m, g, ld, nk, K, coef, work, acc, accumulate);
-  if (dtype == PN_F64) return dense_tgrad<double>(st, n, m, g, ld, nk, K, coef, work, acc, accumulate);
-  return pn::fail("pn_rk_dense_tgrad: unknown dtype");
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return dense_tgrad<decltype(t)>(st, n, m, g, ld, nk, K, coef, work, acc, accumulate); });
+  return pn::or_fail(rc, "pn_rk_dense_tgrad: unknown dtype");
 }
 
 }  // extern "C"

@@ -85,6 +85,102 @@ def test_the_wgrad_pair_struct_matches_the_header_layout():
     assert lib.pn_linear_wgrad_work_bytes(_lib.PN_F64, 512, 512, None) == 8 * 512 * 512 * 8
 
 
+def _refusal_table():
+    """name -> (call(dtype, count), (lowest, highest) count or None, text for a count outside it, text for an unknown dtype).
+    Operands are host buffers (never dereferenced: every refusal comes before a launch); the pointer tables, which the
+    host does read, are real arrays."""
+    lib = _lib.load()
+    buf = (ctypes.c_double * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    tab = (ctypes.c_void_p * 9)(*([p.value] * 9))
+    mtab = (ctypes.c_void_p * 9)(*([p.value] * 9))
+    coef = (ctypes.c_double * 128)(*([0.5] * 128))
+    one = (ctypes.c_int64 * 1)(4)
+    zero = (ctypes.c_int64 * 1)(0)
+    generic = b"dtype must be PN_F32 or PN_F64"
+    return {
+        "pn_lincomb": (lambda dt, k: lib.pn_lincomb(None, dt, 8, p, k, tab, coef), (1, 8),
+                       b"pn_lincomb: between 1 and 8 input vectors", generic),
+        "pn_rk_stage": (lambda dt, k: lib.pn_rk_stage(None, dt, 8, p, p, k, tab, coef), (0, 7),
+                        b"pn_rk_stage: nk out of range", generic),
+        "pn_adj_theta": (lambda dt, k: lib.pn_adj_theta(None, dt, 8, p, p, 0.5, k, tab, coef), (0, 7),
+                         b"pn_adj_theta: nk out of range", generic),
+        "pn_adj_accum": (lambda dt, k: lib.pn_adj_accum(None, dt, 8, p, p, k, tab, coef, None, None, 0.0), (0, 7),
+                         b"pn_adj_accum: nk out of range", generic),
+        "pn_rk_combine_wrms": (lambda dt, k: lib.pn_rk_combine_wrms(None, dt, 8, p, p, k, tab, coef, coef, 1e-6, 1e-6, p, p), (1, 7),
+                               b"combine_wrms: between 1 and 7 stage derivatives supported", generic),
+        "pn_dots": (lambda dt, k: lib.pn_dots(None, dt, 8, p, k, tab, p, p), (1, 8),
+                    b"pn_dots: between 1 and 8 vectors per call", generic),
+        "pn_rk_dense_eval": (lambda dt, k: lib.pn_rk_dense_eval(None, dt, 8, p, k, tab, 2, coef, p, 8, 0), (1, 7),
+                             b"pn_rk_dense_eval: nk must be 1..7", b"pn_rk_dense_eval: unknown dtype"),
+        "pn_rk_dense_adjoint": (lambda dt, k: lib.pn_rk_dense_adjoint(None, dt, 8, 2, p, 8, k, coef, tab, p, 0), (0, 7),
+                                b"pn_rk_dense_adjoint: nd must be 0..7", b"pn_rk_dense_adjoint: unknown dtype"),
+        "pn_tgrad_dots": (lambda dt, k: lib.pn_tgrad_dots(None, dt, 8, k, tab, tab, coef, p, p, 0), (1, 7),
+                          b"pn_tgrad_dots: np must be 1..7", b"pn_tgrad_dots: unknown dtype"),
+        "pn_rk_dense_tgrad": (lambda dt, k: lib.pn_rk_dense_tgrad(None, dt, 8, 2, p, 8, k, tab, coef, p, p, 0), (1, 7),
+                              b"pn_rk_dense_tgrad: nk must be 1..7", b"pn_rk_dense_tgrad: unknown dtype"),
+        "pn_rows_stage": (lambda dt, k: lib.pn_rows_stage(None, dt, 2, 4, p, p, k, tab, coef, p), (1, 7),
+                          b"pn_rows_stage: null argument or nk outside 1..7", b"pn_rows_stage: unknown dtype"),
+        "pn_rows_combine_wrms": (lambda dt, k: lib.pn_rows_combine_wrms(None, dt, 2, 4, p, p, k, tab, coef, coef, p, 1e-6, 1e-6, p), (1, 7),
+                                 b"pn_rows_combine_wrms: null argument or nk outside 1..7", b"pn_rows_combine_wrms: unknown dtype"),
+        "pn_rows_adj_theta": (lambda dt, k: lib.pn_rows_adj_theta(None, dt, 2, 4, p, p, 0.5, k, tab, coef, p), (0, 6),
+                              b"pn_rows_adj_theta: null argument or nk outside 0..6", b"pn_rows_adj_theta: unknown dtype"),
+        "pn_rows_adj_accum": (lambda dt, k: lib.pn_rows_adj_accum(None, dt, 2, 4, p, p, k, tab, None, 0, None, 0), (0, 7),
+                              b"pn_rows_adj_accum: null argument, nk outside 0..7 or a cotangent stride shorter than a state",
+                              b"pn_rows_adj_accum: unknown dtype"),
+        # no run-time count to dispatch on: the dtype column alone
+        "pn_rows_commit": (lambda dt, k: lib.pn_rows_commit(None, dt, 2, 4, p, p, p, p, None, None, 0, 0), None, None,
+                           b"pn_rows_commit: unknown dtype"),
+        "pn_param_accum": (lambda dt, k: lib.pn_param_accum(None, dt, p, 0.5, 1, tab, zero, one), None, None, generic),
+        "pn_param_accum_multi": (lambda dt, k: lib.pn_param_accum_multi(None, dt, p, 1, coef, 1, tab, zero, one), None, None, generic),
+        "pn_colsum_accum_multi": (lambda dt, k: lib.pn_colsum_accum_multi(None, dt, 1, one, one, tab, mtab, coef, p), None, None, generic),
+        "pn_krylov_begin": (lambda dt, k: lib.pn_krylov_begin(None, dt, 8, 4, p, p, p, p, 8, p, 1e-6, 1e-6, 10, 1, 0), None, None,
+                            b"pn_krylov: dtype must be PN_F32 or PN_F64"),
+        "pn_linear_wgrad_finish": (lambda dt, k: lib.pn_linear_wgrad_finish(None, dt, 64, 64, p, None, p, None), None, None,
+                                   b"pn_linear_wgrad_finish: fp32 or fp64"),
+    }
+
+
+_REFUSALS = ["pn_lincomb", "pn_rk_stage", "pn_adj_theta", "pn_adj_accum", "pn_rk_combine_wrms", "pn_dots", "pn_rk_dense_eval",
+             "pn_rk_dense_adjoint", "pn_tgrad_dots", "pn_rk_dense_tgrad", "pn_rows_stage", "pn_rows_combine_wrms",
+             "pn_rows_adj_theta", "pn_rows_adj_accum", "pn_rows_commit", "pn_param_accum", "pn_param_accum_multi", "pn_colsum_accum_multi",
+             "pn_krylov_begin", "pn_linear_wgrad_finish"]
+
+
+@pytest.mark.parametrize("name", _REFUSALS)
+def test_dispatching_entry_points_refuse_an_unknown_dtype_and_a_count_outside_their_range(name):
+    """Every entry point that turns a run-time dtype or operand count into a kernel instantiation refuses what it has no
+    instantiation for BEFORE it launches anything, with exactly these texts (clients match on them; a count mapped to
+    the wrong instantiation would read a null pointer on the device instead)."""
+    lib = _lib.load()
+    table = _refusal_table()
+    assert sorted(table) == sorted(_REFUSALS)
+    call, span, count_text, dtype_text = table[name]
+    for dtype in (7, -1):
+        assert call(dtype, span[0] if span else 0) != 0
+        assert lib.pn_last_error() == dtype_text
+    if span:
+        for dtype in (_lib.PN_F32, _lib.PN_F64):
+            for count in (span[0] - 1, span[1] + 1):
+                assert call(dtype, count) != 0
+                assert lib.pn_last_error() == count_text, (dtype, count)
+
+
+def test_param_accum_refuses_an_unknown_dtype_even_with_no_segment_to_add():
+    """pn_param_accum picks its element type before it looks at the segments: an unknown dtype is refused whether or not
+    a segment is live (absent tensor, zero length, nseg = 0), and a known dtype with nothing to add launches nothing."""
+    lib = _lib.load()
+    buf = (ctypes.c_double * 8)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    tab, absent = (ctypes.c_void_p * 1)(p.value), (ctypes.c_void_p * 1)(None)
+    off, four, none = (ctypes.c_int64 * 1)(0), (ctypes.c_int64 * 1)(4), (ctypes.c_int64 * 1)(0)
+    for nseg, g, length in ((0, tab, four), (1, absent, four), (1, tab, none)):
+        assert lib.pn_param_accum(None, 7, p, 0.5, nseg, g, off, length) != 0
+        assert lib.pn_last_error() == b"dtype must be PN_F32 or PN_F64"
+        for dtype in (_lib.PN_F32, _lib.PN_F64):
+            assert lib.pn_param_accum(None, dtype, p, 0.5, nseg, g, off, length) == 0
+
+
 @pytest.mark.parametrize("name", ["1fe", "midpoint", "2a", "2b", "3", "3bs", "4", "5f", "5dp"])
 def test_tableaus_equal_the_oracles(name):
     a = _lib.get_tableau(name)

@@ -44,3 +44,18 @@ def test_disk_tier_engine_under_sanitizers(tmp_path, sanitizer):
     out = subprocess.run([exe, str(tmp_path)], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert "spill selftest ok" in out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_dispatch_helpers_under_asan_ubsan(tmp_path):
+    """pn_dispatch.h with the host compiler alone (no HIP header): with_count reaches exactly the instantiation of its
+    count for the three ranges the launchers use, with_dtype / with_width pick what they should, blocks_for rounds and caps."""
+    exe = str(tmp_path / "dispatch_check")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "pnode_amd", "csrc"),
+           os.path.join(ROOT, "tests", "native", "dispatch_check.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run([exe], env=env, capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "dispatch check ok" in out.stdout
