@@ -450,6 +450,35 @@ int pn_rows_adj_theta(void *stream, int dtype, int64_t B, int64_t d, void *w, co
  * the closing update of a reversed round with the masked forcing (pa.py:938 per row). */
 int pn_rows_adj_accum(void *stream, int dtype, int64_t B, int64_t d, void *lambda_out, const void *lambda, int nk,
                       const void *const *dlam, const void *g, int64_t ld, const int32_t *hit, int nout);
+/* -pn_adapt_scope sample with -pn_output_times interpolate: the controller sees [t[0], t[nout-1]] only and the rows serve
+ * the output times themselves.  times_dev: the nout output times on the device; next: int32 [B], the row's first output
+ * not yet served (1 at the start of a solve); P: the used rows of pn_tableau_dense's table, [nk][PN_DENSE_MAX_POW]
+ * (kernel arguments); log_d / log_hit: the round's log as pn_rows_control has just written it; tnew: the times the
+ * controller wrote (row PN_ROWS_T of sd).
+ * pn_rows_dense_eval, after an accepted attempt of row r from t_r with h_r to tnew_r: the outputs next <= o <= nout-2 with
+ * times[o] < tnew_r become sol[o*ld + r*d ..] = u[r] + sum_j c_j K[j][r], c_j = h_r beta_j((times[o] - t_r)/h_r) formed
+ * in double as ODEPetsc._dense_coefs forms it (Horner from the highest power, then h * v) and rounded once; u first, then
+ * fma in j order.  An output with times[o] == tnew_r, and output nout-1 when log_hit[r] >= 0 on entry (the controller
+ * landed on the final time), is a copy of unew[r].  Written back: next, range = int32 [2][B] (the row's [lo, hi) of this
+ * round) and log_hit[r] = the output copied or -1 (what pn_rows_adj_accum's masked forcing reads in the reverse sweep).
+ * Rejected and finished rows (h_eff == 0) serve nothing; rows of sol outside a row's range are not touched.  A row's
+ * bits do not depend on B or on the other rows.  pn_rows_dense_plan_host: the same plan on host arrays (no device);
+ * next == NULL: range is given and only coefficients are formed; coef (may be NULL): [nout][B][nk], entries
+ * (o, r, .) written for lo_r <= o < hi_r. */
+int pn_rows_dense_eval(void *stream, int dtype, int64_t B, int64_t d, const void *u, int nk, const void *const *K,
+                       const double *P, const void *unew, void *sol, int64_t ld, int nout, const double *times_dev,
+                       const double *log_d, const double *tnew, int32_t *log_hit, int32_t *next, int32_t *range);
+int pn_rows_dense_plan_host(int64_t B, int nout, const double *times, const double *log_d, const double *tnew,
+                            int32_t *log_hit, int32_t *next, int32_t *range, int nk, const double *P, double *coef);
+/* The transpose for a reversed round: D[j][r] = sum_{lo_r <= o < hi_r} c_{o,j,r} g[o*ld + r*d ..] (from zero, fma, o
+ * ascending) for the nd used columns and G[r] = sum_o g[o*ld + r*d ..]; rows with an empty range get zeros. */
+int pn_rows_dense_adjoint(void *stream, int dtype, int64_t B, int64_t d, const void *g, int64_t ld, int nout,
+                          const double *times_dev, const double *log_d, const int32_t *range, int nd, const double *P,
+                          void *const *D, void *G);
+/* pn_rows_adj_theta with one more source, added last and NOT scaled by h[r] (pn_rk_adjoint_step_dense's D_i per row):
+ * w[r] = (h[r]*c_lam) lambda[r] + sum_{j<nk} (h[r]*coef[j]) dlam[j][r] + dense_w[r]. */
+int pn_rows_adj_theta_dense(void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam,
+                            int nk, const void *const *dlam, const double *coef, const double *h, const void *dense_w);
 
 /* ------------------------------------------------------------------------------------------
  * 3b. GMRES core for the implicit (theta-method) stage solves: the small dense part of

@@ -89,6 +89,10 @@ PROTOTYPES = {
     "pn_rows_commit": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i]),
     "pn_rows_adj_theta": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _d, _i, _pvp, _pd, _vp]),
     "pn_rows_adj_accum": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _vp, _i64, _vp, _i]),
+    "pn_rows_dense_eval": (_i, [_vp, _i, _i64, _i64, _vp, _i, _pvp, _pd, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pn_rows_dense_plan_host": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _pd, _vp]),
+    "pn_rows_dense_adjoint": (_i, [_vp, _i, _i64, _i64, _vp, _i64, _i, _vp, _vp, _vp, _i, _pd, _pvp, _vp]),
+    "pn_rows_adj_theta_dense": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _d, _i, _pvp, _pd, _vp, _vp]),
     "pn_last_error": (_cp, []),
     "pn_abi_version": (_i, []),
     "pn_tableau_get": (_i, [_cp, ctypes.POINTER(Tableau)]),

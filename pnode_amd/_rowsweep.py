@@ -6,7 +6,12 @@ advance together in ROUNDS: one step attempt of every unfinished row, with func 
 (``t`` is a float64 tensor of shape (B, 1, ..., 1)).  The per-row controller runs on the device (pn_rows_control: the text of
 pn_ts_judge); the host reads one small summary per round.  The round log (per round and row: h_eff = the step size where the
 attempt was accepted, else 0; the times; the output index the row landed on) is all the reverse sweep needs: a round with
-h_eff = 0 is the identity on that row in both sweeps, so the rounds are reversed in order with no per-row control flow."""
+h_eff = 0 is the identity on that row in both sweeps, so the rounds are reversed in order with no per-row control flow.
+
+With ``-pn_output_times interpolate`` (a backend with the row-dense entry points, ``rows_dense``) the controller sees
+``[t[0], t[-1]]`` only: every row takes the steps its own tolerance asks for, and after each round pn_rows_dense_eval fills the
+output times an accepted attempt has passed from the tableau's continuous extension (the output times and a per-row "next
+output" counter live on the device; the round's log grows by the range [lo, hi) of outputs each row interpolated)."""
 import ctypes
 import warnings
 
@@ -21,6 +26,7 @@ _LOG_BLOCK = 64          # rounds per allocation of the round log
 class RowSweep(object):
     _sample = False
     _rows_probe = False
+    _rdense = False          # the last per-sample solve interpolated its outputs
     rounds = 0
     sample_steps = None
     sample_rejections = None
@@ -36,8 +42,9 @@ class RowSweep(object):
                           "-ts_adapt_type basic" % opt)
         if len(self.tensor_size) < 2:
             raise PnError("%s: the first dimension of the state is the batch; a 1-D state has no rows to control" % opt)
-        if self._dense:
-            raise PnError("%s cannot be combined with -pn_output_times interpolate" % opt)
+        if self._dense and not getattr(self._ops, "rows_dense", False):
+            # (a tableau without a continuous extension has been refused by ts_tableau_dense before)
+            raise PnError("%s cannot be combined with -pn_output_times interpolate on this backend" % opt)
         if self._max_cps > 0:
             raise PnError("%s cannot be combined with -ts_trajectory_max_cps_ram / -ts_trajectory_max_cps_disk" % opt)
         if self._traj_disk:
@@ -88,8 +95,12 @@ class RowSweep(object):
 
     # ------------------------------------------------------------------ helpers
     def _rows_log_at(self, k):
-        bd, bh = self._rlog[k // _LOG_BLOCK]
-        return bd[k % _LOG_BLOCK], bh[k % _LOG_BLOCK]
+        blk = self._rlog[k // _LOG_BLOCK]
+        return blk[0][k % _LOG_BLOCK], blk[1][k % _LOG_BLOCK]
+
+    def _rows_range_at(self, k):
+        """int32 [2][B]: the outputs [lo, hi) every row interpolated in round k (-pn_output_times interpolate)."""
+        return self._rlog[k // _LOG_BLOCK][2][k % _LOG_BLOCK]
 
     def _rows_t(self, tvec):
         """The time argument of func: float64, one entry per row, broadcastable against the state."""
@@ -144,13 +155,25 @@ class RowSweep(object):
         solution = ops.empty((T,) + tuple(self.tensor_size))
         sol_flat = solution.view(T, -1)
         u0f = u0.detach().contiguous().reshape(-1)
+        # -pn_output_times interpolate: the controller sees the end points only; t[1:-1] are filled by rows_dense_eval
+        rd = self._rdense = self._dense and T > 2
+        full_T, full_sol = T, sol_flat
+        if rd:
+            if any(not (b > a) for a, b in zip(times, times[1:])):
+                raise PnError("-pn_output_times interpolate: the output times must be strictly increasing")
+            times_dev = self._rtimes = self.sol_times.to(self.device)
+            T, times, sol_flat = 2, [times[0], times[-1]], sol_flat[:: T - 1]
+            cols = self._dense_cols
+            pv = [v for j in cols for v in list(self._dense_P[j]) + [0.0] * (_lib.PN_DENSE_MAX_POW - len(self._dense_P[j]))]
+            P = self._rP = (ctypes.c_double * len(pv))(*pv)
+            nxt_out = ops.i32(B)
+            nxt_out.fill_(1)                     # times[0] is the initial condition itself
         # the first step of every row: the host engine's own MATCHSTEP clamp at the start of a solve (pn_ts_begin)
         check(lib.pn_ts_begin(ts, 0.0, dt0, T, (ctypes.c_double * T)(*times)))
         t0 = 0.0 if T == 1 else times[0]
         self._rlog, self._rtraj, self._rY = [], ([] if save else None), None
         self._rows_probe = True                    # the first evaluation of this solve is still to come
         self.rounds = 0
-        self._rT = T
         sd, si = ops.f64(4, B), ops.i32(8, B)
         self._rsi = si
         cur = ops.empty(n)
@@ -162,7 +185,7 @@ class RowSweep(object):
             for i in range(T):
                 ops.copy(sol_flat[i], u0f)
             si[0].fill_(T)
-            self._rows_finish(si, B, T)
+            self._rows_finish(si[0], si, B, T)
             return solution
         tt, hh = ctypes.c_double(), ctypes.c_double()
         check(lib.pn_ts_attempt(ts, ctypes.byref(tt), ctypes.byref(hh)))
@@ -187,7 +210,7 @@ class RowSweep(object):
         k = 0
         while True:
             if k % _LOG_BLOCK == 0:
-                self._rlog.append((ops.f64(_LOG_BLOCK, 3, B), ops.i32(_LOG_BLOCK, B)))
+                self._rlog.append((ops.f64(_LOG_BLOCK, 3, B), ops.i32(_LOG_BLOCK, B)) + ((ops.i32(_LOG_BLOCK, 2, B),) if rd else ()))
             log_d, log_hit = self._rows_log_at(k)
             h, tr = sd[1], sd[0]
             unew = unew_buf[k % 2]
@@ -213,7 +236,14 @@ class RowSweep(object):
                     self._rY.append(Ybuf)
             else:
                 nxt = pp[k % 2]
-            ops.rows_commit(B, d, nxt, cur, unew, accept, log_hit, sol_flat, n, T)
+            if rd:
+                # the outputs this round's accepted attempts have passed, and the copies of the new state (an exact landing, the
+                # final time): log_hit becomes the output copied, as the reverse sweep's masked forcing reads it
+                ops.rows_dense_eval(B, d, full_sol, times_dev, cur, [K[j] for j in cols], P, unew, log_d, sd[0], log_hit, nxt_out,
+                                    self._rows_range_at(k))
+                ops.rows_commit(B, d, nxt, cur, unew, accept, None, None, 0, 0)
+            else:
+                ops.rows_commit(B, d, nxt, cur, unew, accept, log_hit, sol_flat, n, T)
             cur = nxt
             k += 1
             self.rounds = k
@@ -226,21 +256,23 @@ class RowSweep(object):
                       % (k, float(sd[0].min()), float(sd[0].max()), float(sd[1].min()), float(sd[1].max()), nopen))
             if nopen == 0:
                 break
-        self._rows_finish(si, B, T)
+        self._rows_finish(nxt_out if rd else si[0], si, B, full_T)
         if self._view:
             print("TS Object (pnode_amd): type rk, -pn_adapt_scope sample: %d rounds for %d rows, accepted steps per row %d..%d, "
-                  "rejected %d..%d; launches: %s" % (self.rounds, B, int(self.sample_steps.min()), int(self.sample_steps.max()),
-                                                     int(self.sample_rejections.min()), int(self.sample_rejections.max()),
-                                                     self._graph_status))
+                  "rejected %d..%d; output times: %s; launches: %s"
+                  % (self.rounds, B, int(self.sample_steps.min()), int(self.sample_steps.max()),
+                     int(self.sample_rejections.min()), int(self.sample_rejections.max()),
+                     "interpolate (per row, continuous extension of order %d)" % self._dense_order if rd else "match", self._graph_status))
         return solution
 
-    def _rows_finish(self, si, B, T):
+    def _rows_finish(self, served, si, B, T):
+        """`served`: per row, the number of output times it has reached (the span counter, or the rows' own counter)."""
         host = si.cpu()
         self.sample_steps = host[1].clone()
         self.sample_rejections = host[2].clone()
         self._nsteps = int(self.sample_steps.max()) if B else 0
         if T > 1:
-            short = (host[0] != T).nonzero()
+            short = (served.cpu() != T).nonzero()
             if short.numel():
                 raise Exception("TSSolve fails to step on all the specified points (-pn_adapt_scope sample: row %d)" % int(short[0]))
 
@@ -255,6 +287,13 @@ class RowSweep(object):
         B, n = self._rB, self.n
         d = n // B
         s_eff, A, b, c = self._s_eff, self._A, self._b, self._c
+        rd = self._rdense
+        # the stages of a reversed round.  With interpolated outputs whose extension uses the last stage of a first-same-as-last
+        # tableau, that stage is an ordinary one here (nothing is routed between rounds: stage 0 is re-evaluated every round):
+        # Y_{s-1} = u + h sum_j a_{s-1,j} K_j, cotangent D_{s-1} alone -- one more evaluation and VJP per reversed round
+        stages = list(range(s_eff))
+        if rd and self._fsal and (self._s - 1) in self._dense_cols:
+            stages.append(self._s - 1)
         lam = self.adj_u_tensor = self.adj_u_flat = ops.empty(n)
         lam.zero_()
         if self.adj_p_tensor is None or self.adj_p_tensor.numel() != self.np:
@@ -272,18 +311,22 @@ class RowSweep(object):
         hit0 = ops.i32(B) if T > 1 else None           # every row's state at t[0] is u0
         ops.rows_adj_accum(B, d, lam, lam, [], g, ld, self._rows_log_at(R - 1)[1], T)
         wbuf = ops.empty(n)
-        ybuf = [None] + [ops.empty(n) for _ in range(1, s_eff)]
+        ybuf = [None] + [ops.empty(n) for _ in range(1, stages[-1] + 1)]
+        if rd:
+            cols = self._dense_cols
+            Dbuf = dict((j, ops.empty(n)) for j in cols)
+            Gbuf = ops.empty(n)
         for k in range(R - 1, -1, -1):
             log_d, _ = self._rows_log_at(k)
             heff, tr, tf = log_d[0], log_d[1], log_d[2]
             u = self._rtraj[k]
             Y = self._rY[k] if self._rY is not None else None
-            tapes, K = [], []
-            for i in range(s_eff):
+            tapes, K = {}, {}
+            for i in stages:
                 if i == 0:
                     y, targ = u, tf.clone()
                 else:
-                    if Y is not None:
+                    if Y is not None and i < s_eff:
                         y = Y[i]
                     else:
                         y = ybuf[i]
@@ -291,27 +334,39 @@ class RowSweep(object):
                         ops.rows_stage(B, d, y, u, [K[j] for j in idx], [A[i][j] for j in idx], heff)
                     targ = tr + c[i] * heff
                 rec = []
-                K.append(self._rows_func(self._rows_t(targ), y, rec))
-                tapes.append(rec[0])
+                K[i] = self._rows_func(self._rows_t(targ), y, rec)
+                tapes[i] = rec[0]
                 self.nfe_backward += 1
-            dlam = [None] * s_eff
-            for i in range(s_eff - 1, -1, -1):
-                js = [j for j in range(i + 1, s_eff) if A[j][i] != 0.0 and dlam[j] is not None]
-                if b[i] == 0.0 and not js:
+            if rd:
+                # D_j[r] = sum_o h_r beta_j(theta_o) g[o, r] over the outputs row r interpolated in this round, G[r] = sum_o g[o, r]
+                ops.rows_dense_adjoint(B, d, [Dbuf[j] for j in cols], Gbuf, g, self._rtimes, self._rP, self._rows_range_at(k), log_d)
+            dlam = [None] * self._s
+            for i in reversed(stages):
+                js = [j for j in stages if j > i and A[j][i] != 0.0 and dlam[j] is not None]
+                Di = Dbuf.get(i) if rd else None
+                if b[i] == 0.0 and not js and Di is None:
                     continue
-                ops.rows_adj_theta(B, d, wbuf, lam if b[i] != 0.0 else None, b[i], [dlam[j] for j in js], [A[j][i] for j in js], heff)
+                if b[i] == 0.0 and not js:
+                    w = Di                               # the stage's cotangent is what its outputs send it
+                else:
+                    w = wbuf
+                    if Di is None:
+                        ops.rows_adj_theta(B, d, w, lam if b[i] != 0.0 else None, b[i], [dlam[j] for j in js], [A[j][i] for j in js], heff)
+                    else:
+                        ops.rows_adj_theta(B, d, w, lam if b[i] != 0.0 else None, b[i], [dlam[j] for j in js], [A[j][i] for j in js], heff,
+                                           dense_w=Di)
                 y, out, wrt = tapes[i]
                 tapes[i] = None
-                grads = torch.autograd.grad(out, (y,) + tuple(wrt), self._shaped(wbuf).view(out.shape), allow_unused=True)
+                grads = torch.autograd.grad(out, (y,) + tuple(wrt), self._shaped(w).view(out.shape), allow_unused=True)
                 gy = grads[0]
                 if gy is not None:
                     if gy.dtype != self.tensor_dtype:
                         gy = gy.to(self.tensor_dtype)
                     gy = gy.contiguous().reshape(-1)
-                    if gy.untyped_storage().data_ptr() == wbuf.untyped_storage().data_ptr():
+                    if gy.untyped_storage().data_ptr() == w.untyped_storage().data_ptr():
                         gy = gy.clone()
                 dlam[i] = gy
-                wst = wbuf.untyped_storage().data_ptr()
+                wst = w.untyped_storage().data_ptr()
                 gp = []
                 for q in grads[1:]:
                     if q is not None:
@@ -324,9 +379,14 @@ class RowSweep(object):
                     self._pend_a.append(1.0)              # the row's h is inside the cotangent
                     self._pend_g.append(gp)
             self._flush_param_accum()
-            idx = [i for i in range(s_eff) if dlam[i] is not None]
+            terms = [dlam[i] for i in stages if dlam[i] is not None]
+            if rd:
+                terms.append(Gbuf)
+            if len(terms) > _lib.PN_MAX_STAGES:          # (5dp with interpolated outputs: seven stages and G)
+                ops.rows_adj_accum(B, d, lam, lam, terms[_lib.PN_MAX_STAGES:], None, ld, None, T)
+                terms = terms[: _lib.PN_MAX_STAGES]
             hit_prev = self._rows_log_at(k - 1)[1] if k > 0 else hit0
-            ops.rows_adj_accum(B, d, lam, lam, [dlam[i] for i in idx], g if hit_prev is not None else None, ld, hit_prev, T)
+            ops.rows_adj_accum(B, d, lam, lam, terms, g if hit_prev is not None else None, ld, hit_prev, T)
             self._rtraj[k] = None
             if self._rY is not None:
                 self._rY[k] = None

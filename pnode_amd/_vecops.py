@@ -270,9 +270,30 @@ class HipVecOps(object):
                                       accept.data_ptr(), None if hit is None else hit.data_ptr(),
                                       None if sol is None else sol.data_ptr(), ld, nout))
 
-    def rows_adj_theta(self, B, d, w, lam, c_lam, dlams, coefs, h):
+    def rows_adj_theta(self, B, d, w, lam, c_lam, dlams, coefs, h, dense_w=None):
+        """`dense_w`: the D_i of the rows' interpolated outputs, added last and not scaled by h (pn_rows_adj_theta_dense)."""
+        if dense_w is not None:
+            check(self.lib.pn_rows_adj_theta_dense(self.stream(), self.code, B, d, w.data_ptr(), None if lam is None else lam.data_ptr(),
+                                                   c_lam, len(dlams), self._ptrs(dlams), self._dbl(coefs), h.data_ptr(),
+                                                   dense_w.data_ptr()))
+            return
         check(self.lib.pn_rows_adj_theta(self.stream(), self.code, B, d, w.data_ptr(), None if lam is None else lam.data_ptr(),
                                          c_lam, len(dlams), self._ptrs(dlams), self._dbl(coefs), h.data_ptr()))
+
+    # ... with -pn_output_times interpolate: the rows serve the output times themselves
+    rows_dense = True
+
+    def rows_dense_eval(self, B, d, sol, times, u, Ks, P, unew, log_d, tnew, log_hit, nxt, rng):
+        """The outputs of a round (pn_rows_dense_eval): `sol` the 2-D view of the solution tensor, `times` its output times on the
+        device, `P` the used rows of the extension's table (a C array of len(Ks) * PN_DENSE_MAX_POW doubles)."""
+        check(self.lib.pn_rows_dense_eval(self.stream(), self.code, B, d, u.data_ptr(), len(Ks), self._ptrs(Ks), P, unew.data_ptr(),
+                                          sol.data_ptr(), sol.stride(0), sol.shape[0], times.data_ptr(), log_d.data_ptr(),
+                                          tnew.data_ptr(), log_hit.data_ptr(), nxt.data_ptr(), rng.data_ptr()))
+
+    def rows_dense_adjoint(self, B, d, Ds, G, g, times, P, rng, log_d):
+        """Ds[j][r] = sum_o c_ojr g[o][r], G[r] = sum_o g[o][r] over the row's logged range (pn_rows_dense_adjoint)."""
+        check(self.lib.pn_rows_dense_adjoint(self.stream(), self.code, B, d, g.data_ptr(), g.stride(0), g.shape[0], times.data_ptr(),
+                                             log_d.data_ptr(), rng.data_ptr(), len(Ds), P, self._ptrs(Ds), G.data_ptr()))
 
     def rows_adj_accum(self, B, d, lam_out, lam, dlams, g, ld, hit, nout):
         check(self.lib.pn_rows_adj_accum(self.stream(), self.code, B, d, lam_out.data_ptr(), lam.data_ptr(), len(dlams),

@@ -198,6 +198,56 @@ PN_HD int pn_rows_judge_row(const PnRowsCtl &rc, const double *span, int64_t B, 
   return s.finished ? 0 : 1;
 }
 
+// ------------------------------------------------------------------------------------------
+// -pn_adapt_scope sample with -pn_output_times interpolate: what one row's accepted attempt serves of the output times.
+// The controller above sees [t[0], t[T-1]] only; after it has judged a round, a row that was accepted from t_r with h_r
+// to tnew_r (the time the controller wrote) interpolates the outputs next <= o <= T-2 with t[o] < tnew_r, copies its new
+// state into the output with t[o] == tnew_r (if any) and into output T-1 when the controller reports the final time.
+// ODEPetsc._dense_step's classification, per row; a rejected or finished row (h_eff == 0) serves nothing.
+// ------------------------------------------------------------------------------------------
+#define PN_ROWS_DENSE_POW 4                     /* PN_DENSE_MAX_POW (include/pnode_amd.h) */
+
+struct PnDensePlan {
+  int lo, hi;        // outputs [lo, hi) are interpolated from this attempt
+  int hit;           // the output that is a copy of the row's new state, or -1
+  int next;          // the row's first output not yet served afterwards
+};
+
+PN_HD PnDensePlan pn_rows_dense_plan_row(const double *times, int nout, double h_eff, double tnew, int ctl_hit, int next) {
+  PnDensePlan p;
+  int o = next < 0 ? 0 : (next > nout ? nout : next);
+  p.lo = p.hi = o;
+  p.hit = -1;
+  if (h_eff > 0.0) {
+    while (o < nout - 1 && times[o] < tnew) ++o;
+    p.hi = o;
+    if (o < nout - 1 && times[o] == tnew) p.hit = o++;
+    if (ctl_hit >= 0) {                          // the controller landed on t[T-1]: every output before it is served
+      p.hit = nout - 1;
+      o = nout;
+    }
+  }
+  p.next = o;
+  return p;
+}
+
+// h * beta(theta) of one stage, theta = (to - tn) / h, beta(theta) = sum_p P[p] theta^(p+1): ODEPetsc._dense_coefs' Horner
+// form.  Inside one Horner step an add feeds a multiply, but the product of one step is an operand of the next step's add:
+// contraction is switched off here, or the device (where hipcc fuses across statements) would round differently from the host.
+PN_HD double pn_rows_dense_coef(const double *P, double to, double tn, double h) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double d = to - tn;
+  const double th = d / h;
+  double v = 0.0;
+  for (int p = PN_ROWS_DENSE_POW - 1; p >= 0; --p) {
+    const double s = v + P[p];
+    v = s * th;
+  }
+  return h * v;
+}
+
 namespace pn {
 // the controller constants of `ts` and what the row controllers need of its tableau (pn_ts.cpp)
 void rows_ctl_config(const pn_ts *ts, int nspan, double max_time, PnRowsCtl *out);

@@ -13,6 +13,11 @@
 // Coefficients h_r * a_ij are formed in double and rounded once to the storage type, then used in pn_lincomb_kernel's
 // order (first term, then fused multiply-adds in j order).  Per-row step sizes, masks and hit indices are read from
 // device vectors (double / int32); tableau coefficients are kernel arguments.  No float atomics.
+//
+// With -pn_output_times interpolate the rows also serve the output times themselves (pn_rows_dense_eval and its transpose
+// pn_rows_dense_adjoint, the per-row forms of pn_dense.hip's two kernels): a row's range of outputs and the coefficients
+// h_r beta_j(theta) come from the shared text of pn_adapt.h, formed in double from the polynomial table (a kernel argument)
+// and rounded once; the output times and the row's "next output" counter live on the device.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -22,6 +27,8 @@
 #include "pn_launch.h"
 #include "pn_device.h"
 #include "pn_adapt.h"
+
+static_assert(PN_ROWS_DENSE_POW == PN_DENSE_MAX_POW, "pn_adapt.h and pnode_amd.h disagree on the width of a continuous extension's table");
 
 namespace {
 
@@ -34,6 +41,7 @@ struct RowsLinArgs {
   const T *x[PN_MAX_TERMS];
   double c[PN_MAX_TERMS];        // tableau coefficients, multiplied by h[r] in double
   const double *h;               // null: every row uses 1
+  const T *tail;                 // added last, unscaled (the D_i of a row's interpolated outputs); HAS_TAIL kernels only
 };
 
 template <typename T>
@@ -66,6 +74,34 @@ struct RowsAccumArgs {
   const int32_t *hit;
   int64_t ld;
   int nout;
+};
+
+template <typename T>
+struct RowsDenseEvalArgs {
+  const T *u, *unew;
+  const T *k[PN_MAX_STAGES];
+  T *sol;                        // [nout][B*d] with row stride ld
+  int64_t ld;
+  int nout;
+  const double *times;           // [nout]
+  const double *heff, *trow;     // the round's log: h_eff and the time at the round's start
+  const double *tnew;            // the time the controller wrote
+  int32_t *hit;                  // in: the controller's hit (>= 0: the final time); out: the output copied, or -1
+  int32_t *next;                 // the row's first output not yet served
+  int32_t *range;                // out: [2][B] = lo, hi
+  double P[PN_MAX_STAGES][PN_DENSE_MAX_POW];
+};
+
+template <typename T>
+struct RowsDenseAdjArgs {
+  const T *g;                    // [nout][B*d] with row stride ld
+  int64_t ld;
+  int nout;
+  const double *times, *heff, *trow;
+  const int32_t *range;
+  T *d[PN_MAX_STAGES];
+  T *G;
+  double P[PN_MAX_STAGES][PN_DENSE_MAX_POW];
 };
 
 struct RowsGeom {
@@ -109,7 +145,8 @@ __device__ __forceinline__ void store_chunk(T *row, int64_t c, int64_t d, const 
 
 // out[r] = base[r] + sum_j (h_r c_j) x_j[r]   (HAS_BASE: pn_rk_stage's order -- u, then fma in j)
 // out[r] = (h_r c_0) x_0[r] + sum_{j>0} ...   (!HAS_BASE: pn_adj_theta's order -- the first product, then fma)
-template <typename T, int NK, bool VEC, bool HAS_BASE>
+// HAS_TAIL: ... + tail[r], added last with coefficient one (pn_rk_adjoint_step_dense's last term)
+template <typename T, int NK, bool VEC, bool HAS_BASE, bool HAS_TAIL = false>
 __global__ __launch_bounds__(kBlock) void pn_rows_lin_kernel(RowsLinArgs<T> a, RowsGeom q) {
   constexpr int VW = 16 / sizeof(T);
   const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
@@ -120,15 +157,21 @@ __global__ __launch_bounds__(kBlock) void pn_rows_lin_kernel(RowsLinArgs<T> a, R
     for (int j = 0; j < NK; ++j) c[j] = (T)(h * a.c[j]);
     const int64_t off = r * q.d;
     for (int64_t ch = g; ch < q.nch; ch += G) {
-      T b[VW], x[NK][VW], o[VW];
+      T b[VW], x[NK][VW], o[VW], t[VW];
       if (HAS_BASE) load_chunk<T, VEC>(a.base + off, ch, q.d, b);
 #pragma unroll
       for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.x[j] + off, ch, q.d, x[j]);
+      if (HAS_TAIL) load_chunk<T, VEC>(a.tail + off, ch, q.d, t);
 #pragma unroll
       for (int e = 0; e < VW; ++e) {
         T acc = HAS_BASE ? b[e] : c[0] * x[0][e];
 #pragma unroll
         for (int j = HAS_BASE ? 0 : 1; j < NK; ++j) acc = fma(c[j], x[j][e], acc);
+        if (HAS_TAIL) {
+          // one addition of its own: with a single scaled term the product before it must not be fused into it
+#pragma clang fp contract(off)
+          acc = acc + t[e];
+        }
         o[e] = acc;
       }
       store_chunk<T, VEC>(a.out + off, ch, q.d, o);
@@ -244,6 +287,113 @@ __global__ __launch_bounds__(kBlock) void pn_rows_adj_accum_kernel(RowsAccumArgs
   }
 }
 
+// The outputs of a round (-pn_output_times interpolate).  Per row: the shared classification (pn_adapt.h) from the round's
+// log, the time the controller wrote, the row's counter and the output times; then, chunk by chunk, u and the used K_j are
+// loaded once and every output o in [lo, hi) is written as u + sum_j c_j K_j (u first, then fma in j order) with
+// c_j = (T)(h_r beta_j(theta_o)) formed in double; an exact landing or the final time copies unew[r].  Every thread of a
+// row's group classifies for itself; thread 0 of the group writes the counter, [lo, hi) and the hit after a barrier (the
+// other waves of the group have read them by then).  Rows outside every range are not touched.
+template <typename T, int NK, bool VEC>
+__global__ __launch_bounds__(kBlock) void pn_rows_dense_eval_kernel(RowsDenseEvalArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < q.B; r0 += (int64_t)gridDim.x * rpb) {
+    const int64_t r = r0 + sub;
+    const bool live = r < q.B;
+    PnDensePlan p = {0, 0, -1, 0};
+    double h = 0, tr = 0;
+    if (live) {
+      h = a.heff[r];
+      tr = a.trow[r];
+      p = pn_rows_dense_plan_row(a.times, a.nout, h, a.tnew[r], a.hit[r], a.next[r]);
+    }
+    __syncthreads();
+    if (live && g == 0) {
+      a.next[r] = p.next;
+      a.range[r] = p.lo;
+      a.range[q.B + r] = p.hi;
+      a.hit[r] = p.hit;
+    }
+    if (!live || (p.hi == p.lo && p.hit < 0)) continue;
+    const int64_t off = r * q.d;
+    for (int64_t ch = g; ch < q.nch; ch += G) {
+      if (p.hi > p.lo) {
+        T u[VW], k[NK][VW];
+        load_chunk<T, VEC>(a.u + off, ch, q.d, u);
+#pragma unroll
+        for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.k[j] + off, ch, q.d, k[j]);
+        for (int o = p.lo; o < p.hi; ++o) {
+          const double to = a.times[o];
+          T c[NK], v[VW];
+#pragma unroll
+          for (int j = 0; j < NK; ++j) c[j] = (T)pn_rows_dense_coef(a.P[j], to, tr, h);
+#pragma unroll
+          for (int e = 0; e < VW; ++e) {
+            T acc = u[e];
+#pragma unroll
+            for (int j = 0; j < NK; ++j) acc = fma(c[j], k[j][e], acc);
+            v[e] = acc;
+          }
+          store_chunk<T, VEC>(a.sol + (int64_t)o * a.ld + off, ch, q.d, v);
+        }
+      }
+      if (p.hit >= 0) {
+        T v[VW];
+        load_chunk<T, VEC>(a.unew + off, ch, q.d, v);
+        store_chunk<T, VEC>(a.sol + (int64_t)p.hit * a.ld + off, ch, q.d, v);
+      }
+    }
+  }
+}
+
+// The transpose, for a reversed round: D_j[r] = sum_{o in [lo_r, hi_r)} c_{o,j,r} g[o][r] (from zero, fma, o ascending) and
+// G[r] = sum_o g[o][r]; a row with an empty range gets zeros.  kAhead rows of g are loaded before the first is used.
+template <typename T, int ND, bool VEC>
+__global__ __launch_bounds__(kBlock) void pn_rows_dense_adjoint_kernel(RowsDenseAdjArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  constexpr int kAhead = 4;
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r = (int64_t)blockIdx.x * rpb + sub; r < q.B; r += (int64_t)gridDim.x * rpb) {
+    int lo = a.range[r], hi = a.range[q.B + r];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > a.nout ? a.nout : hi;
+    const double h = a.heff[r], tr = a.trow[r];
+    const int64_t off = r * q.d;
+    for (int64_t ch = g; ch < q.nch; ch += G) {
+      T D[ND][VW], S[VW];
+#pragma unroll
+      for (int e = 0; e < VW; ++e) {
+        S[e] = (T)0;
+#pragma unroll
+        for (int j = 0; j < ND; ++j) D[j][e] = (T)0;
+      }
+      for (int o = lo; o < hi; o += kAhead) {
+        T f[kAhead][VW];
+#pragma unroll
+        for (int w = 0; w < kAhead; ++w)
+          if (o + w < hi) load_chunk<T, VEC>(a.g + (int64_t)(o + w) * a.ld + off, ch, q.d, f[w]);
+#pragma unroll
+        for (int w = 0; w < kAhead; ++w) {
+          if (o + w < hi) {
+            const double to = a.times[o + w];
+#pragma unroll
+            for (int j = 0; j < ND; ++j) {
+              const T c = (T)pn_rows_dense_coef(a.P[j], to, tr, h);
+#pragma unroll
+              for (int e = 0; e < VW; ++e) D[j][e] = fma(c, f[w][e], D[j][e]);
+            }
+#pragma unroll
+            for (int e = 0; e < VW; ++e) S[e] += f[w][e];
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < ND; ++j) store_chunk<T, VEC>(a.d[j] + off, ch, q.d, D[j]);
+      store_chunk<T, VEC>(a.G + off, ch, q.d, S);
+    }
+  }
+}
+
 // One thread per row runs the shared controller (pn_adapt.h).  Every workgroup publishes (unfinished rows, first failing
 // row) and draws a ticket; the last to arrive adds / compares them in index order and writes the summary.
 __global__ __launch_bounds__(kBlock) void pn_rows_control_kernel(PnRowsCtl rc, const double *span, int64_t B, const double *enorm,
@@ -333,13 +483,14 @@ dim3 grid_for(const RowsGeom &q) { return dim3((unsigned)pn::blocks_for(q.B, kBl
 
 template <typename T>
 int rows_lin(hipStream_t st, int64_t B, int64_t d, void *out, const void *base, int nk, const void *const *x, const double *c,
-             const double *h, const char *name) {
+             const double *h, const char *name, const void *tail = nullptr) {
   constexpr int VW = 16 / sizeof(T);
   RowsLinArgs<T> a = {};
   a.out = (T *)out;
   a.base = (const T *)base;
   a.h = h;
-  const bool vec = (d % VW) == 0 && pn::aligned16(out, base) && pn::aligned16(x, nk);
+  a.tail = (const T *)tail;
+  const bool vec = (d % VW) == 0 && pn::aligned16(out, base, tail) && pn::aligned16(x, nk);
   for (int j = 0; j < nk; ++j) {
     a.x[j] = (const T *)x[j];
     a.c[j] = c[j];
@@ -349,6 +500,7 @@ int rows_lin(hipStream_t st, int64_t B, int64_t d, void *out, const void *base, 
     constexpr int NK = decltype(N)::value;
     auto kern = base ? (vec ? pn_rows_lin_kernel<T, NK, true, true> : pn_rows_lin_kernel<T, NK, false, true>)
                      : (vec ? pn_rows_lin_kernel<T, NK, true, false> : pn_rows_lin_kernel<T, NK, false, false>);
+    if (tail && !base) kern = vec ? pn_rows_lin_kernel<T, NK, true, false, true> : pn_rows_lin_kernel<T, NK, false, false, true>;
     return pn::launch(name, kern, grid_for(q), dim3(kBlock), st, a, q);
   });
   if (rc == pn::kNoCase) return pn::fail(std::string(name) + ": nk out of range");
@@ -421,6 +573,65 @@ int rows_accum(hipStream_t st, int64_t B, int64_t d, void *out, const void *lam,
                       dim3(kBlock), st, a, q);
   });
   return pn::or_fail(rc, "pn_rows_adj_accum: nk out of range");
+}
+
+template <typename T>
+int rows_dense_eval(hipStream_t st, int64_t B, int64_t d, const void *u, int nk, const void *const *K, const double *P,
+                    const void *unew, void *sol, int64_t ld, int nout, const double *times, const double *log_d, const double *tnew,
+                    int32_t *hit, int32_t *next, int32_t *range) {
+  constexpr int VW = 16 / sizeof(T);
+  RowsDenseEvalArgs<T> a = {};
+  a.u = (const T *)u;
+  a.unew = (const T *)unew;
+  a.sol = (T *)sol;
+  a.ld = ld;
+  a.nout = nout;
+  a.times = times;
+  a.heff = log_d;
+  a.trow = log_d + B;
+  a.tnew = tnew;
+  a.hit = hit;
+  a.next = next;
+  a.range = range;
+  for (int j = 0; j < nk; ++j) {
+    a.k[j] = (const T *)K[j];
+    for (int p = 0; p < PN_DENSE_MAX_POW; ++p) a.P[j][p] = P[j * PN_DENSE_MAX_POW + p];
+  }
+  const bool vec = (d % VW) == 0 && pn::aligned16(u, unew, sol) && (ld % VW) == 0 && pn::aligned16(K, nk);
+  const RowsGeom q = geom<T>(B, d);
+  const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+    constexpr int NK = decltype(N)::value;
+    return pn::launch("pn_rows_dense_eval", vec ? pn_rows_dense_eval_kernel<T, NK, true> : pn_rows_dense_eval_kernel<T, NK, false>,
+                      grid_for(q), dim3(kBlock), st, a, q);
+  });
+  return pn::or_fail(rc, "pn_rows_dense_eval: nk out of range");
+}
+
+template <typename T>
+int rows_dense_adjoint(hipStream_t st, int64_t B, int64_t d, const void *g, int64_t ld, int nout, const double *times,
+                       const double *log_d, const int32_t *range, int nd, const double *P, void *const *D, void *G) {
+  constexpr int VW = 16 / sizeof(T);
+  RowsDenseAdjArgs<T> a = {};
+  a.g = (const T *)g;
+  a.ld = ld;
+  a.nout = nout;
+  a.times = times;
+  a.heff = log_d;
+  a.trow = log_d + B;
+  a.range = range;
+  a.G = (T *)G;
+  for (int j = 0; j < nd; ++j) {
+    a.d[j] = (T *)D[j];
+    for (int p = 0; p < PN_DENSE_MAX_POW; ++p) a.P[j][p] = P[j * PN_DENSE_MAX_POW + p];
+  }
+  const bool vec = (d % VW) == 0 && pn::aligned16(g, G) && (ld % VW) == 0 && pn::aligned16(D, nd);
+  const RowsGeom q = geom<T>(B, d);
+  const int rc = pn::with_count<1, PN_MAX_STAGES>(nd, [&](auto N) {
+    constexpr int ND = decltype(N)::value;
+    return pn::launch("pn_rows_dense_adjoint", vec ? pn_rows_dense_adjoint_kernel<T, ND, true> : pn_rows_dense_adjoint_kernel<T, ND, false>,
+                      grid_for(q), dim3(kBlock), st, a, q);
+  });
+  return pn::or_fail(rc, "pn_rows_dense_adjoint: nd out of range");
 }
 
 int bad_shape(const char *name, int64_t B, int64_t d) {
@@ -514,6 +725,84 @@ int pn_rows_adj_accum(void *stream, int dtype, int64_t B, int64_t d, void *lambd
   hipStream_t st = (hipStream_t)stream;
   const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_accum<decltype(t)>(st, B, d, lambda_out, lambda, nk, dlam, g, ld, hit, nout); });
   return pn::or_fail(rc, "pn_rows_adj_accum: unknown dtype");
+}
+
+int pn_rows_adj_theta_dense(void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam, int nk,
+                            const void *const *dlam, const double *coef, const double *h, const void *dense_w) {
+  if (bad_shape("pn_rows_adj_theta_dense", B, d)) return 1;
+  if (!w || !h || !dense_w || nk < 0 || nk > PN_MAX_STAGES - 1 || (nk > 0 && (!dlam || !coef)) || (!lambda && nk == 0))
+    return pn::fail("pn_rows_adj_theta_dense: null argument or nk outside 0..6");
+  const void *x[PN_MAX_TERMS];
+  double c[PN_MAX_TERMS];
+  int n = 0;
+  if (lambda) {
+    x[n] = lambda;
+    c[n++] = c_lam;
+  }
+  for (int j = 0; j < nk; ++j) {
+    if (!dlam[j]) return pn::fail("pn_rows_adj_theta_dense: null vector");
+    x[n] = dlam[j];
+    c[n++] = coef[j];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    return rows_lin<decltype(t)>(st, B, d, w, nullptr, n, x, c, h, "pn_rows_adj_theta_dense", dense_w);
+  });
+  return pn::or_fail(rc, "pn_rows_adj_theta_dense: unknown dtype");
+}
+
+int pn_rows_dense_eval(void *stream, int dtype, int64_t B, int64_t d, const void *u, int nk, const void *const *K, const double *P,
+                       const void *unew, void *sol, int64_t ld, int nout, const double *times_dev, const double *log_d,
+                       const double *tnew, int32_t *log_hit, int32_t *next, int32_t *range) {
+  if (bad_shape("pn_rows_dense_eval", B, d)) return 1;
+  if (!u || !unew || !sol || !P || !K || nk < 1 || nk > PN_MAX_STAGES || !times_dev || !log_d || !tnew || !log_hit || !next || !range)
+    return pn::fail("pn_rows_dense_eval: null argument or nk outside 1..7");
+  if (nout < 2 || ld < B * d) return pn::fail("pn_rows_dense_eval: fewer than two output times or an output stride shorter than a state");
+  for (int j = 0; j < nk; ++j)
+    if (!K[j]) return pn::fail("pn_rows_dense_eval: null stage derivative");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    return rows_dense_eval<decltype(t)>(st, B, d, u, nk, K, P, unew, sol, ld, nout, times_dev, log_d, tnew, log_hit, next, range);
+  });
+  return pn::or_fail(rc, "pn_rows_dense_eval: unknown dtype");
+}
+
+int pn_rows_dense_adjoint(void *stream, int dtype, int64_t B, int64_t d, const void *g, int64_t ld, int nout, const double *times_dev,
+                          const double *log_d, const int32_t *range, int nd, const double *P, void *const *D, void *G) {
+  if (bad_shape("pn_rows_dense_adjoint", B, d)) return 1;
+  if (!g || !times_dev || !log_d || !range || !P || !D || !G || nd < 1 || nd > PN_MAX_STAGES)
+    return pn::fail("pn_rows_dense_adjoint: null argument or nd outside 1..7");
+  if (nout < 2 || ld < B * d) return pn::fail("pn_rows_dense_adjoint: fewer than two output times or a cotangent stride shorter than a state");
+  for (int j = 0; j < nd; ++j)
+    if (!D[j]) return pn::fail("pn_rows_dense_adjoint: null output vector");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    return rows_dense_adjoint<decltype(t)>(st, B, d, g, ld, nout, times_dev, log_d, range, nd, P, D, G);
+  });
+  return pn::or_fail(rc, "pn_rows_dense_adjoint: unknown dtype");
+}
+
+// The plan of pn_rows_dense_eval on host arrays (no device; the CPU-only tests' stand-in): the shared text of pn_adapt.h.
+int pn_rows_dense_plan_host(int64_t B, int nout, const double *times, const double *log_d, const double *tnew, int32_t *log_hit,
+                            int32_t *next, int32_t *range, int nk, const double *P, double *coef) {
+  if (B < 1 || nout < 2 || !times || !log_d || !range || (next && (!tnew || !log_hit)) || nk < 0 || nk > PN_MAX_STAGES ||
+      (coef && (nk < 1 || !P)))
+    return pn::fail("pn_rows_dense_plan_host: null argument, fewer than two output times or nk outside 0..7");
+  for (int64_t r = 0; r < B; ++r) {
+    const double h = log_d[r], tr = log_d[B + r];
+    if (next) {
+      const PnDensePlan p = pn_rows_dense_plan_row(times, nout, h, tnew[r], log_hit[r], next[r]);
+      next[r] = p.next;
+      range[r] = p.lo;
+      range[B + r] = p.hi;
+      log_hit[r] = p.hit;
+    }
+    if (!coef) continue;
+    const int lo = range[r] < 0 ? 0 : range[r], hi = range[B + r] > nout ? nout : range[B + r];
+    for (int o = lo; o < hi; ++o)
+      for (int j = 0; j < nk; ++j) coef[((int64_t)o * B + r) * nk + j] = pn_rows_dense_coef(P + j * PN_DENSE_MAX_POW, times[o], tr, h);
+  }
+  return 0;
 }
 
 }  // extern "C"
