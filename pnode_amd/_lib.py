@@ -49,6 +49,9 @@ PN_ABI_VERSION = 4
 PN_DENSE_MAX_POW = 4          # columns of a continuous extension's P matrix (pn_tableau_dense)
 PN_DENSE_CHUNK = 32           # output rows per launch of pn_rk_dense_eval / pn_rk_dense_adjoint
 PN_DENSE_NONTEMPORAL = 1
+# -pn_adapt_scope sample (csrc/pn_adapt.h): the rows of the controllers' state, sd = float64 [PN_ROWS_ND][B] and si = int32 [PN_ROWS_NI][B]
+PN_ROWS_T, PN_ROWS_H, PN_ROWS_TFIRST, PN_ROWS_CACHED, PN_ROWS_ND = 0, 1, 2, 3, 4
+PN_ROWS_SPANCTR, PN_ROWS_STEPS, PN_ROWS_REJ, PN_ROWS_REJ_STEP, PN_ROWS_PREV_REJ, PN_ROWS_FINISHED, PN_ROWS_FAIL, PN_ROWS_NI = 0, 1, 2, 3, 4, 5, 6, 8
 _vp, _i, _i64, _d, _cp = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_char_p
 _pd, _pi, _pi64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)
 _pvp = ctypes.POINTER(ctypes.c_void_p)

@@ -58,14 +58,21 @@ class RKSweep(object):
             tape.append((y, k, wrt, t) if self._tgrad else (y, k, wrt))
         else:
             k = self.funcEX(t, y)
+        k = self._func_result(k, y_flat)
+        self.nfe_forward += 1
+        return k
+
+    def _func_result(self, k, y_flat):
+        """func's result as both sweeps take it: refused unless it has the state's shape, dtype and device; flat, detached,
+        contiguous, and a copy when func returned (a view of) its input -- the input buffer is recycled."""
         if k.dtype != self.tensor_dtype or k.device != self.device or k.numel() != self.n:
             raise ValueError("func must return a tensor with the state's shape, dtype and device")
+        k = k.detach()
         if not k.is_contiguous():
             k = k.contiguous()
         if k.untyped_storage().data_ptr() == y_flat.untyped_storage().data_ptr():
-            k = k.clone()      # func returned (a view of) its input; the input buffer is recycled
-        self.nfe_forward += 1
-        return k.detach().reshape(-1)
+            k = k.clone()
+        return k.reshape(-1)
 
     def _rk_step(self, t, h, u, K0, unew, stage_dest, want_err, tapes=None, t_first=None):
         """One explicit RK step attempt from the flat state `u` (TSStep_RK's body).
@@ -140,12 +147,7 @@ class RKSweep(object):
                 if gy is not None and gy.data_ptr() == w.data_ptr():
                     gy = gy.clone()                     # f returned its cotangent unchanged (identity-like f)
                 dlam[i] = gy
-                if o.np > 0 and any(g is not None for g in gp):
-                    if o._accum_mode == "stage":
-                        o._ops.param_accum(o.adj_p_tensor, scale, gp, o._poff, o._plen)
-                    else:
-                        o._pend_a.append(scale)
-                        o._pend_g.append(gp)
+                o._take_param_grads(scale, gp, deferred=o._accum_mode != "stage")
                 return 0 if gy is None else gy.data_ptr()
             except BaseException as exc:
                 o._cb_exc = exc
@@ -393,19 +395,23 @@ class RKSweep(object):
                 lin.flush(self, lam=self.adj_u_flat if last else None)
             if tgx:
                 self._tg_tbar(slot, gt, alpha)
-        gy = grads[0]
-        if gy is not None:
-            if gy.dtype != self.tensor_dtype:
-                gy = gy.to(self.tensor_dtype)
-            gy = gy.contiguous().reshape(-1)
-        gp = []
+        return self._vjp_results(grads[0], grads[1:], w_flat, deferred=self._accum_mode != "stage")
+
+    def _vjp_results(self, gy, grads, cotangent, deferred=True):
+        """What autograd returned for a stage VJP as the sweeps take it: J^T w flat, the parameter cotangents as a list, all in the
+        state's dtype and contiguous (a None stays None).  Deferred accumulation (-pn_param_accum batch|step, the per-sample sweep)
+        reads the parameter cotangents launches later, after the buffer of `cotangent` (w_a, or lambda itself for a folded stage)
+        has been rewritten in place.  Autograd hands the cotangent, or ANY view of it, straight through for f = ... + p,
+        cat([z[:2] + b1, ...]), stack((.. + p0, ..)): every gradient that shares the cotangent's storage is copied, whatever its size.
+        `deferred` False (-pn_param_accum stage): they are added before anything rewrites the buffer, nothing is copied."""
         dt = self.tensor_dtype
-        # Deferred accumulation (-pn_param_accum batch|step) reads these gradients launches later, after the
-        # cotangent buffer (w_a, or lambda itself for a folded stage) has been rewritten in place.  Autograd hands
-        # the cotangent, or ANY view of it, straight through for f = ... + p, cat([z[:2] + b1, ...]), stack((.. + p0, ..)):
-        # every gradient that shares the cotangent's storage is copied, whatever its size.
-        wst = None if self._accum_mode == "stage" else w_flat.untyped_storage().data_ptr()
-        for g in grads[1:]:
+        if gy is not None:
+            if gy.dtype != dt:
+                gy = gy.to(dt)
+            gy = gy.contiguous().reshape(-1)
+        wst = cotangent.untyped_storage().data_ptr() if deferred else None
+        gp = []
+        for g in grads:
             if g is not None:
                 if g.dtype != dt or not g.is_contiguous():
                     g = g.to(dt).contiguous()
@@ -480,7 +486,7 @@ class RKSweep(object):
                 self._rev_next = step - 1
                 continue
             scale = [1.0] * self._s          # true dlam_i = scale[i] * dlam[i]
-            pend_a, pend_g = self._pend_a, self._pend_g      # parameter gradients waiting to be added to mu
+            pend_g = self._pend_g            # parameter gradients waiting to be added to mu
             nw = 0
             for i in range(s_eff - 1, -1, -1):
                 js = [j for j in range(i + 1, s_eff) if A[j][i] != 0.0 and dlam[j] is not None]
@@ -505,12 +511,7 @@ class RKSweep(object):
                 if gy is not None and gy.data_ptr() == w.data_ptr():
                     gy = gy.clone()            # f returned its cotangent unchanged (identity-like f)
                 dlam[i] = gy
-                if self.np > 0 and any(g is not None for g in gp):
-                    if self._accum_mode == "stage":
-                        ops.param_accum(self.adj_p_tensor, scale[i], gp, self._poff, self._plen)
-                    else:
-                        pend_a.append(scale[i])
-                        pend_g.append(gp)
+                self._take_param_grads(scale[i], gp, deferred=self._accum_mode != "stage")
             if pend_g and (self._accum_mode == "step" or self._sg is not None or len(pend_g) + s_eff > self._accum_cap):
                 self._flush_param_accum()      # mu += sum_j scale_j * dmu_j, oldest first: one launch
             elif self._pend_bias and self._accum_mode == "step":
@@ -520,6 +521,16 @@ class RKSweep(object):
                           forcing if r == nsteps - 1 else None)
             self._traj.rev_done(step)
             self._rev_next = step - 1
+
+    def _take_param_grads(self, scale, gp, deferred=True):
+        """mu += scale * gp, the parameter cotangents of one stage VJP: queued for the batched launch of _flush_param_accum, or
+        (-pn_param_accum stage) added at once."""
+        if self.np > 0 and any(g is not None for g in gp):
+            if deferred:
+                self._pend_a.append(scale)
+                self._pend_g.append(gp)
+            else:
+                self._ops.param_accum(self.adj_p_tensor, scale, gp, self._poff, self._plen)
 
     def _add_param_grads(self, alpha, gp, first=0, stable=True, cotangent=None):
         """mu[parameters first .. first+len(gp)) += alpha * gp for the implicit / IMEX steppers: one launch per call with
@@ -542,8 +553,7 @@ class RKSweep(object):
             self._ops.param_accum(self.adj_p_tensor, alpha, list(gp), off, ln)
             return
         if cotangent is not None:
-            st = cotangent.untyped_storage().data_ptr()
-            gp = [g.clone() if (g is not None and g.untyped_storage().data_ptr() == st) else g for g in gp]
+            gp = self._vjp_results(None, gp, cotangent)[1]
         self._pend_a.append(alpha)
         self._pend_g.append(list(gp) if full else [None] * first + list(gp) + [None] * (n_all - first - len(gp)))
         if len(self._pend_g) >= self._accum_cap:
@@ -640,18 +650,22 @@ class RKSweep(object):
                                "(setupTS(enable_adjoint=True) and a differentiable input are required)")
         if self.adj_u_tensor is None:
             self.adj_u_tensor = self._ops.empty(self._npad)
-        if self.adj_p_tensor is None or self.adj_p_tensor.numel() != self.np:
-            self.adj_p_tensor = self._ops.empty(max(self.np, 1))[: self.np]
         self.adj_u_flat = self.adj_u_tensor
         self._ops.copy(self.adj_u_flat, seed)
-        self.adj_p_tensor.zero_()
+        self._begin_param_adjoint()
         self._traj.begin_reverse()
         self._rev_next = self._nsteps - 1
+        if self._lin is not None:
+            self._lin.reset()              # (partial sums a sweep that raised may have left behind)
+
+    def _begin_param_adjoint(self):
+        """mu = 0 and nothing queued for it: the start of every reverse sweep, the per-sample one included."""
+        if self.adj_p_tensor is None or self.adj_p_tensor.numel() != self.np:
+            self.adj_p_tensor = self._ops.empty(max(self.np, 1))[: self.np]
+        self.adj_p_tensor.zero_()
         self._pend_a, self._pend_g = [], []
         self._pend_mixed = False             # the queue holds autograd's cotangents of parameters the Linear hooks also serve
         self._pend_bias, self._pend_bias_bytes = [], 0
-        if self._lin is not None:
-            self._lin.reset()              # (partial sums a sweep that raised may have left behind)
         # pending stage results are kept alive until they are added: bound them to 1 GiB
         esize = 4 if self.tensor_dtype == torch.float32 else 8
         self._accum_cap = max(1, min(self._accum_sources, (1 << 30) // max(self.np * esize, 1)))
@@ -731,12 +745,7 @@ class RKSweep(object):
                 self._tg["yN"] = False
             if gy is not None:
                 ops.adj_accum(self.adj_u_flat, self.adj_u_flat, [gy], [1.0], None)
-            if self.np > 0 and any(x is not None for x in gp):
-                if self._accum_mode == "stage":
-                    ops.param_accum(self.adj_p_tensor, 1.0, gp, self._poff, self._plen)
-                else:
-                    self._pend_a.append(1.0)
-                    self._pend_g.append(gp)
+            self._take_param_grads(1.0, gp, deferred=self._accum_mode != "stage")
         for k in range(N - 1, -1, -1):
             lo, hi, cf = rows[k]
             dw = [None] * _lib.PN_MAX_STAGES

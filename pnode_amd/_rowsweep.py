@@ -12,21 +12,47 @@ With ``-pn_output_times interpolate`` (a backend with the row-dense entry points
 ``[t[0], t[-1]]`` only: every row takes the steps its own tolerance asks for, and after each round pn_rows_dense_eval fills the
 output times an accepted attempt has passed from the tableau's continuous extension (the output times and a per-row "next
 output" counter live on the device; the round's log grows by the range [lo, hi) of outputs each row interpolated)."""
+import collections
 import ctypes
+import types
 import warnings
 
 import torch
 
 from . import _lib
-from ._lib import PnError, check
+from ._lib import PN_ROWS_CACHED, PN_ROWS_H, PN_ROWS_REJ, PN_ROWS_SPANCTR, PN_ROWS_STEPS, PN_ROWS_T, PN_ROWS_TFIRST, PnError, check
 
 _LOG_BLOCK = 64          # rounds per allocation of the round log
+
+# One round of the log, an entry per row in every field: h_eff, the time and the first-stage time at the round's start (`log_d`: the
+# packed [3][B] tensor of the three, as the entry points take it), the output the row landed on or -1, [2][B] the outputs [lo, hi) it interpolated
+_Round = collections.namedtuple("_Round", "heff t tfirst hit range log_d")
+
+
+class _RoundLog(object):
+    """The rounds of a per-sample solve, allocated _LOG_BLOCK rounds at a time (the range block only with interpolated outputs)."""
+
+    def __init__(self, ops, B, ranges):
+        self._new = lambda: (ops.f64(_LOG_BLOCK, 3, B), ops.i32(_LOG_BLOCK, B), ops.i32(_LOG_BLOCK, 2, B) if ranges else None)
+        self._blocks, self._n = [], 0
+
+    def append(self):
+        if self._n % _LOG_BLOCK == 0:
+            self._blocks.append(self._new())
+        self._n += 1
+        return self[self._n - 1]
+
+    def __getitem__(self, k):
+        log_d, hit, rng = self._blocks[k // _LOG_BLOCK]
+        i = k % _LOG_BLOCK
+        d = log_d[i]
+        return _Round(d[0], d[1], d[2], hit[i], None if rng is None else rng[i], d)
 
 
 class RowSweep(object):
     _sample = False
     _rows_probe = False
-    _rdense = False          # the last per-sample solve interpolated its outputs
+    _rdense = None           # the last per-sample solve interpolated its outputs: its device-side plan
     rounds = 0
     sample_steps = None
     sample_rejections = None
@@ -87,27 +113,17 @@ class RowSweep(object):
         """[(t_n, h_n)] of the accepted steps of `row` in the last -pn_adapt_scope sample solve."""
         out = []
         for k in range(self.rounds):
-            ld, _ = self._rows_log_at(k)
-            h = float(ld[0, row])
+            rnd = self._round_log[k]
+            h = float(rnd.heff[row])
             if h > 0.0:
-                out.append((float(ld[1, row]), h))
+                out.append((float(rnd.t[row]), h))
         return out
 
     # ------------------------------------------------------------------ helpers
-    def _rows_log_at(self, k):
-        blk = self._rlog[k // _LOG_BLOCK]
-        return blk[0][k % _LOG_BLOCK], blk[1][k % _LOG_BLOCK]
-
-    def _rows_range_at(self, k):
-        """int32 [2][B]: the outputs [lo, hi) every row interpolated in round k (-pn_output_times interpolate)."""
-        return self._rlog[k // _LOG_BLOCK][2][k % _LOG_BLOCK]
-
-    def _rows_t(self, tvec):
-        """The time argument of func: float64, one entry per row, broadcastable against the state."""
-        return tvec.view((self._rB,) + (1,) * (len(self.tensor_size) - 1))
-
-    def _rows_func(self, targ, y_flat, tape=None):
-        """evalRHSFunction for the whole batch with per-row times; with `tape` (a list) recorded by autograd."""
+    def _rows_func(self, tvec, y_flat, tape=None):
+        """evalRHSFunction for the whole batch with per-row times; with `tape` (a list) recorded by autograd.  The time argument
+        of func: float64, one entry per row, broadcastable against the state."""
+        targ = tvec.view((self._rB,) + (1,) * (len(self.tensor_size) - 1))
         y = self._shaped(y_flat)
         try:
             if tape is not None:
@@ -132,149 +148,158 @@ class RowSweep(object):
                               % (type(exc).__name__, exc)) from exc
             raise
         self._rows_probe = False
-        if k.dtype != self.tensor_dtype or k.device != self.device or k.numel() != self.n:
-            raise ValueError("func must return a tensor with the state's shape, dtype and device")
-        kd = k.detach()
-        if not kd.is_contiguous():
-            kd = kd.contiguous()
-        if kd.untyped_storage().data_ptr() == y_flat.untyped_storage().data_ptr():
-            kd = kd.clone()
-        return kd.reshape(-1)
+        return self._func_result(k, y_flat)
+
+    def _rows_stages(self, stages, Y, held, h, t, tfirst, tapes=None):
+        """K_i = f(t_r + c_i h_r, Y_i) for `stages` in order, the whole batch per call.  Y[0] is the round's state, evaluated at the rows'
+        first-stage times; Y_i = u + h_r sum_j a_ij K_j is formed into Y[i] unless it is `held` there already.  With `tapes` (a dict)
+        the evaluations are the reverse sweep's, recorded by autograd: tapes[i] = (input, output, parameters)."""
+        A, K = self._A, {}
+        for i in stages:
+            if i and i not in held:
+                idx = [j for j in range(i) if A[i][j] != 0.0]
+                self._ops.rows_stage(self._rB, self.n // self._rB, Y[i], Y[0], [K[j] for j in idx], [A[i][j] for j in idx], h)
+            rec = None if tapes is None else []
+            K[i] = self._rows_func(t + self._c[i] * h if i else tfirst.clone(), Y[i], rec)
+            if tapes is None:
+                self.nfe_forward += 1
+            else:
+                tapes[i] = rec[0]
+                self.nfe_backward += 1
+        return K
 
     # ------------------------------------------------------------------ forward rounds
     def _rows_odeint(self, u0, t, save):
+        st = self._rows_begin(u0, t, save)
+        if st.tmax > st.t0:
+            while self._rows_round(st):
+                pass
+        else:
+            # nothing to integrate (one output time at or before 0; pn_ts_begin has refused a span that does not increase)
+            for i in range(st.T):
+                self._ops.copy(st.sol[i], st.u0)
+            st.si[PN_ROWS_SPANCTR].fill_(st.T)
+        # per row, the number of output times it has reached: the rows' own counter, or the controller's span counter
+        served = st.si[PN_ROWS_SPANCTR] if st.dense is None else st.dense.next
+        host = st.si.cpu()
+        self.sample_steps = host[PN_ROWS_STEPS].clone()
+        self.sample_rejections = host[PN_ROWS_REJ].clone()
+        self._nsteps = int(self.sample_steps.max()) if st.B else 0
+        if st.T > 1:
+            short = (served.cpu() != st.T).nonzero()
+            if short.numel():
+                raise Exception("TSSolve fails to step on all the specified points (-pn_adapt_scope sample: row %d)" % int(short[0]))
+        if self._view and self.rounds:
+            print("TS Object (pnode_amd): type rk, -pn_adapt_scope sample: %d rounds for %d rows, accepted steps per row %d..%d, "
+                  "rejected %d..%d; output times: %s; launches: %s"
+                  % (self.rounds, st.B, int(self.sample_steps.min()), int(self.sample_steps.max()),
+                     int(self.sample_rejections.min()), int(self.sample_rejections.max()),
+                     "interpolate (per row, continuous extension of order %d)" % self._dense_order if st.dense is not None else "match",
+                     self._graph_status))
+        return st.solution
+
+    def _rows_begin(self, u0, t, save):
+        """The state of a forward sweep: the span as the controller sees it, the controllers' rows seeded from the host engine's
+        first attempt, the buffers the rounds turn over and, with interpolated outputs, the rows' device-side plan."""
         lib, ops, ts = self._lib, self._ops, self._ts
         B = self._rB = int(self.tensor_size[0])
         n = self.n
-        d = n // B
-        s, A, b, c, e = self._s, self._A, self._b, self._c, self._e
         self.sol_times = t.detach().cpu().to(dtype=torch.float64)
-        T = int(t.shape[0])
         times = self.sol_times.tolist()
-        dt0 = float(self.step_size)
-        solution = ops.empty((T,) + tuple(self.tensor_size))
-        sol_flat = solution.view(T, -1)
-        u0f = u0.detach().contiguous().reshape(-1)
+        T = len(times)
+        st = types.SimpleNamespace(B=B, d=n // B, T=T, save=save, dense=None)
+        st.solution = ops.empty((T,) + tuple(self.tensor_size))
+        st.sol = st.solution.view(T, -1)
+        st.u0 = u0.detach().contiguous().reshape(-1)
         # -pn_output_times interpolate: the controller sees the end points only; t[1:-1] are filled by rows_dense_eval
-        rd = self._rdense = self._dense and T > 2
-        full_T, full_sol = T, sol_flat
-        if rd:
+        self._rdense = None
+        if self._dense and T > 2:
             if any(not (b > a) for a, b in zip(times, times[1:])):
                 raise PnError("-pn_output_times interpolate: the output times must be strictly increasing")
-            times_dev = self._rtimes = self.sol_times.to(self.device)
-            T, times, sol_flat = 2, [times[0], times[-1]], sol_flat[:: T - 1]
             cols = self._dense_cols
             pv = [v for j in cols for v in list(self._dense_P[j]) + [0.0] * (_lib.PN_DENSE_MAX_POW - len(self._dense_P[j]))]
-            P = self._rP = (ctypes.c_double * len(pv))(*pv)
-            nxt_out = ops.i32(B)
-            nxt_out.fill_(1)                     # times[0] is the initial condition itself
+            st.dense = self._rdense = types.SimpleNamespace(times=self.sol_times.to(self.device), cols=cols,
+                                                            P=(ctypes.c_double * len(pv))(*pv), next=ops.i32(B))
+            st.dense.next.fill_(1)               # times[0] is the initial condition itself
+            times = [times[0], times[-1]]
         # the first step of every row: the host engine's own MATCHSTEP clamp at the start of a solve (pn_ts_begin)
-        check(lib.pn_ts_begin(ts, 0.0, dt0, T, (ctypes.c_double * T)(*times)))
-        t0 = 0.0 if T == 1 else times[0]
-        self._rlog, self._rtraj, self._rY = [], ([] if save else None), None
+        nt = len(times)
+        check(lib.pn_ts_begin(ts, 0.0, float(self.step_size), nt, (ctypes.c_double * nt)(*times)))
+        st.t0, st.tmax = (0.0 if nt == 1 else times[0]), times[-1]
+        self._round_log = _RoundLog(ops, B, st.dense is not None)
+        # the stage values of every round are kept for the reverse sweep, or live in scratch that every round rewrites
+        st.store = save and not self._solution_only and not self._solution_only_auto
+        self._rtraj, self._rY = ([] if save else None), ([] if st.store else None)
         self._rows_probe = True                    # the first evaluation of this solve is still to come
         self.rounds = 0
-        sd, si = ops.f64(4, B), ops.i32(8, B)
-        self._rsi = si
-        cur = ops.empty(n)
-        ops.copy(cur, u0f)
+        st.sd, st.si = ops.f64(_lib.PN_ROWS_ND, B), ops.i32(_lib.PN_ROWS_NI, B)
+        st.cur = ops.empty(n)
+        ops.copy(st.cur, st.u0)
         if T > 1:
-            ops.copy(sol_flat[0], u0f)
-        if not times[-1] > t0:
-            # nothing to integrate (one output time at or before 0; pn_ts_begin has refused a span that does not increase)
-            for i in range(T):
-                ops.copy(sol_flat[i], u0f)
-            si[0].fill_(T)
-            self._rows_finish(si[0], si, B, T)
-            return solution
+            ops.copy(st.sol[0], st.u0)
+        if not st.tmax > st.t0:
+            return st
         tt, hh = ctypes.c_double(), ctypes.c_double()
         check(lib.pn_ts_attempt(ts, ctypes.byref(tt), ctypes.byref(hh)))
-        sd[0].fill_(tt.value)
-        sd[1].fill_(hh.value)
-        sd[2].fill_(tt.value)
-        sd[3].fill_(lib.pn_ts_span_cached_dt(ts))
-        if T > 1:
-            si[0].fill_(1)                       # times[0] is the initial condition itself
-        span = torch.tensor(times, dtype=torch.float64).to(self.device) if T > 1 else None
-        nspan = T if T > 1 else 0
-        enorm, accept, summary = ops.f64(B), ops.i32(B), ops.i32(4)
-        store = save and not self._solution_only and not self._solution_only_auto
-        if store:
-            self._rY = []
-        ie = [j for j in range(s) if e[j] != 0.0 or (not self._fsal and b[j] != 0.0)]
-        scratch = [ops.empty(n) for _ in range(s)] if not store else None
-        unew_buf = [ops.empty(n), ops.empty(n)]
-        pp = [ops.empty(n), cur] if not save else None
+        st.sd[PN_ROWS_T].fill_(tt.value)
+        st.sd[PN_ROWS_H].fill_(hh.value)
+        st.sd[PN_ROWS_TFIRST].fill_(tt.value)
+        st.sd[PN_ROWS_CACHED].fill_(lib.pn_ts_span_cached_dt(ts))
+        if nt > 1:
+            st.si[PN_ROWS_SPANCTR].fill_(1)      # times[0] is the initial condition itself
+        st.nspan, st.span = (nt, torch.tensor(times, dtype=torch.float64).to(self.device)) if nt > 1 else (0, None)
+        st.enorm, st.accept, st.summary = ops.f64(B), ops.i32(B), ops.i32(4)
+        st.ie = [j for j in range(self._s) if self._e[j] != 0.0 or (not self._fsal and self._b[j] != 0.0)]    # the stages of the error estimate
+        st.scratch = None if st.store else [ops.empty(n) for _ in range(self._s)]
+        st.unew = [ops.empty(n), ops.empty(n)]
+        if not save:
+            st.pingpong = [ops.empty(n), st.cur]   # the states of successive rounds, in turn
         if self._monitor:
             print("round %d: t [%g, %g] dt [%g, %g] rows unfinished %d" % (0, tt.value, tt.value, hh.value, hh.value, B))
-        k = 0
-        while True:
-            if k % _LOG_BLOCK == 0:
-                self._rlog.append((ops.f64(_LOG_BLOCK, 3, B), ops.i32(_LOG_BLOCK, B)) + ((ops.i32(_LOG_BLOCK, 2, B),) if rd else ()))
-            log_d, log_hit = self._rows_log_at(k)
-            h, tr = sd[1], sd[0]
-            unew = unew_buf[k % 2]
-            Ybuf = [cur] + ([ops.empty(n) for _ in range(1, self._s_eff)] if store else scratch[1:self._s_eff])
-            K = [None] * s
-            for i in range(s):
-                if i == 0:
-                    y, targ = cur, sd[2].clone()
-                else:
-                    y = unew if (self._fsal and i == s - 1) else Ybuf[i]
-                    idx = [j for j in range(i) if A[i][j] != 0.0]
-                    ops.rows_stage(B, d, y, cur, [K[j] for j in idx], [A[i][j] for j in idx], h)
-                    targ = tr + c[i] * h
-                K[i] = self._rows_func(self._rows_t(targ), y)
-                self.nfe_forward += 1
-            ops.rows_combine_wrms(B, d, None if self._fsal else unew, unew if self._fsal else cur, [K[j] for j in ie],
-                                  [b[j] for j in ie], [e[j] for j in ie], h, self._atol, self._rtol, enorm)
-            ops.rows_control(ts, B, nspan, span, times[-1], enorm, sd, si, log_d, log_hit, accept, summary)
-            if save:
-                nxt = ops.empty(n)
-                self._rtraj.append(cur)
-                if store:
-                    self._rY.append(Ybuf)
-            else:
-                nxt = pp[k % 2]
-            if rd:
-                # the outputs this round's accepted attempts have passed, and the copies of the new state (an exact landing, the
-                # final time): log_hit becomes the output copied, as the reverse sweep's masked forcing reads it
-                ops.rows_dense_eval(B, d, full_sol, times_dev, cur, [K[j] for j in cols], P, unew, log_d, sd[0], log_hit, nxt_out,
-                                    self._rows_range_at(k))
-                ops.rows_commit(B, d, nxt, cur, unew, accept, None, None, 0, 0)
-            else:
-                ops.rows_commit(B, d, nxt, cur, unew, accept, log_hit, sol_flat, n, T)
-            cur = nxt
-            k += 1
-            self.rounds = k
-            nopen, frow, fcode = ops.rows_summary(summary)          # the one read-back of the round
-            if frow >= 0:
-                lib.pn_rows_failure(fcode, frow)
-                raise PnError(lib.pn_last_error().decode())
-            if self._monitor:
-                print("round %d: t [%g, %g] dt [%g, %g] rows unfinished %d"
-                      % (k, float(sd[0].min()), float(sd[0].max()), float(sd[1].min()), float(sd[1].max()), nopen))
-            if nopen == 0:
-                break
-        self._rows_finish(nxt_out if rd else si[0], si, B, full_T)
-        if self._view:
-            print("TS Object (pnode_amd): type rk, -pn_adapt_scope sample: %d rounds for %d rows, accepted steps per row %d..%d, "
-                  "rejected %d..%d; output times: %s; launches: %s"
-                  % (self.rounds, B, int(self.sample_steps.min()), int(self.sample_steps.max()),
-                     int(self.sample_rejections.min()), int(self.sample_rejections.max()),
-                     "interpolate (per row, continuous extension of order %d)" % self._dense_order if rd else "match", self._graph_status))
-        return solution
+        return st
 
-    def _rows_finish(self, served, si, B, T):
-        """`served`: per row, the number of output times it has reached (the span counter, or the rows' own counter)."""
-        host = si.cpu()
-        self.sample_steps = host[1].clone()
-        self.sample_rejections = host[2].clone()
-        self._nsteps = int(self.sample_steps.max()) if B else 0
-        if T > 1:
-            short = (served.cpu() != T).nonzero()
-            if short.numel():
-                raise Exception("TSSolve fails to step on all the specified points (-pn_adapt_scope sample: row %d)" % int(short[0]))
+    def _rows_round(self, st):
+        """One step attempt of every unfinished row: the stages, the rows' error norms, the controllers' judgement, the outputs
+        the accepted attempts serve and the next round's state.  Returns the number of rows still unfinished."""
+        ops, B, d, n = self._ops, st.B, st.d, self.n
+        b, e, fsal = self._b, self._e, self._fsal
+        sd, cur, k = st.sd, st.cur, self.rounds
+        log = self._round_log.append()
+        h, tr = sd[PN_ROWS_H], sd[PN_ROWS_T]
+        unew = st.unew[k % 2]
+        Y = [cur] + ([ops.empty(n) for _ in range(1, self._s_eff)] if st.store else st.scratch[1:self._s_eff])
+        # (first same as last: the last stage value is the new state itself)
+        K = self._rows_stages(range(self._s), Y + [unew] if fsal else Y, (), h, tr, sd[PN_ROWS_TFIRST])
+        ops.rows_combine_wrms(B, d, None if fsal else unew, unew if fsal else cur, [K[j] for j in st.ie],
+                              [b[j] for j in st.ie], [e[j] for j in st.ie], h, self._atol, self._rtol, st.enorm)
+        ops.rows_control(self._ts, B, st.nspan, st.span, st.tmax, st.enorm, sd, st.si, log.log_d, log.hit, st.accept, st.summary)
+        if st.save:
+            nxt = ops.empty(n)
+            self._rtraj.append(cur)
+            if st.store:
+                self._rY.append(Y)
+        else:
+            nxt = st.pingpong[k % 2]
+        if st.dense is not None:
+            # the outputs this round's accepted attempts have passed, and the copies of the new state (an exact landing, the
+            # final time): log.hit becomes the output copied, as the reverse sweep's masked forcing reads it
+            dn = st.dense
+            ops.rows_dense_eval(B, d, st.sol, dn.times, cur, [K[j] for j in dn.cols], dn.P, unew, log.log_d, sd[PN_ROWS_T], log.hit,
+                                dn.next, log.range)
+            ops.rows_commit(B, d, nxt, cur, unew, st.accept, None, None, 0, 0)
+        else:
+            ops.rows_commit(B, d, nxt, cur, unew, st.accept, log.hit, st.sol, n, st.T)
+        st.cur = nxt
+        self.rounds = k + 1
+        nopen, frow, fcode = ops.rows_summary(st.summary)          # the one read-back of the round
+        if frow >= 0:
+            self._lib.pn_rows_failure(fcode, frow)
+            raise PnError(self._lib.pn_last_error().decode())
+        if self._monitor:
+            print("round %d: t [%g, %g] dt [%g, %g] rows unfinished %d"
+                  % (k + 1, float(sd[PN_ROWS_T].min()), float(sd[PN_ROWS_T].max()), float(sd[PN_ROWS_H].min()),
+                     float(sd[PN_ROWS_H].max()), nopen))
+        return nopen
 
     # ------------------------------------------------------------------ reverse rounds
     def _rows_reverse(self, g, T):
@@ -283,25 +308,17 @@ class RowSweep(object):
         if self._rtraj is None:
             raise RuntimeError("adjoint requested but no trajectory was saved "
                                "(setupTS(enable_adjoint=True) and a differentiable input are required)")
-        ops = self._ops
-        B, n = self._rB, self.n
-        d = n // B
-        s_eff, A, b, c = self._s_eff, self._A, self._b, self._c
-        rd = self._rdense
+        ops, log = self._ops, self._round_log
+        B, n, d, dn = self._rB, self.n, self.n // self._rB, self._rdense
         # the stages of a reversed round.  With interpolated outputs whose extension uses the last stage of a first-same-as-last
         # tableau, that stage is an ordinary one here (nothing is routed between rounds: stage 0 is re-evaluated every round):
         # Y_{s-1} = u + h sum_j a_{s-1,j} K_j, cotangent D_{s-1} alone -- one more evaluation and VJP per reversed round
-        stages = list(range(s_eff))
-        if rd and self._fsal and (self._s - 1) in self._dense_cols:
+        stages = list(range(self._s_eff))
+        if dn is not None and self._fsal and (self._s - 1) in dn.cols:
             stages.append(self._s - 1)
         lam = self.adj_u_tensor = self.adj_u_flat = ops.empty(n)
         lam.zero_()
-        if self.adj_p_tensor is None or self.adj_p_tensor.numel() != self.np:
-            self.adj_p_tensor = ops.empty(max(self.np, 1))[: self.np]
-        self.adj_p_tensor.zero_()
-        self._pend_a, self._pend_g = [], []
-        self._pend_mixed = False
-        self._pend_bias, self._pend_bias_bytes = [], 0
+        self._begin_param_adjoint()
         g = g.contiguous()
         ld = g.stride(0)
         R = self.rounds
@@ -309,86 +326,59 @@ class RowSweep(object):
             ops.rows_adj_accum(B, d, lam, lam, [], g, ld, ops.i32(B), T)
             return
         hit0 = ops.i32(B) if T > 1 else None           # every row's state at t[0] is u0
-        ops.rows_adj_accum(B, d, lam, lam, [], g, ld, self._rows_log_at(R - 1)[1], T)
-        wbuf = ops.empty(n)
-        ybuf = [None] + [ops.empty(n) for _ in range(1, stages[-1] + 1)]
-        if rd:
-            cols = self._dense_cols
-            Dbuf = dict((j, ops.empty(n)) for j in cols)
-            Gbuf = ops.empty(n)
+        ops.rows_adj_accum(B, d, lam, lam, [], g, ld, log[R - 1].hit, T)
+        rv = types.SimpleNamespace(stages=stages, lam=lam, w=ops.empty(n), y=[None] + [ops.empty(n) for _ in range(1, stages[-1] + 1)],
+                                   D=dict((j, ops.empty(n)) for j in (dn.cols if dn is not None else ())), G=ops.empty(n) if dn is not None else None)
         for k in range(R - 1, -1, -1):
-            log_d, _ = self._rows_log_at(k)
-            heff, tr, tf = log_d[0], log_d[1], log_d[2]
-            u = self._rtraj[k]
-            Y = self._rY[k] if self._rY is not None else None
-            tapes, K = {}, {}
-            for i in stages:
-                if i == 0:
-                    y, targ = u, tf.clone()
-                else:
-                    if Y is not None and i < s_eff:
-                        y = Y[i]
-                    else:
-                        y = ybuf[i]
-                        idx = [j for j in range(i) if A[i][j] != 0.0]
-                        ops.rows_stage(B, d, y, u, [K[j] for j in idx], [A[i][j] for j in idx], heff)
-                    targ = tr + c[i] * heff
-                rec = []
-                K[i] = self._rows_func(self._rows_t(targ), y, rec)
-                tapes[i] = rec[0]
-                self.nfe_backward += 1
-            if rd:
+            rnd = log[k]
+            # the round's stage evaluations again, recorded by autograd: on the stage values the forward sweep kept, else on
+            # ones recomputed from the round's state with the logged h_eff
+            kept = self._rY[k] if self._rY is not None else [self._rtraj[k]]
+            tapes = {}
+            self._rows_stages(stages, kept + rv.y[len(kept):], range(len(kept)), rnd.heff, rnd.t, rnd.tfirst, tapes)
+            if dn is not None:
                 # D_j[r] = sum_o h_r beta_j(theta_o) g[o, r] over the outputs row r interpolated in this round, G[r] = sum_o g[o, r]
-                ops.rows_dense_adjoint(B, d, [Dbuf[j] for j in cols], Gbuf, g, self._rtimes, self._rP, self._rows_range_at(k), log_d)
+                ops.rows_dense_adjoint(B, d, [rv.D[j] for j in dn.cols], rv.G, g, dn.times, dn.P, rnd.range, rnd.log_d)
             dlam = [None] * self._s
             for i in reversed(stages):
-                js = [j for j in stages if j > i and A[j][i] != 0.0 and dlam[j] is not None]
-                Di = Dbuf.get(i) if rd else None
-                if b[i] == 0.0 and not js and Di is None:
-                    continue
-                if b[i] == 0.0 and not js:
-                    w = Di                               # the stage's cotangent is what its outputs send it
-                else:
-                    w = wbuf
-                    if Di is None:
-                        ops.rows_adj_theta(B, d, w, lam if b[i] != 0.0 else None, b[i], [dlam[j] for j in js], [A[j][i] for j in js], heff)
-                    else:
-                        ops.rows_adj_theta(B, d, w, lam if b[i] != 0.0 else None, b[i], [dlam[j] for j in js], [A[j][i] for j in js], heff,
-                                           dense_w=Di)
-                y, out, wrt = tapes[i]
-                tapes[i] = None
-                grads = torch.autograd.grad(out, (y,) + tuple(wrt), self._shaped(w).view(out.shape), allow_unused=True)
-                gy = grads[0]
-                if gy is not None:
-                    if gy.dtype != self.tensor_dtype:
-                        gy = gy.to(self.tensor_dtype)
-                    gy = gy.contiguous().reshape(-1)
-                    if gy.untyped_storage().data_ptr() == w.untyped_storage().data_ptr():
-                        gy = gy.clone()
-                dlam[i] = gy
-                wst = w.untyped_storage().data_ptr()
-                gp = []
-                for q in grads[1:]:
-                    if q is not None:
-                        if q.dtype != self.tensor_dtype or not q.is_contiguous():
-                            q = q.to(self.tensor_dtype).contiguous()
-                        if q.untyped_storage().data_ptr() == wst:
-                            q = q.clone()
-                    gp.append(q)
-                if self.np > 0 and any(q is not None for q in gp):
-                    self._pend_a.append(1.0)              # the row's h is inside the cotangent
-                    self._pend_g.append(gp)
+                w = self._rows_cotangent(rv, i, dlam, rnd.heff)
+                if w is not None:
+                    dlam[i] = self._rows_vjp(tapes, i, w)
             self._flush_param_accum()
+            # lambda += sum_i dlam_i (+ G) (+ g at the output the previous round landed on), at most PN_MAX_STAGES terms a launch
             terms = [dlam[i] for i in stages if dlam[i] is not None]
-            if rd:
-                terms.append(Gbuf)
+            if dn is not None:
+                terms.append(rv.G)
             if len(terms) > _lib.PN_MAX_STAGES:          # (5dp with interpolated outputs: seven stages and G)
                 ops.rows_adj_accum(B, d, lam, lam, terms[_lib.PN_MAX_STAGES:], None, ld, None, T)
                 terms = terms[: _lib.PN_MAX_STAGES]
-            hit_prev = self._rows_log_at(k - 1)[1] if k > 0 else hit0
+            hit_prev = log[k - 1].hit if k > 0 else hit0
             ops.rows_adj_accum(B, d, lam, lam, terms, g if hit_prev is not None else None, ld, hit_prev, T)
             self._rtraj[k] = None
             if self._rY is not None:
                 self._rY[k] = None
         self._flush_param_accum()
 
+    def _rows_cotangent(self, rv, i, dlam, heff):
+        """Stage i's cotangent w_i[r] = h_r (b_i lambda[r] + sum_{j>i} a_ji dlam_j[r]) (+ D_i[r], what the row's interpolated
+        outputs send the stage); None when it is structurally zero."""
+        A, b = self._A, self._b
+        js = [j for j in rv.stages if j > i and A[j][i] != 0.0 and dlam[j] is not None]
+        Di = rv.D.get(i)
+        if b[i] == 0.0 and not js:
+            return Di                                # (the stage's cotangent is what its outputs send it, if anything)
+        kw = {} if Di is None else {"dense_w": Di}
+        self._ops.rows_adj_theta(self._rB, self.n // self._rB, rv.w, rv.lam if b[i] != 0.0 else None, b[i], [dlam[j] for j in js],
+                                 [A[j][i] for j in js], heff, **kw)
+        return rv.w
+
+    def _rows_vjp(self, tapes, i, w):
+        """The backward half of stage i with cotangent `w`: returns J^T w; the parameter cotangents are queued for mu."""
+        y, out, wrt = tapes[i]
+        tapes[i] = None
+        grads = torch.autograd.grad(out, (y,) + tuple(wrt), self._shaped(w).view(out.shape), allow_unused=True)
+        gy, gp = self._vjp_results(grads[0], grads[1:], w)
+        if gy is not None and gy.untyped_storage().data_ptr() == w.untyped_storage().data_ptr():
+            gy = gy.clone()
+        self._take_param_grads(1.0, gp)           # (the row's h is inside the cotangent; one launch per round)
+        return gy

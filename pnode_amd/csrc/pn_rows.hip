@@ -481,27 +481,37 @@ RowsGeom geom(int64_t B, int64_t d) {
 
 dim3 grid_for(const RowsGeom &q) { return dim3((unsigned)pn::blocks_for(q.B, kBlock >> q.lgG, kRowsMaxBlocks)); }
 
+// What the launchers below end in: the row geometry of (B, d), the vector form when the caller's operands are `aligned` and d is
+// a whole number of chunks, and for the N == n of [LO, HI] the kernel pick(N, V) names (V: std::true_type for the vector form)
+// on the capped grid.  pn::kNoCase when n is outside [LO, HI]: the caller's refusal.
+template <typename T, int LO, int HI, typename Args, typename Pick>
+int rows_launch(const char *name, hipStream_t st, int64_t B, int64_t d, bool aligned, int n, const Args &a, Pick pick) {
+  const bool vec = aligned && d % (int64_t)(16 / sizeof(T)) == 0;
+  const RowsGeom q = geom<T>(B, d);
+  return pn::with_count<LO, HI>(n, [&](auto N) {
+    return pn::launch(name, vec ? pick(N, std::true_type{}) : pick(N, std::false_type{}), grid_for(q), dim3(kBlock), st, a, q);
+  });
+}
+
 template <typename T>
 int rows_lin(hipStream_t st, int64_t B, int64_t d, void *out, const void *base, int nk, const void *const *x, const double *c,
              const double *h, const char *name, const void *tail = nullptr) {
-  constexpr int VW = 16 / sizeof(T);
   RowsLinArgs<T> a = {};
   a.out = (T *)out;
   a.base = (const T *)base;
   a.h = h;
   a.tail = (const T *)tail;
-  const bool vec = (d % VW) == 0 && pn::aligned16(out, base, tail) && pn::aligned16(x, nk);
   for (int j = 0; j < nk; ++j) {
     a.x[j] = (const T *)x[j];
     a.c[j] = c[j];
   }
-  const RowsGeom q = geom<T>(B, d);
-  const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+  const bool al = pn::aligned16(out, base, tail) && pn::aligned16(x, nk);
+  const int rc = rows_launch<T, 1, PN_MAX_STAGES>(name, st, B, d, al, nk, a, [&](auto N, auto V) {
     constexpr int NK = decltype(N)::value;
-    auto kern = base ? (vec ? pn_rows_lin_kernel<T, NK, true, true> : pn_rows_lin_kernel<T, NK, false, true>)
-                     : (vec ? pn_rows_lin_kernel<T, NK, true, false> : pn_rows_lin_kernel<T, NK, false, false>);
-    if (tail && !base) kern = vec ? pn_rows_lin_kernel<T, NK, true, false, true> : pn_rows_lin_kernel<T, NK, false, false, true>;
-    return pn::launch(name, kern, grid_for(q), dim3(kBlock), st, a, q);
+    constexpr bool VEC = decltype(V)::value;
+    auto kern = base ? pn_rows_lin_kernel<T, NK, VEC, true> : pn_rows_lin_kernel<T, NK, VEC, false>;
+    if (tail && !base) kern = pn_rows_lin_kernel<T, NK, VEC, false, true>;
+    return kern;
   });
   if (rc == pn::kNoCase) return pn::fail(std::string(name) + ": nk out of range");
   return rc;
@@ -510,7 +520,6 @@ int rows_lin(hipStream_t st, int64_t B, int64_t d, void *out, const void *base, 
 template <typename T>
 int rows_combine(hipStream_t st, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K, const double *cb,
                  const double *ce, const double *h, double atol, double rtol, double *enorm) {
-  constexpr int VW = 16 / sizeof(T);
   RowsErrArgs<T> a = {};
   a.unew = (T *)unew;
   a.u = (const T *)u;
@@ -518,18 +527,16 @@ int rows_combine(hipStream_t st, int64_t B, int64_t d, void *unew, const void *u
   a.enorm = enorm;
   a.atol = atol;
   a.rtol = rtol;
-  const bool vec = (d % VW) == 0 && pn::aligned16(u, unew) && pn::aligned16(K, nk);
   for (int j = 0; j < nk; ++j) {
     a.k[j] = (const T *)K[j];
     a.cb[j] = cb ? cb[j] : 0.0;
     a.ce[j] = ce[j];
   }
-  const RowsGeom q = geom<T>(B, d);
-  const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+  const bool al = pn::aligned16(u, unew) && pn::aligned16(K, nk);
+  const int rc = rows_launch<T, 1, PN_MAX_STAGES>("pn_rows_combine_wrms", st, B, d, al, nk, a, [&](auto N, auto V) {
     constexpr int NK = decltype(N)::value;
-    auto kern = unew ? (vec ? pn_rows_combine_wrms_kernel<T, NK, true, true> : pn_rows_combine_wrms_kernel<T, NK, false, true>)
-                     : (vec ? pn_rows_combine_wrms_kernel<T, NK, true, false> : pn_rows_combine_wrms_kernel<T, NK, false, false>);
-    return pn::launch("pn_rows_combine_wrms", kern, grid_for(q), dim3(kBlock), st, a, q);
+    constexpr bool VEC = decltype(V)::value;
+    return unew ? pn_rows_combine_wrms_kernel<T, NK, VEC, true> : pn_rows_combine_wrms_kernel<T, NK, VEC, false>;
   });
   return pn::or_fail(rc, "pn_rows_combine_wrms: nk out of range");
 }
@@ -564,13 +571,10 @@ int rows_accum(hipStream_t st, int64_t B, int64_t d, void *out, const void *lam,
   a.hit = hit;
   a.ld = ld;
   a.nout = nout;
-  const bool vec = (d % VW) == 0 && pn::aligned16(out, lam, g) && (!g || (ld % VW) == 0) && pn::aligned16(x, nk);
   for (int j = 0; j < nk; ++j) a.x[j] = (const T *)x[j];
-  const RowsGeom q = geom<T>(B, d);
-  const int rc = pn::with_count<0, PN_MAX_STAGES>(nk, [&](auto N) {
-    constexpr int NK = decltype(N)::value;
-    return pn::launch("pn_rows_adj_accum", vec ? pn_rows_adj_accum_kernel<T, NK, true> : pn_rows_adj_accum_kernel<T, NK, false>, grid_for(q),
-                      dim3(kBlock), st, a, q);
+  const bool al = pn::aligned16(out, lam, g) && (!g || (ld % VW) == 0) && pn::aligned16(x, nk);
+  const int rc = rows_launch<T, 0, PN_MAX_STAGES>("pn_rows_adj_accum", st, B, d, al, nk, a, [](auto N, auto V) {
+    return pn_rows_adj_accum_kernel<T, decltype(N)::value, decltype(V)::value>;
   });
   return pn::or_fail(rc, "pn_rows_adj_accum: nk out of range");
 }
@@ -597,12 +601,9 @@ int rows_dense_eval(hipStream_t st, int64_t B, int64_t d, const void *u, int nk,
     a.k[j] = (const T *)K[j];
     for (int p = 0; p < PN_DENSE_MAX_POW; ++p) a.P[j][p] = P[j * PN_DENSE_MAX_POW + p];
   }
-  const bool vec = (d % VW) == 0 && pn::aligned16(u, unew, sol) && (ld % VW) == 0 && pn::aligned16(K, nk);
-  const RowsGeom q = geom<T>(B, d);
-  const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
-    constexpr int NK = decltype(N)::value;
-    return pn::launch("pn_rows_dense_eval", vec ? pn_rows_dense_eval_kernel<T, NK, true> : pn_rows_dense_eval_kernel<T, NK, false>,
-                      grid_for(q), dim3(kBlock), st, a, q);
+  const bool al = pn::aligned16(u, unew, sol) && (ld % VW) == 0 && pn::aligned16(K, nk);
+  const int rc = rows_launch<T, 1, PN_MAX_STAGES>("pn_rows_dense_eval", st, B, d, al, nk, a, [](auto N, auto V) {
+    return pn_rows_dense_eval_kernel<T, decltype(N)::value, decltype(V)::value>;
   });
   return pn::or_fail(rc, "pn_rows_dense_eval: nk out of range");
 }
@@ -624,12 +625,9 @@ int rows_dense_adjoint(hipStream_t st, int64_t B, int64_t d, const void *g, int6
     a.d[j] = (T *)D[j];
     for (int p = 0; p < PN_DENSE_MAX_POW; ++p) a.P[j][p] = P[j * PN_DENSE_MAX_POW + p];
   }
-  const bool vec = (d % VW) == 0 && pn::aligned16(g, G) && (ld % VW) == 0 && pn::aligned16(D, nd);
-  const RowsGeom q = geom<T>(B, d);
-  const int rc = pn::with_count<1, PN_MAX_STAGES>(nd, [&](auto N) {
-    constexpr int ND = decltype(N)::value;
-    return pn::launch("pn_rows_dense_adjoint", vec ? pn_rows_dense_adjoint_kernel<T, ND, true> : pn_rows_dense_adjoint_kernel<T, ND, false>,
-                      grid_for(q), dim3(kBlock), st, a, q);
+  const bool al = pn::aligned16(g, G) && (ld % VW) == 0 && pn::aligned16(D, nd);
+  const int rc = rows_launch<T, 1, PN_MAX_STAGES>("pn_rows_dense_adjoint", st, B, d, al, nd, a, [](auto N, auto V) {
+    return pn_rows_dense_adjoint_kernel<T, decltype(N)::value, decltype(V)::value>;
   });
   return pn::or_fail(rc, "pn_rows_dense_adjoint: nd out of range");
 }
@@ -637,6 +635,29 @@ int rows_dense_adjoint(hipStream_t st, int64_t B, int64_t d, const void *g, int6
 int bad_shape(const char *name, int64_t B, int64_t d) {
   if (B < 1 || d < 1 || B > ((int64_t)1 << 40) / d) return pn::fail(std::string(name) + ": B and d must be positive");
   return 0;
+}
+
+// pn_rows_adj_theta and, with the D_i of a row's interpolated outputs as the last term (`dense`), pn_rows_adj_theta_dense
+int rows_adj_theta(const char *name, void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam, int nk,
+                   const void *const *dlam, const double *coef, const double *h, const void *dense_w, bool dense) {
+  if (bad_shape(name, B, d)) return 1;
+  if (!w || !h || (dense && !dense_w) || nk < 0 || nk > PN_MAX_STAGES - 1 || (nk > 0 && (!dlam || !coef)) || (!lambda && nk == 0))
+    return pn::fail(std::string(name) + ": null argument or nk outside 0..6");
+  const void *x[PN_MAX_TERMS];
+  double c[PN_MAX_TERMS];
+  int n = 0;
+  if (lambda) {
+    x[n] = lambda;
+    c[n++] = c_lam;
+  }
+  for (int j = 0; j < nk; ++j) {
+    if (!dlam[j]) return pn::fail(std::string(name) + ": null vector");
+    x[n] = dlam[j];
+    c[n++] = coef[j];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_lin<decltype(t)>(st, B, d, w, nullptr, n, x, c, h, name, dense_w); });
+  return rc == pn::kNoCase ? pn::fail(std::string(name) + ": unknown dtype") : rc;
 }
 
 }  // namespace
@@ -695,24 +716,7 @@ int pn_rows_commit(void *stream, int dtype, int64_t B, int64_t d, void *unext, c
 
 int pn_rows_adj_theta(void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam, int nk,
                       const void *const *dlam, const double *coef, const double *h) {
-  if (bad_shape("pn_rows_adj_theta", B, d)) return 1;
-  if (!w || !h || nk < 0 || nk > PN_MAX_STAGES - 1 || (nk > 0 && (!dlam || !coef)) || (!lambda && nk == 0))
-    return pn::fail("pn_rows_adj_theta: null argument or nk outside 0..6");
-  const void *x[PN_MAX_TERMS];
-  double c[PN_MAX_TERMS];
-  int n = 0;
-  if (lambda) {
-    x[n] = lambda;
-    c[n++] = c_lam;
-  }
-  for (int j = 0; j < nk; ++j) {
-    if (!dlam[j]) return pn::fail("pn_rows_adj_theta: null vector");
-    x[n] = dlam[j];
-    c[n++] = coef[j];
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_lin<decltype(t)>(st, B, d, w, nullptr, n, x, c, h, "pn_rows_adj_theta"); });
-  return pn::or_fail(rc, "pn_rows_adj_theta: unknown dtype");
+  return rows_adj_theta("pn_rows_adj_theta", stream, dtype, B, d, w, lambda, c_lam, nk, dlam, coef, h, nullptr, false);
 }
 
 int pn_rows_adj_accum(void *stream, int dtype, int64_t B, int64_t d, void *lambda_out, const void *lambda, int nk,
@@ -729,26 +733,7 @@ int pn_rows_adj_accum(void *stream, int dtype, int64_t B, int64_t d, void *lambd
 
 int pn_rows_adj_theta_dense(void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam, int nk,
                             const void *const *dlam, const double *coef, const double *h, const void *dense_w) {
-  if (bad_shape("pn_rows_adj_theta_dense", B, d)) return 1;
-  if (!w || !h || !dense_w || nk < 0 || nk > PN_MAX_STAGES - 1 || (nk > 0 && (!dlam || !coef)) || (!lambda && nk == 0))
-    return pn::fail("pn_rows_adj_theta_dense: null argument or nk outside 0..6");
-  const void *x[PN_MAX_TERMS];
-  double c[PN_MAX_TERMS];
-  int n = 0;
-  if (lambda) {
-    x[n] = lambda;
-    c[n++] = c_lam;
-  }
-  for (int j = 0; j < nk; ++j) {
-    if (!dlam[j]) return pn::fail("pn_rows_adj_theta_dense: null vector");
-    x[n] = dlam[j];
-    c[n++] = coef[j];
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = pn::with_dtype(dtype, [&](auto t) {
-    return rows_lin<decltype(t)>(st, B, d, w, nullptr, n, x, c, h, "pn_rows_adj_theta_dense", dense_w);
-  });
-  return pn::or_fail(rc, "pn_rows_adj_theta_dense: unknown dtype");
+  return rows_adj_theta("pn_rows_adj_theta_dense", stream, dtype, B, d, w, lambda, c_lam, nk, dlam, coef, h, dense_w, true);
 }
 
 int pn_rows_dense_eval(void *stream, int dtype, int64_t B, int64_t d, const void *u, int nk, const void *const *K, const double *P,

@@ -51,6 +51,28 @@ def test_abi_version_and_error_channel():
         _lib.check(lib.pn_tableau_get(b"nope", ctypes.byref(t)))
 
 
+def test_the_rows_state_constants_are_the_headers():
+    """The rows of the per-sample controllers' state (sd, si) as Python indexes them: every enumerator of the two PN_ROWS_*
+    enums of csrc/pn_adapt.h, by C's counting rule, equals the binding's constant of that name -- and none is missing."""
+    src = open(os.path.join(ROOT, "pnode_amd", "csrc", "pn_adapt.h")).read()
+    enums = [m for m in re.findall(r"enum \{([^}]*)\};", src) if "PN_ROWS_" in m]
+    assert len(enums) == 2
+    seen = {}
+    for body in enums:
+        value = -1
+        for item in body.split(","):
+            name, _, explicit = [x.strip() for x in item.partition("=")]
+            value = int(explicit) if explicit else value + 1
+            seen[name] = value
+    assert len(seen) == 13 and seen["PN_ROWS_ND"] == 4 and seen["PN_ROWS_NI"] == 8
+    for name, value in seen.items():
+        assert getattr(_lib, name) == value, name
+    assert sorted(n for n in dir(_lib) if n.startswith("PN_ROWS_")) == sorted(seen)
+    assert int(re.search(r"#define PN_ROWS_DENSE_POW (\d+)", src).group(1)) == _lib.PN_DENSE_MAX_POW
+    header = open(os.path.join(ROOT, "include", "pnode_amd.h")).read()
+    assert int(re.search(r"#define PN_DENSE_MAX_POW (\d+)", header).group(1)) == _lib.PN_DENSE_MAX_POW
+
+
 def test_prof_collect_fills_no_more_than_the_callers_arrays_hold():
     """pn_prof_collect(count, ...): a client built against a shorter pn_kernel_id enum passes its own array length and is not
     overrun (PN_K_COUNT grew from 8 to 9 under an unchanged ABI version)."""

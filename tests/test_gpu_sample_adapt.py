@@ -213,18 +213,18 @@ def test_rows_control_is_the_host_controller(B, case, nspan):
     g = torch.Generator().manual_seed(B + nspan)
     span = torch.tensor([0.0, 0.1, 0.25, 0.4], dtype=torch.float64)
     tmax = 0.4
-    sd = torch.zeros(4, B, dtype=torch.float64)
-    sd[0] = 0.1 * torch.rand(B, generator=g, dtype=torch.float64)
-    sd[1] = 0.001 + 0.05 * torch.rand(B, generator=g, dtype=torch.float64)
-    sd[2] = sd[0]
-    si = torch.zeros(8, B, dtype=torch.int32)
+    sd = torch.zeros(_lib.PN_ROWS_ND, B, dtype=torch.float64)
+    sd[_lib.PN_ROWS_T] = 0.1 * torch.rand(B, generator=g, dtype=torch.float64)
+    sd[_lib.PN_ROWS_H] = 0.001 + 0.05 * torch.rand(B, generator=g, dtype=torch.float64)
+    sd[_lib.PN_ROWS_TFIRST] = sd[_lib.PN_ROWS_T]
+    si = torch.zeros(_lib.PN_ROWS_NI, B, dtype=torch.int32)
     if nspan:
-        si[0] = 1
+        si[_lib.PN_ROWS_SPANCTR] = 1
     enorm = torch.exp(2.0 * torch.randn(B, generator=g, dtype=torch.float64)) * 0.5
     if case == "all-rejected":
         enorm = enorm + 1.5
     if case == "all-finished":
-        si[5] = 1
+        si[_lib.PN_ROWS_FINISHED] = 1
     if case == "nan-row":
         enorm[B // 2] = float("nan")
     outs = []

@@ -111,7 +111,7 @@ if a.from_trace:
     sys.exit(0)
 
 import torch  # noqa: E402
-from pnode_amd import options, petsc_adjoint  # noqa: E402
+from pnode_amd import _lib, options, petsc_adjoint  # noqa: E402
 from pnode_amd._vecops import HipVecOps  # noqa: E402
 from problems import MLPFunc, SpiralFunc  # noqa: E402
 dev = torch.device("cuda:0")
@@ -202,8 +202,8 @@ if not a.only_solves:
     import ctypes
     ts = ctypes.c_void_p(lib.pn_ts_create())
     lib.pn_ts_set_rk_type(ts, b"5dp")
-    sd, si = ops.f64(4, B), ops.i32(8, B)
-    sd[1].fill_(1e-6)
+    sd, si = ops.f64(_lib.PN_ROWS_ND, B), ops.i32(_lib.PN_ROWS_NI, B)
+    sd[_lib.PN_ROWS_H].fill_(1e-6)
     en = torch.full((B,), 0.5, dtype=torch.float64, device=dev)
     log_d, log_hit, summary = ops.f64(3, B), ops.i32(B), ops.i32(4)
     for _ in range(a.launches):
