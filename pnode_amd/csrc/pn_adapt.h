@@ -56,6 +56,10 @@ PN_HD bool pn_ctl_close_rel(double a, double b, double rtol) {
 // -1) and *done (1 final time reached, 2 stopped by max_steps) as pn_ts_judge documents them.
 PN_HD int pn_ctl_judge(const PnCtlCfg &c, const double *span, PnCtlState &s, double enorm, int *accept_out, int *hit_span,
                        int *done) {
+  // (see pn_rows_judge_row: the host and the device must round alike; here span_reltol * fabs(h) + span_abstol is the candidate)
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   const double h = s.time_step;
   bool accept = true;
   double hnew = h;
@@ -158,6 +162,13 @@ struct PnRowsCtl {
 
 PN_HD int pn_rows_judge_row(const PnRowsCtl &rc, const double *span, int64_t B, int64_t r, const double *enorm, double *sd,
                             int32_t *si, double *log_d, int32_t *log_hit, int32_t *accept) {
+  // Contraction is switched off, as in pn_rows_dense_coef below: hipcc fused t0 + c_last * h0 (the first-stage time of a
+  // first-same-as-last tableau) into one rounding on the device, the host rounds twice.  5dp's c_last is 1 - 2^-52, so the
+  // product rounds whenever h0 is no power of two, and the two forms of t_first differed in the last bit: from t0 = 11/128
+  // with h0 = 5/128 the host gives 1/8, the fused form 1/8 - 2^-56 (tests/test_gpu_rows_controller.py, exact scripts).
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   const double t0 = sd[PN_ROWS_T * B + r], h0 = sd[PN_ROWS_H * B + r], tf0 = sd[PN_ROWS_TFIRST * B + r];
   log_d[B + r] = t0;
   log_d[2 * B + r] = tf0;
