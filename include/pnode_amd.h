@@ -479,6 +479,44 @@ int pn_rows_dense_adjoint(void *stream, int dtype, int64_t B, int64_t d, const v
  * w[r] = (h[r]*c_lam) lambda[r] + sum_{j<nk} (h[r]*coef[j]) dlam[j][r] + dense_w[r]. */
 int pn_rows_adj_theta_dense(void *stream, int dtype, int64_t B, int64_t d, void *w, const void *lambda, double c_lam,
                             int nk, const void *const *dlam, const double *coef, const double *h, const void *dense_w);
+/* dL/dt of a per-sample solve (the reference returns no gradient for the output times, pa.py:947):
+ * row r is a batch-of-one solve and its dL/dt is section 5.6's rule on its own logged steps; dtrow = doubles [nout][B]
+ * holds what each row sends to each output time, and dL/dt is its sum over the rows.  Nothing waits for the host.
+ * pn_rows_tgrad_dots: rowacc[r] (+)= sum_{p<np} coef[p] <x[p][r], y[p][r]> (np <= PN_MAX_STAGES; accumulate 0: overwritten),
+ * products and sums in double, in the geometry and the tree of pn_rows_combine_wrms: a row's bits do not depend on B.
+ * pn_rows_dense_tgrad: erow[o*B + r] = sum_{j<nk} beta'_j(theta) <g[o*ld + r*d ..], K[j][r]> for the outputs lo_r <= o < hi_r
+ * of the round's logged range, theta = (times[o] - t_r)/h_r and beta'_j(theta) = sum_p (p+1) P[j][p] theta^p formed in double
+ * (Horner, the shared text of csrc/pn_adapt.h); entries outside a row's range are not written.  pn_rows_dense_tgrad_host:
+ * theta ([nout][B]) and beta' (dcoef, may be NULL: [nout][B][nk]) of the same ranges on host arrays (no device).
+ * pn_rows_tgrad_scatter: one reversed round into every row's own column of dtrow (no atomics), from the round's log.  The
+ * output interval [is, ie] of the round: with `range` (interpolated outputs) [0, nout-1], the step is its last when
+ * log_hit[r] == nout-1; else ie = the output the row last landed on in the reversed order (kept in iv[r]; the step with
+ * log_hit[r] >= 0 is the interval's last) and is = ie-1 (none when nout == 1).  With q = sum_j tbar[j][r] (+ held[r]) and
+ * p = rowacc[r]/h_r + sum_j coef[j] tbar[j][r] (+ c_last held[r]): dtrow[is] += q, and for the last step dtrow[ie] += p,
+ * dtrow[is] -= p.  fsal: stage 0 of the round was evaluated by the row's previous accepted step, so held[r] is replaced by
+ * tbar0[r] (NULL: 0) for the round that reverses that step.  An output o of the range adds erow[o*B + r] to dtrow[o], takes
+ * it from q and theta times it from p.  Rows with h_eff == 0 are not touched.  flush != 0 (after the last reversed round):
+ * dtrow[0] += held[r] when nout > 1 (the row's first step evaluated stage 0 at t[0] itself), held[r] = 0.  held: B doubles,
+ * iv: B int32, zero and nout-1 at the start of a reverse sweep.  pn_rows_tgrad_scatter_host: the same on host arrays.
+ * pn_rows_tgrad_reduce: dt[i] = sum_r dtrow[i*B + r] in a fixed order (per-workgroup partials, the last workgroup adds them in
+ * index order; the grid depends on B and nout alone).  `work`: pn_rows_tgrad_work_bytes(B, nout) bytes, ZERO-FILLED once. */
+int pn_rows_tgrad_dots(void *stream, int dtype, int64_t B, int64_t d, int np, const void *const *x, const void *const *y,
+                       const double *coef, double *rowacc, int accumulate);
+int pn_rows_dense_tgrad(void *stream, int dtype, int64_t B, int64_t d, const void *g, int64_t ld, int nout,
+                        const double *times_dev, const double *log_d, const int32_t *range, int nk, const double *P,
+                        const void *const *K, double *erow);
+int pn_rows_dense_tgrad_host(int64_t B, int nout, const double *times, const double *log_d, const int32_t *range, int nk,
+                             const double *P, double *theta, double *dcoef);
+int pn_rows_tgrad_scatter(void *stream, int64_t B, int nout, double *dtrow, const double *rowacc, int nt,
+                          const double *const *tbar, const double *coef, const double *tbar0, double c_last, int fsal,
+                          const double *log_d, const int32_t *log_hit, const int32_t *range, const double *erow,
+                          const double *times_dev, double *held, int32_t *iv, int flush);
+int pn_rows_tgrad_scatter_host(int64_t B, int nout, double *dtrow, const double *rowacc, int nt, const double *const *tbar,
+                               const double *coef, const double *tbar0, double c_last, int fsal, const double *log_d,
+                               const int32_t *log_hit, const int32_t *range, const double *erow, const double *times,
+                               double *held, int32_t *iv, int flush);
+int64_t pn_rows_tgrad_work_bytes(int64_t B, int nout);
+int pn_rows_tgrad_reduce(void *stream, int64_t B, int nout, const double *dtrow, double *dt, void *work);
 
 /* ------------------------------------------------------------------------------------------
  * 3b. GMRES core for the implicit (theta-method) stage solves: the small dense part of

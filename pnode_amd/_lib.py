@@ -96,6 +96,13 @@ PROTOTYPES = {
     "pn_rows_dense_plan_host": (_i, [_i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _pd, _vp]),
     "pn_rows_dense_adjoint": (_i, [_vp, _i, _i64, _i64, _vp, _i64, _i, _vp, _vp, _vp, _i, _pd, _pvp, _vp]),
     "pn_rows_adj_theta_dense": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _d, _i, _pvp, _pd, _vp, _vp]),
+    "pn_rows_tgrad_dots": (_i, [_vp, _i, _i64, _i64, _i, _pvp, _pvp, _pd, _vp, _i]),
+    "pn_rows_dense_tgrad": (_i, [_vp, _i, _i64, _i64, _vp, _i64, _i, _vp, _vp, _vp, _i, _pd, _pvp, _vp]),
+    "pn_rows_dense_tgrad_host": (_i, [_i64, _i, _vp, _vp, _vp, _i, _pd, _vp, _vp]),
+    "pn_rows_tgrad_scatter": (_i, [_vp, _i64, _i, _vp, _vp, _i, _pvp, _pd, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "pn_rows_tgrad_scatter_host": (_i, [_i64, _i, _vp, _vp, _i, _pvp, _pd, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "pn_rows_tgrad_work_bytes": (_i64, [_i64, _i]),
+    "pn_rows_tgrad_reduce": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
     "pn_last_error": (_cp, []),
     "pn_abi_version": (_i, []),
     "pn_tableau_get": (_i, [_cp, ctypes.POINTER(Tableau)]),

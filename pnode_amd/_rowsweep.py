@@ -11,7 +11,11 @@ h_eff = 0 is the identity on that row in both sweeps, so the rounds are reversed
 With ``-pn_output_times interpolate`` (a backend with the row-dense entry points, ``rows_dense``) the controller sees
 ``[t[0], t[-1]]`` only: every row takes the steps its own tolerance asks for, and after each round pn_rows_dense_eval fills the
 output times an accepted attempt has passed from the tableau's continuous extension (the output times and a per-row "next
-output" counter live on the device; the round's log grows by the range [lo, hi) of outputs each row interpolated)."""
+output" counter live on the device; the round's log grows by the range [lo, hi) of outputs each row interpolated).
+
+dL/dt (``t.requires_grad``, a backend with ``rows_tgrad``): every row's dL/dt is DESIGN.md section 5.6's rule on its own logged
+steps.  Per reversed round the rows' <w_j, K_j> and <w_j, df/dt> are gathered on the device and pn_rows_tgrad_scatter sends them
+into the row's own column of an fp64 [T][B] matrix (``sample_time_grads``); one ordered sum over the rows at the end is t.grad."""
 import collections
 import ctypes
 import types
@@ -56,6 +60,7 @@ class RowSweep(object):
     rounds = 0
     sample_steps = None
     sample_rejections = None
+    sample_time_grads = None      # after a backward with t.requires_grad: fp64 [T][B], what row r sends to dL/dt_i (its sum over r is t.grad)
 
     # ------------------------------------------------------------------ surface
     def _rows_refusals(self):
@@ -86,6 +91,8 @@ class RowSweep(object):
 
     def _tgrad_supported(self):
         if self._sample:
+            if getattr(self._ops, "rows_tgrad", False):
+                return super(RowSweep, self)._tgrad_supported()          # (-pn_reference_defaults keeps the reference's None)
             if not self._tg_warned:
                 self._tg_warned = True
                 warnings.warn("pnode_amd: the gradient with respect to the output times t is not built under -pn_adapt_scope "
@@ -129,8 +136,11 @@ class RowSweep(object):
             if tape is not None:
                 with torch.enable_grad():
                     y = y.detach().requires_grad_(True)
+                    if self._tgrad:
+                        # dL/dt: the rows' times are one more leaf of this evaluation (its gradient: <w, df/dt> per row)
+                        targ = targ.detach().requires_grad_(True)
                     k, wrt = self._func_with_grad(targ, y)
-                tape.append((y, k, wrt))
+                tape.append((y, k, wrt, targ) if self._tgrad else (y, k, wrt))
             else:
                 k = self.funcEX(targ, y)
         except Exception as exc:
@@ -322,8 +332,10 @@ class RowSweep(object):
         g = g.contiguous()
         ld = g.stride(0)
         R = self.rounds
+        tg = self._rows_tg_begin(T) if self._tgrad else None
         if R == 0:
             ops.rows_adj_accum(B, d, lam, lam, [], g, ld, ops.i32(B), T)
+            self._rows_tg_end(tg)
             return
         hit0 = ops.i32(B) if T > 1 else None           # every row's state at t[0] is u0
         ops.rows_adj_accum(B, d, lam, lam, [], g, ld, log[R - 1].hit, T)
@@ -335,7 +347,9 @@ class RowSweep(object):
             # ones recomputed from the round's state with the logged h_eff
             kept = self._rY[k] if self._rY is not None else [self._rtraj[k]]
             tapes = {}
-            self._rows_stages(stages, kept + rv.y[len(kept):], range(len(kept)), rnd.heff, rnd.t, rnd.tfirst, tapes)
+            K = self._rows_stages(stages, kept + rv.y[len(kept):], range(len(kept)), rnd.heff, rnd.t, rnd.tfirst, tapes)
+            if tg is not None:
+                tg.K, tg.first, tg.tbar = K, True, {}
             if dn is not None:
                 # D_j[r] = sum_o h_r beta_j(theta_o) g[o, r] over the outputs row r interpolated in this round, G[r] = sum_o g[o, r]
                 ops.rows_dense_adjoint(B, d, [rv.D[j] for j in dn.cols], rv.G, g, dn.times, dn.P, rnd.range, rnd.log_d)
@@ -343,8 +357,10 @@ class RowSweep(object):
             for i in reversed(stages):
                 w = self._rows_cotangent(rv, i, dlam, rnd.heff)
                 if w is not None:
-                    dlam[i] = self._rows_vjp(tapes, i, w)
+                    dlam[i] = self._rows_vjp(tapes, i, w, tg)
             self._flush_param_accum()
+            if tg is not None:
+                self._rows_tg_round(tg, rnd, g, K)
             # lambda += sum_i dlam_i (+ G) (+ g at the output the previous round landed on), at most PN_MAX_STAGES terms a launch
             terms = [dlam[i] for i in stages if dlam[i] is not None]
             if dn is not None:
@@ -358,6 +374,7 @@ class RowSweep(object):
             if self._rY is not None:
                 self._rY[k] = None
         self._flush_param_accum()
+        self._rows_tg_end(tg)
 
     def _rows_cotangent(self, rv, i, dlam, heff):
         """Stage i's cotangent w_i[r] = h_r (b_i lambda[r] + sum_{j>i} a_ji dlam_j[r]) (+ D_i[r], what the row's interpolated
@@ -372,13 +389,61 @@ class RowSweep(object):
                                  [A[j][i] for j in js], heff, **kw)
         return rv.w
 
-    def _rows_vjp(self, tapes, i, w):
-        """The backward half of stage i with cotangent `w`: returns J^T w; the parameter cotangents are queued for mu."""
-        y, out, wrt = tapes[i]
+    def _rows_vjp(self, tapes, i, w, tg=None):
+        """The backward half of stage i with cotangent `w`: returns J^T w; the parameter cotangents are queued for mu.  With `tg`
+        (this backward computes dL/dt) the rows' <w, K_i> are taken first -- the cotangent buffer is rewritten for the next
+        stage -- and the rows' times are one more input of autograd.grad: their gradient is <w, df/dt> per row."""
+        y, out, wrt = tapes[i][:3]
+        tt = () if tg is None else (tapes[i][3],)
         tapes[i] = None
-        grads = torch.autograd.grad(out, (y,) + tuple(wrt), self._shaped(w).view(out.shape), allow_unused=True)
+        if tg is not None:
+            self._ops.rows_tgrad_dots(self._rB, self.n // self._rB, tg.rowacc, [w], [tg.K[i]], [1.0], accumulate=not tg.first)
+            tg.first = False
+        grads = torch.autograd.grad(out, (y,) + tuple(wrt) + tt, self._shaped(w).view(out.shape), allow_unused=True)
+        if tt:
+            gt, grads = grads[-1], grads[:-1]
+            if gt is not None:                       # (None: func's output does not reach t -- nothing is launched for it)
+                tg.tbar[i] = gt.to(torch.float64).contiguous().reshape(-1)
         gy, gp = self._vjp_results(grads[0], grads[1:], w)
         if gy is not None and gy.untyped_storage().data_ptr() == w.untyped_storage().data_ptr():
             gy = gy.clone()
         self._take_param_grads(1.0, gp)           # (the row's h is inside the cotangent; one launch per round)
         return gy
+
+    # ------------------------------------------------------------------ dL/dt (DESIGN.md section 5.7)
+    def _rows_tg_begin(self, T):
+        """The accumulators of a reverse sweep that returns dL/dt: dtrow [T][B] (row r's share of every dL/dt_i), the rows' sums of a
+        round, and per row the output interval it is in and the first-stage scalar held for its previous accepted step."""
+        ops, B, dn = self._ops, self._rB, self._rdense
+        tg = types.SimpleNamespace(dtrow=ops.f64(T, B), rowacc=ops.f64(B), held=ops.f64(B), iv=ops.i32(B), K=None, first=True, tbar={},
+                                   erow=ops.f64(T, B) if dn is not None else None)
+        tg.iv.fill_(T - 1)
+        return tg
+
+    def _rows_tg_round(self, tg, rnd, g, K):
+        """A reversed round's share of dL/dt, once its stage VJPs have run: the interpolated outputs' e_o, then the scatter into the
+        rows' columns of dtrow (pn_rows_dense_tgrad, pn_rows_tgrad_scatter)."""
+        ops, B, dn = self._ops, self._rB, self._rdense
+        if dn is not None:
+            ops.rows_dense_tgrad(B, self.n // B, tg.erow, g, [K[j] for j in dn.cols], dn.times, dn.P, rnd.range, rnd.log_d)
+        own = [j for j in sorted(tg.tbar) if not (self._fsal and j == 0)]
+        ops.rows_tgrad_scatter(B, tg.dtrow, tg.rowacc, [tg.tbar[j] for j in own], [self._c[j] for j in own],
+                               tg.tbar.get(0) if self._fsal else None, self._c[self._s - 1], self._fsal, rnd.log_d, rnd.hit,
+                               rnd.range if dn is not None else None, tg.erow, dn.times if dn is not None else None, tg.held, tg.iv)
+
+    def _rows_tg_end(self, tg):
+        """After the last reversed round: what the rows still hold goes to t[0], then the one ordered sum over the rows."""
+        if tg is None:
+            return
+        ops, B = self._ops, self._rB
+        ops.rows_tgrad_scatter(B, tg.dtrow, None, [], [], None, 0.0, self._fsal, None, None, None, None, None, tg.held, tg.iv, flush=True)
+        acc = ops.f64(tg.dtrow.shape[0])
+        ops.rows_tgrad_reduce(B, tg.dtrow, acc)
+        self.sample_time_grads = tg.dtrow
+        self._tg = dict(acc=acc, rows=True)         # (over batch shards `acc` is summed with mu: ODEPetsc._allreduce_adj_p)
+
+    def _tg_finish(self, t):
+        if self._tg is not None and self._tg.get("rows"):
+            tg, self._tg = self._tg, None
+            return tg["acc"].to(dtype=t.dtype, device=t.device).view_as(t)
+        return super(RowSweep, self)._tg_finish(t)

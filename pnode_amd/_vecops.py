@@ -295,6 +295,42 @@ class HipVecOps(object):
         check(self.lib.pn_rows_dense_adjoint(self.stream(), self.code, B, d, g.data_ptr(), g.stride(0), g.shape[0], times.data_ptr(),
                                              log_d.data_ptr(), rng.data_ptr(), len(Ds), P, self._ptrs(Ds), G.data_ptr()))
 
+    # ... and dL/dt of such a solve: row-wise reductions, the per-row scatter, one ordered sum over rows
+    rows_tgrad = True
+
+    def rows_tgrad_dots(self, B, d, rowacc, xs, ys, coefs, accumulate=True):
+        """rowacc[r] (+)= sum_p coefs[p] * <xs[p][r], ys[p][r]> in double (pn_rows_tgrad_dots)."""
+        np_ = len(xs)                                      # (two pointer tables in one call: _ptrs' one array serves the first)
+        check(self.lib.pn_rows_tgrad_dots(self.stream(), self.code, B, d, np_, self._ptrs(xs),
+                                          (ctypes.c_void_p * np_)(*[y.data_ptr() for y in ys]), self._dbl(coefs),
+                                          rowacc.data_ptr(), 1 if accumulate else 0))
+
+    def rows_dense_tgrad(self, B, d, erow, g, Ks, times, P, rng, log_d):
+        """erow[o][r] = sum_j beta'_j(theta_or) <g[o][r], Ks[j][r]> over the row's logged range (pn_rows_dense_tgrad)."""
+        check(self.lib.pn_rows_dense_tgrad(self.stream(), self.code, B, d, g.data_ptr(), g.stride(0), g.shape[0], times.data_ptr(),
+                                           log_d.data_ptr(), rng.data_ptr(), len(Ks), P, self._ptrs(Ks), erow.data_ptr()))
+
+    def _tgrad_scatter_args(self, B, dtrow, rowacc, tbars, coefs, tbar0, c_last, fsal, log_d, hit, rng, erow, times, held, iv, flush):
+        opt = lambda x: None if x is None else x.data_ptr()
+        return (B, dtrow.shape[0], dtrow.data_ptr(), opt(rowacc), len(tbars), self._ptrs(tbars) if tbars else None,
+                self._dbl(coefs) if tbars else None, opt(tbar0), c_last, 1 if fsal else 0, opt(log_d), opt(hit), opt(rng), opt(erow),
+                opt(times), held.data_ptr(), iv.data_ptr(), 1 if flush else 0)
+
+    def rows_tgrad_scatter(self, B, dtrow, rowacc, tbars, coefs, tbar0, c_last, fsal, log_d, hit, rng, erow, times, held, iv, flush=False):
+        """One reversed round (or, with `flush`, what the rows still hold after the last one) into every row's own column of the
+        fp64 matrix `dtrow` [T][B] (pn_rows_tgrad_scatter); `tbars`: fp64 vectors of B entries, <w_j, df/dt> per row."""
+        check(self.lib.pn_rows_tgrad_scatter(self.stream(), *self._tgrad_scatter_args(B, dtrow, rowacc, tbars, coefs, tbar0, c_last, fsal,
+                                                                                      log_d, hit, rng, erow, times, held, iv, flush)))
+
+    def rows_tgrad_reduce(self, B, dtrow, dt):
+        """dt[i] = sum_r dtrow[i][r] in a fixed order (pn_rows_tgrad_reduce)."""
+        T = dtrow.shape[0]
+        need = self.lib.pn_rows_tgrad_work_bytes(B, T)
+        w = getattr(self, "_rows_tg_work", None)
+        if w is None or w.numel() * 8 < need:             # arrival counters start at zero
+            w = self._rows_tg_work = torch.zeros(need // 8, dtype=torch.float64, device=self.device)
+        check(self.lib.pn_rows_tgrad_reduce(self.stream(), B, T, dtrow.data_ptr(), dt.data_ptr(), w.data_ptr()))
+
     def rows_adj_accum(self, B, d, lam_out, lam, dlams, g, ld, hit, nout):
         check(self.lib.pn_rows_adj_accum(self.stream(), self.code, B, d, lam_out.data_ptr(), lam.data_ptr(), len(dlams),
                                          self._ptrs(dlams), None if g is None else g.data_ptr(), ld,

@@ -259,7 +259,132 @@ PN_HD double pn_rows_dense_coef(const double *P, double to, double tn, double h)
   return h * v;
 }
 
+// theta = (to - tn) / h of an interpolated output, as pn_rows_dense_coef forms it, and beta'(theta) = sum_p (p+1) P[p] theta^p of
+// one stage (dL/dt of a per-sample solve): Horner from the highest power.  Contraction is off for the same
+// reason as above: the host stand-in and the device must round alike.
+PN_HD double pn_rows_dense_theta(double to, double tn, double h) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double d = to - tn;
+  return d / h;
+}
+
+PN_HD double pn_rows_dense_dcoef(const double *P, double th) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double v = 0.0;
+  for (int p = PN_ROWS_DENSE_POW - 1; p >= 0; --p) {
+    const double m = v * th;
+    v = m + (double)(p + 1) * P[p];
+  }
+  return v;
+}
+
+// ------------------------------------------------------------------------------------------
+// dL/dt of a per-sample solve: what one reversed round sends into row r's column of dtrow = doubles [nout][B] (pn_rows_tgrad_scatter
+// on the device, pn_rows_tgrad_scatter_host on host arrays).  The output interval [t[is], t[ie]] a round belongs to: one interval
+// [0, nout-1] with interpolated outputs (`dense`), else ie = the output the row last landed on in the reversed order (kept in iv[r])
+// and is = ie - 1 (none for a single output time, whose start 0 does not move).  P = dL/dH of the interval's last step goes to
+// dtrow[ie] and, negated, to dtrow[is]; Q = dL/dtau of every step to dtrow[is] (ODEPetsc._tg_finish's P_i - P_{i+1} + Q_{i+1}).
+//   own stages:        Q += tbar_j, P += c_j tbar_j
+//   first same as last: stage 0 was evaluated by the row's previous accepted step at tau + c_last H: its tbar_0 is HELD for the
+//                       round that reverses that step (held[r]); the held scalar of the step after this one arrives here
+//   interpolated o:     dtrow[o] += e_o, Q -= e_o, P -= theta_o e_o
+// A round with h_eff = 0 sends nothing.  `flush` (after the last reversed round): the scalar still held belongs to the row's
+// first step, evaluated at t[0] itself.
+// ------------------------------------------------------------------------------------------
+struct PnRowsTgScatter {
+  double *dtrow;
+  const double *rowacc;              // sum_j <w_j, K_j> of the round
+  const double *tbar[7];             // PN_MAX_STAGES
+  double c[7];
+  int nt;
+  const double *tbar0;               // null: stage 0 is an own stage (or func is autonomous)
+  double c_last;
+  int fsal;
+  const double *heff, *trow;
+  const int32_t *hit;
+  const int32_t *range;              // [2][B], with interpolated outputs
+  const double *erow;                // [nout][B]
+  const double *times;
+  double *held;
+  int32_t *iv;
+  int nout, dense, flush;
+};
+
+PN_HD void pn_rows_tgrad_scatter_row(const PnRowsTgScatter &a, int64_t B, int64_t r) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (a.flush) {
+    if (a.fsal && a.nout > 1) a.dtrow[r] += a.held[r];
+    a.held[r] = 0.0;
+    return;
+  }
+  const double h = a.heff[r];
+  if (!(h > 0.0)) return;
+  int hit = a.hit[r];
+  if (hit >= a.nout) hit = -1;
+  int ie, is;
+  bool last;
+  if (a.dense) {
+    ie = a.nout - 1;
+    is = 0;
+    last = hit == ie;
+  } else {
+    last = hit >= 0;
+    if (last) a.iv[r] = hit;
+    ie = a.iv[r];
+    is = ie - 1;
+  }
+  if (ie < 0 || ie >= a.nout) return;
+  double q = 0.0, p = 0.0;
+  // (a fixed trip count: indices into the argument block stay compile-time constants on the device)
+#if defined(__clang__)
+#pragma unroll
+#endif
+  for (int j = 0; j < 7; ++j) {
+    if (j < a.nt) {
+      const double tb = a.tbar[j][r];
+      q += tb;
+      p += a.c[j] * tb;
+    }
+  }
+  if (a.fsal) {
+    const double hd = a.held[r];
+    q += hd;
+    p += a.c_last * hd;
+    a.held[r] = a.tbar0 ? a.tbar0[r] : 0.0;
+  }
+  p += a.rowacc[r] / h;
+  if (a.dense && a.range) {
+    int lo = a.range[r], hi = a.range[B + r];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > a.nout ? a.nout : hi;
+    const double tr = a.trow[r];
+    for (int o = lo; o < hi; ++o) {
+      const double e = a.erow[(int64_t)o * B + r];
+      a.dtrow[(int64_t)o * B + r] += e;
+      q -= e;
+      p -= pn_rows_dense_theta(a.times[o], tr, h) * e;
+    }
+  }
+  if (is >= 0) a.dtrow[(int64_t)is * B + r] += q;
+  if (last) {
+    a.dtrow[(int64_t)ie * B + r] += p;
+    if (is >= 0) a.dtrow[(int64_t)is * B + r] -= p;
+  }
+}
+
 namespace pn {
 // the controller constants of `ts` and what the row controllers need of its tableau (pn_ts.cpp)
 void rows_ctl_config(const pn_ts *ts, int nspan, double max_time, PnRowsCtl *out);
+// the argument block of one pn_rows_tgrad_scatter (device and host entry points alike, pn_ts.cpp); a non-null return is the
+// refusal's text
+const char *rows_tgrad_scatter_args(int64_t B, int nout, double *dtrow, const double *rowacc, int nt, const double *const *tbar,
+                                    const double *coef, const double *tbar0, double c_last, int fsal, const double *log_d,
+                                    const int32_t *log_hit, const int32_t *range, const double *erow, const double *times, double *held,
+                                    int32_t *iv, int flush, PnRowsTgScatter *a);
 }  // namespace pn

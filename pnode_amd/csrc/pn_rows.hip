@@ -467,6 +467,191 @@ __global__ __launch_bounds__(kBlock) void pn_rows_control_kernel(PnRowsCtl rc, c
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// dL/dt of a per-sample solve: two row-wise reductions in the geometry above, the per-row scatter
+// of a reversed round into the row's column of dtrow (the shared text of pn_adapt.h) and the ordered sum over the rows.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+struct RowsTgDotArgs {
+  const T *x[PN_MAX_STAGES];
+  const T *y[PN_MAX_STAGES];
+  double c[PN_MAX_STAGES];
+  double *rowacc;
+  int accumulate;
+};
+
+template <typename T>
+struct RowsTgDenseArgs {
+  const T *g;                    // [nout][B*d] with row stride ld
+  int64_t ld;
+  int nout;
+  const T *k[PN_MAX_STAGES];
+  const double *times, *heff, *trow;
+  const int32_t *range;
+  double *erow;                  // [nout][B]
+  double P[PN_MAX_STAGES][PN_DENSE_MAX_POW];
+};
+
+// the sum of a row's group, valid in thread 0 of the group: shuffles inside a wave (width G), and for G > 64 the waves of
+// the group through LDS in wave order (pn_rows_combine_wrms_kernel's tree).  Every thread of the workgroup calls it.
+__device__ __forceinline__ double rows_group_sum(double sum, int lgG, double *lds) {
+  const int G = 1 << lgG;
+  if (G <= kWave) {
+    for (int o = G >> 1; o > 0; o >>= 1) sum += __shfl_down(sum, o, G);
+    return sum;
+  }
+  sum = wave_sum(sum);
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  if (lane == 0) lds[wid] = sum;
+  __syncthreads();
+  if ((threadIdx.x & (G - 1)) == 0) {
+    const int w0 = (threadIdx.x >> lgG) * (G / kWave);
+    sum = 0;
+    for (int w = 0; w < G / kWave; ++w) sum += lds[w0 + w];
+  }
+  __syncthreads();
+  return sum;
+}
+
+// rowacc[r] (+)= sum_p c_p <x_p[r], y_p[r]>: products and sums in double; per thread the chunks in ascending order, per chunk
+// the pairs in p order, per pair the elements in order; then the group's tree.
+template <typename T, int NP, bool VEC>
+__global__ __launch_bounds__(kBlock) void pn_rows_tgrad_dots_kernel(RowsTgDotArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  __shared__ double lds[kBlock / kWave];
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < q.B; r0 += (int64_t)gridDim.x * rpb) {
+    const int64_t r = r0 + sub;
+    const bool live = r < q.B;
+    double sum = 0;
+    if (live) {
+      const int64_t off = r * q.d;
+      for (int64_t ch = g; ch < q.nch; ch += G) {
+        T x[NP][VW], y[NP][VW];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          load_chunk<T, VEC>(a.x[p] + off, ch, q.d, x[p]);
+          load_chunk<T, VEC>(a.y[p] + off, ch, q.d, y[p]);
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          double dot = 0;
+#pragma unroll
+          for (int e = 0; e < VW; ++e) dot += (double)x[p][e] * (double)y[p][e];
+          sum += a.c[p] * dot;
+        }
+      }
+    }
+    sum = rows_group_sum(sum, q.lgG, lds);
+    if (live && g == 0) a.rowacc[r] = a.accumulate ? a.rowacc[r] + sum : sum;
+  }
+}
+
+// erow[o][r] = sum_j beta'_j(theta_{o,r}) <g[o][r], K_j[r]> for the outputs o of the row's logged range, kTgTile outputs at a
+// time: a thread that owns one chunk of the row loads its K_j once for all tiles; a thread that strides loads them once per
+// tile.  The tile count is the workgroup's largest (the tree of a group wider than a wave meets at barriers): rows with
+// fewer tiles ride along with nothing to add.  Entries outside a row's range are not written.
+constexpr int kTgTile = 8;
+
+template <typename T, int NK, bool VEC>
+__global__ __launch_bounds__(kBlock) void pn_rows_dense_tgrad_kernel(RowsTgDenseArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  __shared__ double lds[kBlock / kWave];
+  __shared__ int s_tiles;
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  const bool single = q.nch <= G;
+  for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < q.B; r0 += (int64_t)gridDim.x * rpb) {
+    const int64_t r = r0 + sub;
+    const bool live = r < q.B;
+    int lo = 0, hi = 0;
+    double h = 1, tr = 0;
+    if (live) {
+      lo = a.range[r];
+      hi = a.range[q.B + r];
+      lo = lo < 0 ? 0 : lo;
+      hi = hi > a.nout ? a.nout : hi;
+      h = a.heff[r];
+      tr = a.trow[r];
+      if (!(h > 0.0)) hi = lo;
+    }
+    if (threadIdx.x == 0) s_tiles = 0;
+    __syncthreads();
+    if (live && g == 0 && hi > lo) atomicMax(&s_tiles, (hi - lo + kTgTile - 1) / kTgTile);
+    __syncthreads();
+    const int tiles = s_tiles;
+    const int64_t off = r * q.d;
+    T k[NK][VW];
+    if (single && live && hi > lo && g < q.nch) {
+#pragma unroll
+      for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.k[j] + off, g, q.d, k[j]);
+    }
+    for (int t = 0; t < tiles; ++t) {
+      const int o0 = lo + t * kTgTile;
+      double s[kTgTile];
+#pragma unroll
+      for (int w = 0; w < kTgTile; ++w) s[w] = 0;
+      if (live && o0 < hi) {
+        for (int64_t ch = g; ch < q.nch; ch += G) {
+          if (!single) {
+#pragma unroll
+            for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.k[j] + off, ch, q.d, k[j]);
+          }
+#pragma unroll
+          for (int w = 0; w < kTgTile; ++w) {
+            if (o0 + w < hi) {
+              T f[VW];
+              load_chunk<T, VEC>(a.g + (int64_t)(o0 + w) * a.ld + off, ch, q.d, f);
+              const double th = pn_rows_dense_theta(a.times[o0 + w], tr, h);
+#pragma unroll
+              for (int j = 0; j < NK; ++j) {
+                double dot = 0;
+#pragma unroll
+                for (int e = 0; e < VW; ++e) dot += (double)f[e] * (double)k[j][e];
+                s[w] += pn_rows_dense_dcoef(a.P[j], th) * dot;
+              }
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int w = 0; w < kTgTile; ++w) {
+        const double v = rows_group_sum(s[w], q.lgG, lds);
+        if (live && g == 0 && o0 + w < hi) a.erow[(int64_t)(o0 + w) * q.B + r] = v;
+      }
+    }
+    __syncthreads();                      // s_tiles is rewritten by the next rows of this workgroup
+  }
+}
+
+// One thread per row sends the round into the row's own column of dtrow (pn_adapt.h): no atomics.
+__global__ __launch_bounds__(kBlock) void pn_rows_tgrad_scatter_kernel(PnRowsTgScatter a, int64_t B) {
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r < B) pn_rows_tgrad_scatter_row(a, B, r);
+}
+
+// dt[i] = sum_r dtrow[i][r]: workgroup (bx, i) adds the columns bx*256 + tid, + 256*gridDim.x, ... of row i (per thread in that
+// order, then the block tree) and publishes one partial; the last workgroup of the grid adds every row's partials in index
+// order (one wave per row, as pn_rk_dense_tgrad_kernel finishes).  gridDim.x depends on B alone: the same call, the same bits.
+constexpr int kTgReduceBlocks = 64;
+
+__global__ __launch_bounds__(kBlock) void pn_rows_tgrad_reduce_kernel(const double *dtrow, int64_t B, int nout, double *dt, double *work) {
+  double *partial = work + kTicketDoubles;
+  const int i = blockIdx.y;
+  double s = 0;
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < B; r += (int64_t)gridDim.x * kBlock) s += dtrow[(int64_t)i * B + r];
+  const double b = block_sum(s);
+  if (threadIdx.x == 0) publish_partial(partial + (int64_t)i * gridDim.x + blockIdx.x, b);
+  if (draw_ticket(work, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x)) {
+    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+    for (int o = wid; o < nout; o += kBlock / kWave) {
+      double t = 0;
+      for (int bx = lane; bx < (int)gridDim.x; bx += kWave) t += read_partial(partial + (int64_t)o * gridDim.x + bx);
+      t = wave_sum(t);
+      if (lane == 0) dt[o] = t;
+    }
+  }
+}
+
 template <typename T>
 RowsGeom geom(int64_t B, int64_t d) {
   constexpr int VW = 16 / sizeof(T);
@@ -632,6 +817,50 @@ int rows_dense_adjoint(hipStream_t st, int64_t B, int64_t d, const void *g, int6
   return pn::or_fail(rc, "pn_rows_dense_adjoint: nd out of range");
 }
 
+template <typename T>
+int rows_tgrad_dots(hipStream_t st, int64_t B, int64_t d, int np, const void *const *x, const void *const *y, const double *coef,
+                    double *rowacc, int accumulate) {
+  RowsTgDotArgs<T> a = {};
+  for (int p = 0; p < np; ++p) {
+    a.x[p] = (const T *)x[p];
+    a.y[p] = (const T *)y[p];
+    a.c[p] = coef[p];
+  }
+  a.rowacc = rowacc;
+  a.accumulate = accumulate ? 1 : 0;
+  const bool al = pn::aligned16(x, np) && pn::aligned16(y, np);
+  const int rc = rows_launch<T, 1, PN_MAX_STAGES>("pn_rows_tgrad_dots", st, B, d, al, np, a, [](auto N, auto V) {
+    return pn_rows_tgrad_dots_kernel<T, decltype(N)::value, decltype(V)::value>;
+  });
+  return pn::or_fail(rc, "pn_rows_tgrad_dots: np out of range");
+}
+
+template <typename T>
+int rows_dense_tgrad(hipStream_t st, int64_t B, int64_t d, const void *g, int64_t ld, int nout, const double *times,
+                     const double *log_d, const int32_t *range, int nk, const double *P, const void *const *K, double *erow) {
+  constexpr int VW = 16 / sizeof(T);
+  RowsTgDenseArgs<T> a = {};
+  a.g = (const T *)g;
+  a.ld = ld;
+  a.nout = nout;
+  a.times = times;
+  a.heff = log_d;
+  a.trow = log_d + B;
+  a.range = range;
+  a.erow = erow;
+  for (int j = 0; j < nk; ++j) {
+    a.k[j] = (const T *)K[j];
+    for (int p = 0; p < PN_DENSE_MAX_POW; ++p) a.P[j][p] = P[j * PN_DENSE_MAX_POW + p];
+  }
+  const bool al = pn::aligned16(g) && (ld % VW) == 0 && pn::aligned16(K, nk);
+  const int rc = rows_launch<T, 1, PN_MAX_STAGES>("pn_rows_dense_tgrad", st, B, d, al, nk, a, [](auto N, auto V) {
+    return pn_rows_dense_tgrad_kernel<T, decltype(N)::value, decltype(V)::value>;
+  });
+  return pn::or_fail(rc, "pn_rows_dense_tgrad: nk out of range");
+}
+
+int tgrad_reduce_blocks(int64_t B) { return (int)pn::blocks_for(B, kBlock, kTgReduceBlocks); }
+
 int bad_shape(const char *name, int64_t B, int64_t d) {
   if (B < 1 || d < 1 || B > ((int64_t)1 << 40) / d) return pn::fail(std::string(name) + ": B and d must be positive");
   return 0;
@@ -788,6 +1017,55 @@ int pn_rows_dense_plan_host(int64_t B, int nout, const double *times, const doub
       for (int j = 0; j < nk; ++j) coef[((int64_t)o * B + r) * nk + j] = pn_rows_dense_coef(P + j * PN_DENSE_MAX_POW, times[o], tr, h);
   }
   return 0;
+}
+
+int pn_rows_tgrad_dots(void *stream, int dtype, int64_t B, int64_t d, int np, const void *const *x, const void *const *y,
+                       const double *coef, double *rowacc, int accumulate) {
+  if (bad_shape("pn_rows_tgrad_dots", B, d)) return 1;
+  if (np < 1 || np > PN_MAX_STAGES || !x || !y || !coef || !rowacc) return pn::fail("pn_rows_tgrad_dots: null argument or np outside 1..7");
+  for (int p = 0; p < np; ++p)
+    if (!x[p] || !y[p]) return pn::fail("pn_rows_tgrad_dots: null vector");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_tgrad_dots<decltype(t)>(st, B, d, np, x, y, coef, rowacc, accumulate); });
+  return pn::or_fail(rc, "pn_rows_tgrad_dots: unknown dtype");
+}
+
+int pn_rows_dense_tgrad(void *stream, int dtype, int64_t B, int64_t d, const void *g, int64_t ld, int nout, const double *times_dev,
+                        const double *log_d, const int32_t *range, int nk, const double *P, const void *const *K, double *erow) {
+  if (bad_shape("pn_rows_dense_tgrad", B, d)) return 1;
+  if (!g || !times_dev || !log_d || !range || !P || !K || !erow || nk < 1 || nk > PN_MAX_STAGES)
+    return pn::fail("pn_rows_dense_tgrad: null argument or nk outside 1..7");
+  if (nout < 2 || ld < B * d) return pn::fail("pn_rows_dense_tgrad: fewer than two output times or a cotangent stride shorter than a state");
+  for (int j = 0; j < nk; ++j)
+    if (!K[j]) return pn::fail("pn_rows_dense_tgrad: null stage derivative");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    return rows_dense_tgrad<decltype(t)>(st, B, d, g, ld, nout, times_dev, log_d, range, nk, P, K, erow);
+  });
+  return pn::or_fail(rc, "pn_rows_dense_tgrad: unknown dtype");
+}
+
+int pn_rows_tgrad_scatter(void *stream, int64_t B, int nout, double *dtrow, const double *rowacc, int nt, const double *const *tbar,
+                          const double *coef, const double *tbar0, double c_last, int fsal, const double *log_d,
+                          const int32_t *log_hit, const int32_t *range, const double *erow, const double *times_dev, double *held,
+                          int32_t *iv, int flush) {
+  PnRowsTgScatter a;
+  const char *why = pn::rows_tgrad_scatter_args(B, nout, dtrow, rowacc, nt, tbar, coef, tbar0, c_last, fsal, log_d, log_hit, range, erow,
+                                       times_dev, held, iv, flush, &a);
+  if (why) return pn::fail(std::string("pn_rows_tgrad_scatter: ") + why);
+  return pn::launch("pn_rows_tgrad_scatter", pn_rows_tgrad_scatter_kernel, dim3((unsigned)pn::blocks_for(B, kBlock)), dim3(kBlock),
+                    (hipStream_t)stream, a, B);
+}
+
+int64_t pn_rows_tgrad_work_bytes(int64_t B, int nout) {
+  return (int64_t)sizeof(double) * (kTicketDoubles + (int64_t)(nout < 1 ? 1 : nout) * tgrad_reduce_blocks(B));
+}
+
+int pn_rows_tgrad_reduce(void *stream, int64_t B, int nout, const double *dtrow, double *dt, void *work) {
+  if (B < 1 || nout < 1 || nout > 65535 || !dtrow || !dt || !work)
+    return pn::fail("pn_rows_tgrad_reduce: null argument, B not positive or nout outside 1..65535");
+  return pn::launch("pn_rows_tgrad_reduce", pn_rows_tgrad_reduce_kernel, dim3((unsigned)tgrad_reduce_blocks(B), (unsigned)nout),
+                    dim3(kBlock), (hipStream_t)stream, dtrow, B, nout, dt, (double *)work);
 }
 
 }  // extern "C"

@@ -218,6 +218,41 @@ void rows_ctl_config(const pn_ts *ts, int nspan, double max_time, PnRowsCtl *out
   out->fsal = ts->tab.fsal;
   out->c_last = ts->tab.c[ts->tab.s - 1];
 }
+
+// the argument block of one scatter (device and host entry points alike); a non-zero return is the refusal's message
+const char *rows_tgrad_scatter_args(int64_t B, int nout, double *dtrow, const double *rowacc, int nt, const double *const *tbar,
+                                    const double *coef, const double *tbar0, double c_last, int fsal, const double *log_d,
+                                    const int32_t *log_hit, const int32_t *range, const double *erow, const double *times, double *held,
+                                    int32_t *iv, int flush, PnRowsTgScatter *a) {
+  if (B < 1 || B > 0x7fffff00 || nout < 1 || !dtrow || !held || !iv) return "null argument, or B or nout not positive";
+  if (!flush && (!rowacc || !log_d || !log_hit || nt < 0 || nt > PN_MAX_STAGES || (nt > 0 && (!tbar || !coef))))
+    return "null argument or nt outside 0..7";
+  if (!flush && range && (!erow || !times || nout < 2)) return "a range without the outputs' sums and times";
+  *a = PnRowsTgScatter();
+  a->dtrow = dtrow;
+  a->rowacc = rowacc;
+  a->nt = flush ? 0 : nt;
+  for (int j = 0; j < a->nt; ++j) {
+    if (!tbar[j]) return "null vector";
+    a->tbar[j] = tbar[j];
+    a->c[j] = coef[j];
+  }
+  a->tbar0 = tbar0;
+  a->c_last = c_last;
+  a->fsal = fsal ? 1 : 0;
+  a->heff = log_d;
+  a->trow = log_d ? log_d + B : nullptr;
+  a->hit = log_hit;
+  a->range = range;
+  a->erow = erow;
+  a->times = times;
+  a->held = held;
+  a->iv = iv;
+  a->nout = nout;
+  a->dense = range ? 1 : 0;
+  a->flush = flush ? 1 : 0;
+  return nullptr;
+}
 }  // namespace pn
 
 extern "C" {
@@ -424,6 +459,38 @@ int pn_rows_control_host(const pn_ts *ts, int64_t B, int nspan, const double *sp
 }
 
 int pn_rows_failure(int code, int64_t row) { return ctl_fail(code, row); }
+
+// theta and beta'_j(theta) of pn_rows_dense_tgrad on host arrays (no device; the CPU-only tests' stand-in and the native
+// self-test): the shared text of pn_adapt.h.
+int pn_rows_dense_tgrad_host(int64_t B, int nout, const double *times, const double *log_d, const int32_t *range, int nk,
+                             const double *P, double *theta, double *dcoef) {
+  if (B < 1 || nout < 2 || !times || !log_d || !range || !theta || nk < 0 || nk > PN_MAX_STAGES || (dcoef && (nk < 1 || !P)))
+    return pn::fail("pn_rows_dense_tgrad_host: null argument, fewer than two output times or nk outside 0..7");
+  for (int64_t r = 0; r < B; ++r) {
+    const double h = log_d[r], tr = log_d[B + r];
+    if (!(h > 0.0)) continue;
+    const int lo = range[r] < 0 ? 0 : range[r], hi = range[B + r] > nout ? nout : range[B + r];
+    for (int o = lo; o < hi; ++o) {
+      const double th = theta[(int64_t)o * B + r] = pn_rows_dense_theta(times[o], tr, h);
+      if (!dcoef) continue;
+      for (int j = 0; j < nk; ++j) dcoef[((int64_t)o * B + r) * nk + j] = pn_rows_dense_dcoef(P + j * PN_DENSE_MAX_POW, th);
+    }
+  }
+  return 0;
+}
+
+int pn_rows_tgrad_scatter_host(int64_t B, int nout, double *dtrow, const double *rowacc, int nt, const double *const *tbar,
+                               const double *coef, const double *tbar0, double c_last, int fsal, const double *log_d,
+                               const int32_t *log_hit, const int32_t *range, const double *erow, const double *times, double *held,
+                               int32_t *iv, int flush) {
+  PnRowsTgScatter a;
+  const char *why = pn::rows_tgrad_scatter_args(B, nout, dtrow, rowacc, nt, tbar, coef, tbar0, c_last, fsal, log_d, log_hit, range, erow,
+                                       times, held, iv, flush, &a);
+  if (why) return pn::fail(std::string("pn_rows_tgrad_scatter_host: ") + why);
+  for (int64_t r = 0; r < B; ++r) pn_rows_tgrad_scatter_row(a, B, r);
+  return 0;
+}
+
 
 int64_t pn_ts_count_fixed_steps(const pn_ts *ts) {
   if (pn_ts_is_adaptive(ts)) return -1;
