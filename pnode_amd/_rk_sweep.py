@@ -1,16 +1,31 @@
-"""The explicit Runge-Kutta sweeps behind ``ODEPetsc``: what PETSc's ``TSStep_RK`` / ``TSAdjointStep_RK`` / ``TSTrajectoryGet`` do
-between two callbacks into Python, as a mixin.  ``ODEPetsc`` itself (pnode_amd/petsc_adjoint.py)
-keeps the reference-shaped surface -- setupTS / odeint / petsc_adjointsolve / odeint_adjoint, pa.py:366-900 -- and calls in here
-where the reference calls ``ts.solve`` / ``ts.adjointSolve``."""
+"""The explicit Runge-Kutta sweeps behind ``ODEPetsc`` (pnode_amd/petsc_adjoint.py, the reference-shaped surface), as a mixin: what
+PETSc's ``TSSolve`` / ``TSStep_RK`` / ``TSAdjointStep_RK`` / ``TSTrajectoryGet`` do between two callbacks into Python (SURVEY 8a-3, a-6,
+a-8, a-9, a-10), forward beside reverse.  The callback shells and the step; the forward sweep (begin / accepted step / end; dense output,
+time span, trajectory and tape policy); the step advance both directions share; recomputation from checkpoints; the reverse sweep, dL/dt."""
 import contextlib
 import ctypes
 import warnings
 
 import torch
-import torch.nn as nn  # noqa: F401
 
 from . import _lib, options
 from ._lib import PnError, check  # noqa: F401
+
+
+def _mem_now(device):
+    """(bytes allocated, bytes reserved) by PyTorch's caching allocator on `device`.  torch.cuda.memory_allocated()
+    flattens the whole statistics dictionary in Python (~90 us per call, measured in the eager sweep's profile); the
+    nested dictionary underneath costs a tenth of that."""
+    try:
+        st = torch._C._cuda_memoryStats(device.index if device.index is not None else torch.cuda.current_device())
+        return st["allocated_bytes"]["all"]["current"], st["reserved_bytes"]["all"]["current"]
+    except Exception:
+        return torch.cuda.memory_allocated(device), torch.cuda.memory_reserved(device)
+
+
+class _RKState(object):
+    """The state of one forward sweep (RKSweep._rk_begin); slots: the step loop reads and writes it once per accepted step."""
+    __slots__ = "save T times full solution sol traj keep_tape tape_budget tape_steps tape_fsal K_fsal pingpong pp cur cur_slot ctl finished".split()
 
 
 class RKSweep(object):
@@ -207,6 +222,272 @@ class RKSweep(object):
             self._plans[h] = plan
         return plan
 
+    # ------------------------------------------------------------------ forward sweep (pa.py:777-869)
+    def _rk_odeint(self, u0, t, save):
+        """ts.solve (pa.py:829) for the explicit RK tableaus with one step-size controller for the whole batch."""
+        st = self._rk_begin(u0, t, save)
+        while not self._rk_accept_step(st):
+            pass
+        return self._rk_end(st)
+
+    def _rk_begin(self, u0, t, save):
+        """The state of a forward sweep: the span as the stepper sees it, the trajectory and the tape policy (_rk_trajectory), the
+        ping-pong pair for states no checkpoint holds, and the initial state in its home."""
+        lib, ops, ts = self._lib, self._ops, self._ts
+        self.sol_times = t.detach().cpu().to(dtype=torch.float64)
+        T, times = int(t.shape[0]), self.sol_times.tolist()
+        dt0 = float(self.step_size[0] if isinstance(self.step_size, list) else self.step_size)
+        st = _RKState()
+        st.save, st.T, st.times, st.full, st.K_fsal, st.tape_fsal, st.tape_steps = save, T, times, None, None, None, 0
+        st.solution = ops.empty((T,) + tuple(self.tensor_size))
+        st.sol = st.solution.view(T, -1)
+        # -pn_output_times interpolate: the stepper sees the end points only; t[1:-1] are filled by _dense_step
+        self._dense_active = self._dense and T > 2
+        if self._dense_active:
+            if any(not (b > a) for a, b in zip(times, times[1:])):
+                raise PnError("-pn_output_times interpolate: the output times must be strictly increasing")
+            st.full = (T, times, st.sol)
+            st.T, st.times, st.sol = 2, [times[0], times[-1]], st.sol[:: T - 1]      # rows 0 and T-1 of the solution
+            self._dense_next = 1
+        T, times = st.T, st.times
+        check(lib.pn_ts_begin(ts, 0.0, dt0, T, (ctypes.c_double * T)(*times)))
+        self._span_begin(T)
+        u0f = u0.detach().contiguous().reshape(-1)
+        self._rk_trajectory(st)
+        st.pingpong, st.pp = [self._buf("u_a"), self._buf("u_b")], 0
+        st.cur, st.cur_slot = self._state_home(st, 0)
+        ops.copy(st.cur[0], u0f)
+        if T > 1:
+            ops.copy(st.sol[0], u0f)
+        st.ctl = (ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(0))   # t_n, h, accepted, hit, done
+        st.finished = not (times[-1] > (0.0 if T == 1 else times[0]))
+        if self._monitor:
+            print("%d TS dt %g time %g" % (0, dt0, 0.0 if T == 1 else times[0]))
+        return st
+
+    def _rk_trajectory(self, st):
+        """Where the state at the start of every step will live (the solve was just begun, pn_ts_begin done), and whether
+        the stages' autograd tapes are kept for the reverse sweep."""
+        self._tmode = self._pick_traj_mode(self._s_eff) if st.save else self._traj_mode
+        st.traj = self._traj = None
+        if st.save:
+            vecs = self._s_eff if (self._tmode == _lib.PN_TRAJ_ALL or self._budget_stages) else 1
+            st.traj = self._traj = self._new_trajectory(vecs, self._tmode)
+            if self._tmode == _lib.PN_TRAJ_BUDGET and not self._adaptive and not isinstance(self.step_size, list):
+                total = self._lib.pn_ts_count_fixed_steps(self._ts)         # fixed step: the sweep length is known
+                if total > 0:
+                    check(self._lib.pn_traj_set_total(st.traj.handle, total))
+        # (per-evaluation graphs, pnode_amd/_stagegraphs.py: a captured evaluation's tape is overwritten by its next replay)
+        st.keep_tape = st.save and self._tmode == _lib.PN_TRAJ_ALL and self._retain_graph != 0 and self._sg is None
+        st.tape_budget = None
+        if st.keep_tape and self._retain_graph == 2:
+            st.tape_budget = self._tape_budget()
+            st.keep_tape = st.tape_budget is not None and st.tape_budget > 0
+        self._tapes = {} if st.keep_tape else None
+
+    def _state_home(self, st, step):
+        """(view, slot) of the state at the start of `step`: its trajectory slot's (vecs, npad), or a ping-pong buffer's (1, npad) and -1."""
+        traj = st.traj
+        if traj is not None:
+            slot = traj.fwd_slot(step)
+            if slot >= 0:
+                traj.stage_step.pop(slot, None)  # a recycled slot no longer holds the old step's stages
+                return traj.claim(slot), slot
+        st.pp ^= 1
+        return st.pingpong[st.pp].view(1, -1), -1
+
+    def _rk_advance(self, cur, cur_slot, nxt, tn, h, K0, want_err, tapes=None, t_first=None):
+        """One attempt of the step [tn, tn+h] from the state in the view `cur` (of trajectory slot `cur_slot`, -1: none) into the
+        view `nxt`, in either direction of the sweep: the stage values go behind the checkpoint `cur` lives in where the
+        trajectory keeps them, else into scratch.  Returns the stage derivatives K (see _rk_step)."""
+        kept = cur_slot >= 0 and (self._tmode == _lib.PN_TRAJ_ALL or self._budget_stages)
+        dest = (lambda i: cur[i]) if kept else (lambda i: self._buf("y_scratch"))
+        return self._rk_step(tn, h, cur[0], K0, nxt[0], dest, want_err, tapes, t_first)
+
+    def _rk_step_stands(self, k, cur_slot, K, state_sealed):
+        """Step k, advanced by _rk_advance from trajectory slot `cur_slot` (-1: none), stands (a rejected forward attempt must not seal):
+        the slot carries the step's stage values now, if budgeted checkpoints keep them, and is complete.  `state_sealed`: a re-advance
+        starts from complete checkpoints, the forward sweep seals once, here.  Returns K_0 of step k+1 for a first-same-as-last tableau."""
+        if cur_slot >= 0:
+            if self._budget_stages:
+                self._traj.stage_step[cur_slot] = k
+            if self._budget_stages or not state_sealed:
+                self._traj.seal(cur_slot)          # (a no-op on the HBM tier)
+        return K[self._s - 1] if self._fsal else None
+
+    def _rk_accept_step(self, st):
+        """One accepted step of the forward sweep: attempts until pn_ts_judge accepts one, then what follows an accepted step.
+        Returns whether the solve is finished."""
+        if st.finished:
+            return True                  # (an empty span: nothing to step over)
+        lib, ts, s, adaptive = self._lib, self._ts, self._s, self._adaptive
+        tt, hh, acc, hit, done = st.ctl
+        cur, cur_slot, keep_tape = st.cur, st.cur_slot, st.keep_tape
+        step = lib.pn_ts_steps(ts)
+        nxt, nxt_slot = self._state_home(st, step + 1)
+        K0, tape0 = st.K_fsal, st.tape_fsal
+        while True:
+            check(lib.pn_ts_attempt(ts, ctypes.byref(tt), ctypes.byref(hh)))
+            tn, h = tt.value, hh.value
+            tapes = [tape0] + [None] * (s - 1) if keep_tape else None
+            K = self._rk_advance(cur, cur_slot, nxt, tn, h, K0, adaptive, tapes)
+            if keep_tape:
+                tape0 = tapes[0]
+            enorm = self._global_enorm(self._ops.read_enorm()) if adaptive else -1.0
+            check(lib.pn_ts_judge(ts, enorm, ctypes.byref(acc), ctypes.byref(hit), ctypes.byref(done)))
+            if acc.value:
+                break
+            K0 = K[0]            # f(t_n, u_n) does not depend on h
+        if keep_tape:
+            self._rk_keep_tapes(st, step, tapes)
+        st.K_fsal = self._rk_step_stands(step, cur_slot, K, False)
+        st.cur, st.cur_slot = nxt, nxt_slot
+        tnew = lib.pn_ts_time(ts)
+        self._span_post_step(st.T, st.times, hit.value, done.value, step + 1, tnew, nxt[0], st.sol)
+        if st.full is not None:
+            self._dense_step(tn, h, tnew, cur[0], K, nxt[0], st.full[1], st.full[2])
+        if self._monitor:
+            print("%d TS dt %g time %g" % (step + 1, h, tnew))
+        st.finished = bool(done.value)
+        return st.finished
+
+    def _rk_keep_tapes(self, st, step, tapes):
+        """The accepted step's tapes go to the reverse sweep; in `auto` mode, as long as the budget measured at step 0 lasts."""
+        self._tapes[step] = tapes[: self._s_eff]
+        st.tape_fsal = tapes[self._s - 1] if self._fsal else None
+        if st.tape_budget is not None and st.tape_budget != float("inf"):
+            if step == 0:                 # one measurement: what a step's tapes (and its slot) take
+                per_step = max(_mem_now(self.device)[0] - self._tape_mem0, 1)
+                st.tape_steps = int(st.tape_budget // per_step) - 1
+            if step + 1 >= st.tape_steps:
+                st.keep_tape, st.tape_fsal = False, None       # later steps re-evaluate f in the reverse sweep
+                self._tape_all_fit = False
+
+    def _rk_end(self, st):
+        """The closing bookkeeping of a forward sweep: -ts_view, the T == 1 copy, the span and dense end checks; returns the solution."""
+        self._nsteps = self._lib.pn_ts_steps(self._ts)
+        if self._view:
+            self._ts_view()
+        if st.T == 1:
+            self._ops.copy(st.sol[0], st.cur[0])
+        else:
+            self._span_end(st.T)
+        if st.full is not None:
+            if self._dense_next != st.full[0] - 1:
+                raise Exception("TSSolve fails to step on all the specified points")
+            if st.save and self._fsal:
+                self._ops.copy(self._buf("dense_yN"), st.cur[0])       # where the last step's FSAL derivative was evaluated (reverse sweep)
+        return st.solution
+
+    # ------------------------------------------------------------------ dense output (-pn_output_times interpolate)
+    def _dense_coefs(self, to, tn, h):
+        """h*beta_j(theta) for every stage j, theta = (to - tn)/h, in double (rounded once to the storage type by the kernels)."""
+        th = (to - tn) / h
+        out = []
+        for row in self._dense_P:
+            v = 0.0
+            for p in reversed(row):
+                v = (v + p) * th
+            out.append(h * v)
+        return out
+
+    def _dense_step(self, tn, h, tnew, u, K, unew, times, sol):
+        """After the accepted step [tn, tnew] (stage derivatives K, start state u, end state unew): the output times inside it
+        from the continuous extension in ONE launch, an output time equal to tnew as a copy of the state."""
+        T = len(times)
+        lo = o = self._dense_next
+        while o < T - 1 and times[o] < tnew:
+            o += 1
+        if o > lo:
+            cols = self._dense_cols
+            coefs = []
+            for q in range(lo, o):
+                c = self._dense_coefs(times[q], tn, h)
+                coefs.append([c[j] for j in cols])
+            self._ops.dense_eval(sol[lo:o], u, [K[j] for j in cols], coefs)
+        if o < T - 1 and times[o] == tnew:
+            self._ops.copy(sol[o], unew)
+            o += 1
+        self._dense_next = o
+
+    # ------------------------------------------------------------------ time span (pa.py:518-532, 822-868)
+    def _span_begin(self, T):
+        self.cur_sol_steps = [0] * T      # steps taken from the previous output time to this one
+        self.cur_sol_index = 1
+        self._span_hits = 1               # output times whose solution has been kept (t[0] is u0)
+        self._span_delta = 1e-5 if self.tensor_dtype == torch.double else 1e-3
+
+    def _span_post_step(self, T, times, hit, done, stepno, tnew, cur, sol_flat):
+        """What happens after an accepted step of a multi-output solve.
+
+        * The output itself: the reference reads PETSc's ``getTimeSpanSolutions()`` (pa.py:845), i.e.
+          the state of exactly the step that landed on t[i].  Here: ``pn_ts_judge`` reports that step
+          (`hit` = i) and the state is copied out then.
+        * ``tspanPostStep`` (pa.py:518-532): a ``step_size`` list sets the next step; the steps of
+          each output interval are counted for the reverse sweep.  The reference advances its
+          interval counter when ``|t - t[i]| < 1e-5`` (fp64) / ``1e-3`` (fp32), which is one step
+          early whenever the step is shorter than that window: its backward pass then injects
+          dL/dy(t[i]) one step off and never reverses the sweep's first step.  The default here
+          counts with the exact hit (the discrete adjoint of what the forward sweep computed);
+          ``-pn_span_count reference`` counts as the reference does (identical whenever every step
+          is longer than the window)."""
+        if T <= 1:
+            return
+        if hit >= 0:
+            self._ops.copy(sol_flat[hit], cur)
+            self._span_hits += 1
+        if self.cur_sol_index < T:
+            if isinstance(self.step_size, list) and stepno < len(self.step_size) and not done:
+                check(self._lib.pn_ts_override_next_dt(self._ts, float(self.step_size[stepno])))
+            self.cur_sol_steps[self.cur_sol_index] += 1
+            if self._span_count_reference:
+                if abs(tnew - times[self.cur_sol_index]) < self._span_delta:
+                    self.cur_sol_index += 1
+            elif hit >= 0:
+                self.cur_sol_index = hit + 1
+
+    def _span_end(self, T):
+        if self.cur_sol_index != T or self._span_hits != T:
+            raise Exception("TSSolve fails to step on all the specified points")
+
+    def _pick_traj_mode(self, vecs_all):
+        """Trajectory mode of the solve that was just begun (pn_ts_begin done).  When
+        -ts_trajectory_solution_only is not given PETSc keeps the states only and recomputes a step's
+        stages when it is reversed.  Every mode replays the same arithmetic -- gradients are identical bit
+        for bit -- so on a 288 GB part the stage values are kept as well whenever the step count is known
+        (fixed step) and the whole trajectory fits in a quarter of the HBM that is free right now: the
+        reverse sweep then recomputes nothing.  Give the option (0 or 1) to decide yourself."""
+        mode = self._traj_mode
+        if (mode != _lib.PN_TRAJ_SOLUTION or not self._solution_only_auto or self.device.type != "cuda"
+                or isinstance(self.step_size, list)):
+            return mode
+        if torch.cuda.is_current_stream_capturing():        # no driver query while capturing: as the last eager solve
+            return getattr(self, "_tmode_auto", mode)
+        total = self._lib.pn_ts_count_fixed_steps(self._ts)
+        self._tmode_auto = mode
+        if total > 0:
+            esize = 4 if self.tensor_dtype == torch.float32 else 8
+            need = (total + 1) * vecs_all * self._npad * esize
+            free, _ = torch.cuda.mem_get_info(self.device)
+            allocated, reserved = _mem_now(self.device)
+            if need <= 0.25 * (free + max(reserved - allocated, 0)):
+                self._tmode_auto = _lib.PN_TRAJ_ALL
+        return self._tmode_auto
+
+    def _tape_budget(self):
+        """Bytes the retained tapes of this sweep may take in `auto` mode: half of the HBM that is free now
+        (driver-free + cached-but-unused blocks of PyTorch's allocator); None on the CPU test stand-in.
+        While a hipGraph is being captured no driver query is made: the sweep keeps what the eager
+        warm-up call before it kept."""
+        if self.device.type != "cuda":
+            return None
+        if torch.cuda.is_current_stream_capturing():
+            return float("inf") if getattr(self, "_tape_all_fit", False) else None
+        self._tape_mem0, reserved = _mem_now(self.device)
+        free, _ = torch.cuda.mem_get_info(self.device)
+        self._tape_all_fit = True
+        return 0.5 * (free + max(reserved - self._tape_mem0, 0))
+
     def _first_stage_time(self, k):
         """Time argument of f for the first stage of step k when it is RE-computed from a checkpoint.
         In the original sweep of a first-same-as-last tableau that derivative was the previous step's
@@ -225,51 +506,42 @@ class RKSweep(object):
     def _stages_of(self, step):
         """Stage values Y_0..Y_{s_eff-1} of `step` as flat tensors: read from the store-all
         trajectory, or recomputed from the nearest kept state (TSTrajectoryGet)."""
-        traj, ops = self._traj, self._ops
-        s_eff = self._s_eff
-        if self._tmode == _lib.PN_TRAJ_ALL:
-            fs, fl, _ = traj.rev_plan(step)
-            v = traj.view(fl)
-            return [v[i] for i in range(s_eff)]
+        traj = self._traj
         fs, fl, stores = traj.rev_plan(step)
-        keep = self._budget_stages
-        if keep and fs == step and traj.stage_step.get(fl) == step:
-            v = traj.view(fl)              # the checkpoint of this very step holds its stage values
-            return [v[i] for i in range(s_eff)]
-        slot_view = traj.view(fl)
-        cur, cur_slot = slot_view[0], fl
-        K_fsal = None
-        k = fs
-        pp = 0
-        while k < step:                   # re-advance k -> k+1, keeping what the plan asks for
+        if self._tmode == _lib.PN_TRAJ_ALL or (self._budget_stages and fs == step and traj.stage_step.get(fl) == step):
+            v = traj.view(fl)              # (budgeted checkpoints: the checkpoint of this very step holds its stage values)
+            return [v[i] for i in range(self._s_eff)]
+        return self._stage_values(step, *self._readvance(fs, fl, stores, step))
+
+    def _readvance(self, fs, fl, stores, step):
+        """Re-advance from the checkpoint of step `fs` in slot `fl` to the start of `step`, keeping what the plan asks for
+        (`stores`: step -> slot of a new checkpoint).  Returns (flat state at the start of `step`, its K_0 or None)."""
+        traj, keep = self._traj, self._budget_stages
+        cur, cur_slot = traj.view(fl), fl
+        K_fsal, pp = None, 0
+        for k in range(fs, step):
             tn, h = self._step_info(k)
-            if (k + 1) in stores:
-                nxt_slot = stores[k + 1]
-                nxt_view = traj.claim(nxt_slot)
-                nxt = nxt_view[0]
+            nxt_slot = stores.get(k + 1, -1)
+            if nxt_slot >= 0:
+                nxt = traj.claim(nxt_slot)
                 traj.stage_step.pop(nxt_slot, None)
             else:
                 pp ^= 1
-                nxt_slot, nxt_view = -1, None
-                nxt = self._buf("r_a" if pp else "r_b")
-            if keep and cur_slot >= 0:
-                dest = lambda i, c=slot_view: c[i]          # stage values of step k go behind its checkpoint
-            else:
-                dest = lambda i: self._buf("y_scratch")
-            K = self._rk_step(tn, h, cur, K_fsal, nxt, dest, False,
-                              t_first=self._first_stage_time(k) if K_fsal is None else None)
-            if keep and cur_slot >= 0:
-                traj.stage_step[cur_slot] = k
-                traj.seal(cur_slot)                  # (disk tier) the checkpoint now carries its stage values
+                nxt = self._buf("r_a" if pp else "r_b").view(1, -1)
+            K = self._rk_advance(cur, cur_slot, nxt, tn, h, K_fsal, False,
+                                 t_first=self._first_stage_time(k) if K_fsal is None else None)
+            K_fsal = self._rk_step_stands(k, cur_slot, K, True)
             if nxt_slot >= 0 and not keep:
                 traj.seal(nxt_slot)                  # (disk tier) a new state-only checkpoint is complete
-            K_fsal = K[self._s - 1] if self._fsal else None
-            cur, cur_slot, slot_view = nxt, nxt_slot, nxt_view
-            k += 1
-        # stage values of `step` itself (its own derivatives K_0..K_{s_eff-2} are needed)
+            cur, cur_slot = nxt, nxt_slot
+        return cur[0], K_fsal
+
+    def _stage_values(self, step, cur, K_fsal):
+        """Stage values of `step` itself from its start state `cur` (its own derivatives K_0..K_{s_eff-2} are needed)."""
+        ops, s_eff = self._ops, self._s_eff
         tn, h = self._step_info(step)
-        Y = [cur]
-        K = [K_fsal]
+        plan = self._stage_plan(h)
+        Y, K = [cur], [K_fsal]
         # The derivatives K_0..K_{s_eff-2} evaluated here are evaluations of f at exactly the points the stage VJPs of this
         # step differentiate f at: unless tapes are switched off (-pn_trajectory_retain_graph 0, -pn_reference_defaults) they
         # are recorded by autograd and the VJPs of those stages run their backward half only -- (s_eff - 1) evaluations of f
@@ -280,15 +552,12 @@ class RKSweep(object):
             if K[i - 1] is None:
                 t_eval = self._first_stage_time(step) if i == 1 else None
                 tt = tn + self._c[i - 1] * h if t_eval is None else t_eval
+                rec = [] if rt is not None else None
+                K[i - 1] = self._call_func(tt, Y[i - 1], rec, slot=i - 1)
                 if rt is not None:
-                    rec = []
-                    K[i - 1] = self._call_func(tt, Y[i - 1], rec, slot=i - 1)
                     rt[i - 1] = rec[0]
-                else:
-                    K[i - 1] = self._call_func(tt, Y[i - 1], slot=i - 1)
             y = self._buf("ys%d" % i)
-            idx = [j for j in range(i) if self._A[i][j] != 0.0]
-            ops.rk_stage(y, cur, [K[j] for j in idx], [h * self._A[i][j] for j in idx])
+            ops.rk_stage(y, cur, [K[j] for j in plan[i][0]], plan[i][1])
             Y.append(y)
             K.append(None)
         if self._ref_defaults:
@@ -300,8 +569,7 @@ class RKSweep(object):
             if self._fsal:
                 i = self._s - 1
                 y = self._buf("y_scratch")
-                idx = [j for j in range(i) if self._A[i][j] != 0.0]
-                ops.rk_stage(y, cur, [K[j] for j in idx], [h * self._A[i][j] for j in idx])
+                ops.rk_stage(y, cur, [K[j] for j in plan[i][0]], plan[i][1])
                 self._call_func(tn + self._c[i] * h, y)
         return Y
 
@@ -439,13 +707,12 @@ class RKSweep(object):
         None; added to w_i as the last term (a stage with a D_i is always formed, pn_rk_adjoint_step_dense)."""
         if self._theta is not None:
             return self._theta.adjoint_steps(nsteps, forcing)
-        ops, s_eff, A, b = self._ops, self._s_eff, self._A, self._b
-        lam = self.adj_u_flat
         if nsteps == 0 and forcing is not None:
-            ops.adj_accum(lam, lam, [], [], forcing)
+            self._ops.adj_accum(self.adj_u_flat, self.adj_u_flat, [], [], forcing)
         # two cotangent buffers in turn while the weight-sensitivity products of a stage run beside the next stage on a second
         # stream (pnode_amd/_lineargrad.py): the product of stage i reads stage i's cotangent while stage i-1's is written
         two_w = self._lin is not None and self._lin.side_on
+        reversed_step = self._adjoint_step_native if self._native else self._adjoint_step_python
         for r in range(nsteps):
             step = self._rev_next
             tn, H = self._step_info(step)
@@ -459,68 +726,71 @@ class RKSweep(object):
                 tapes = self._rtapes             # recorded while the stage values were recomputed (_stages_of)
             self._rtapes = None
             dlam = [None] * self._s          # raw VJP results
-            if self._native:
-                if getattr(self, "_vjp_cb_c", None) is None:
-                    self._make_callbacks()
-                self._rcbs = (Y, tapes, dlam, self._first_stage_time(step))
-                fo = forcing if r == nsteps - 1 else None
-                if dense_w is not None:
-                    dw = (ctypes.c_void_p * _lib.PN_MAX_STAGES)(*[None if d is None else d.data_ptr() for d in dense_w])
-                    rc = self._lib.pn_rk_adjoint_step_dense(ops.stream(), ops.code, self.n, self._ts, ops.vec_ops, tn, H,
-                                                            lam.data_ptr(), self._buf("w_a").data_ptr(),
-                                                            self._buf("w_b").data_ptr() if two_w else None, self._vjp_cb_c, None,
-                                                            dw, None if fo is None else fo.data_ptr())
-                else:
-                    rc = self._lib.pn_rk_adjoint_step(ops.stream(), ops.code, self.n, self._ts, ops.vec_ops, tn, H, lam.data_ptr(),
-                                                      self._buf("w_a").data_ptr(), self._buf("w_b").data_ptr() if two_w else None,
-                                                      self._vjp_cb_c, None,
-                                                      None if fo is None else fo.data_ptr())
-                self._rcbs = None
-                if rc:
-                    self._raise_from_loop(rc)
-                if self._pend_g and (self._accum_mode == "step" or self._sg is not None or len(self._pend_g) + s_eff > self._accum_cap):
-                    self._flush_param_accum()          # (per-evaluation graphs: the cotangents sit in static outputs)
-                elif self._pend_bias and self._accum_mode == "step":
-                    self._flush_bias_accum()
-                self._traj.rev_done(step)
-                self._rev_next = step - 1
-                continue
-            scale = [1.0] * self._s          # true dlam_i = scale[i] * dlam[i]
-            pend_g = self._pend_g            # parameter gradients waiting to be added to mu
-            nw = 0
-            for i in range(s_eff - 1, -1, -1):
-                js = [j for j in range(i + 1, s_eff) if A[j][i] != 0.0 and dlam[j] is not None]
-                di = dense_w[i] if dense_w is not None else None
-                if b[i] == 0.0 and not js and di is None:
-                    continue                   # structurally zero cotangent
-                if not js and di is None:
-                    w, scale[i] = lam, H * b[i]
-                else:
-                    w = self._buf("w_b" if (two_w and nw % 2) else "w_a")
-                    nw += 1
-                    ops.adj_theta(w, lam if b[i] != 0.0 else None, H * b[i],
-                                  [dlam[j] for j in js] + ([di] if di is not None else []),
-                                  [H * A[j][i] * scale[j] for j in js] + ([1.0] if di is not None else []))
-                # (stage 0 of a first-same-as-last tableau was evaluated at the previous step's last stage time, which is
-                # t_n only to the last bit: the VJP differentiates f THERE, with and without a tape -- the exact discrete
-                # adjoint, the same bits in every checkpoint mode for a time-dependent f; PETSc passes t_n)
-                t0 = self._first_stage_time(step) if i == 0 else None
-                gy, gp = self._vjp(tn + self._c[i] * H if t0 is None else t0, Y[i], w, tapes[i] if tapes else None, alpha=scale[i], last=(i == 0), slot=i)
-                if tapes:
-                    tapes[i] = None            # release the stage's activations as soon as they are used
-                if gy is not None and gy.data_ptr() == w.data_ptr():
-                    gy = gy.clone()            # f returned its cotangent unchanged (identity-like f)
-                dlam[i] = gy
-                self._take_param_grads(scale[i], gp, deferred=self._accum_mode != "stage")
-            if pend_g and (self._accum_mode == "step" or self._sg is not None or len(pend_g) + s_eff > self._accum_cap):
-                self._flush_param_accum()      # mu += sum_j scale_j * dmu_j, oldest first: one launch
-            elif self._pend_bias and self._accum_mode == "step":
-                self._flush_bias_accum()
-            idx = [i for i in range(s_eff) if dlam[i] is not None]
-            ops.adj_accum(lam, lam, [dlam[i] for i in idx], [scale[i] for i in idx],
-                          forcing if r == nsteps - 1 else None)
+            reversed_step(step, tn, H, Y, tapes, dlam, forcing if r == nsteps - 1 else None, dense_w, two_w)
             self._traj.rev_done(step)
             self._rev_next = step - 1
+
+    def _flush_after_step(self):
+        """What a reversed step's stage VJPs queued for mu, once they have all run: added now (oldest first, one launch) with
+        -pn_param_accum step, with per-evaluation graphs (the cotangents sit in static outputs) and when the queue is full."""
+        if self._pend_g and (self._accum_mode == "step" or self._sg is not None or len(self._pend_g) + self._s_eff > self._accum_cap):
+            self._flush_param_accum()
+        elif self._pend_bias and self._accum_mode == "step":
+            self._flush_bias_accum()
+
+    def _adjoint_step_native(self, step, tn, H, Y, tapes, dlam, forcing, dense_w, two_w):
+        """One reversed step by the C++ loop (pn_rk_adjoint_step; with `dense_w` pn_rk_adjoint_step_dense), which calls back for
+        the stage VJPs only."""
+        ops, lam = self._ops, self.adj_u_flat
+        if getattr(self, "_vjp_cb_c", None) is None:
+            self._make_callbacks()
+        self._rcbs = (Y, tapes, dlam, self._first_stage_time(step))
+        args = (ops.stream(), ops.code, self.n, self._ts, ops.vec_ops, tn, H, lam.data_ptr(), self._buf("w_a").data_ptr(),
+                self._buf("w_b").data_ptr() if two_w else None, self._vjp_cb_c, None)
+        fo = None if forcing is None else forcing.data_ptr()
+        if dense_w is not None:
+            dw = (ctypes.c_void_p * _lib.PN_MAX_STAGES)(*[None if d is None else d.data_ptr() for d in dense_w])
+            rc = self._lib.pn_rk_adjoint_step_dense(*(args + (dw, fo)))
+        else:
+            rc = self._lib.pn_rk_adjoint_step(*(args + (fo,)))
+        self._rcbs = None
+        if rc:
+            self._raise_from_loop(rc)
+        self._flush_after_step()
+
+    def _adjoint_step_python(self, step, tn, H, Y, tapes, dlam, forcing, dense_w, two_w):
+        """One reversed step with the stage loop in Python, one call per launch: the same launches, coefficients and bits."""
+        ops, s_eff, A, b = self._ops, self._s_eff, self._A, self._b
+        lam = self.adj_u_flat
+        scale = [1.0] * self._s          # true dlam_i = scale[i] * dlam[i]
+        nw = 0
+        for i in range(s_eff - 1, -1, -1):
+            js = [j for j in range(i + 1, s_eff) if A[j][i] != 0.0 and dlam[j] is not None]
+            di = dense_w[i] if dense_w is not None else None
+            if b[i] == 0.0 and not js and di is None:
+                continue                   # structurally zero cotangent
+            if not js and di is None:
+                w, scale[i] = lam, H * b[i]
+            else:
+                w = self._buf("w_b" if (two_w and nw % 2) else "w_a")
+                nw += 1
+                ops.adj_theta(w, lam if b[i] != 0.0 else None, H * b[i],
+                              [dlam[j] for j in js] + ([di] if di is not None else []),
+                              [H * A[j][i] * scale[j] for j in js] + ([1.0] if di is not None else []))
+            # (stage 0 of a first-same-as-last tableau was evaluated at the previous step's last stage time, which is
+            # t_n only to the last bit: the VJP differentiates f THERE, with and without a tape -- the exact discrete
+            # adjoint, the same bits in every checkpoint mode for a time-dependent f; PETSc passes t_n)
+            t0 = self._first_stage_time(step) if i == 0 else None
+            gy, gp = self._vjp(tn + self._c[i] * H if t0 is None else t0, Y[i], w, tapes[i] if tapes else None, alpha=scale[i], last=(i == 0), slot=i)
+            if tapes:
+                tapes[i] = None            # release the stage's activations as soon as they are used
+            if gy is not None and gy.data_ptr() == w.data_ptr():
+                gy = gy.clone()            # f returned its cotangent unchanged (identity-like f)
+            dlam[i] = gy
+            self._take_param_grads(scale[i], gp, deferred=self._accum_mode != "stage")
+        self._flush_after_step()           # (before lambda's update: the launches keep their order)
+        idx = [i for i in range(s_eff) if dlam[i] is not None]
+        ops.adj_accum(lam, lam, [dlam[i] for i in idx], [scale[i] for i in idx], forcing)
 
     def _take_param_grads(self, scale, gp, deferred=True):
         """mu += scale * gp, the parameter cotangents of one stage VJP: queued for the batched launch of _flush_param_accum, or
@@ -672,14 +942,7 @@ class RKSweep(object):
 
     def _reverse_sweep(self, g, T):
         """The body of OdeintAdjointMethod.backward (pa.py:924-944) on the (T, n) cotangent."""
-        with self._device_guard():
-            if self._trace:
-                torch.cuda.nvtx.range_push("pnode_amd.reverse_sweep")
-                try:
-                    return self._reverse_sweep_impl(g, T)
-                finally:
-                    torch.cuda.nvtx.range_pop()
-            return self._reverse_sweep_impl(g, T)
+        return self._traced("pnode_amd.reverse_sweep", self._reverse_sweep_impl, g, T)
 
     def _reverse_sweep_impl(self, g, T):
         self._tg = None

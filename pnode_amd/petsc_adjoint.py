@@ -1,18 +1,17 @@
-"""Drop-in for ``pnode.petsc_adjoint`` on the explicit-RK path, MI355X-native.
+"""Drop-in for ``pnode.petsc_adjoint`` on the explicit-RK path, MI355X-native: the surface.
 
-Same surface as the reference (``/root/reference/pnode/petsc_adjoint.py``, "pa.py"):
-``ODEPetsc.setupTS / odeint / odeint_adjoint`` and ``OdeintAdjointMethod`` with the same
-arguments, argument meaning and error behaviour -- but no PETSc/petsc4py underneath.  The
-PETSc TS / TSAdapt / TSAdjoint / TSTrajectory / Vec machinery the reference drives
-(pa.py:370, 637-656, 766-775, 812-829, 875-878) is replaced by ``libpnode_amd.so``
-(``include/pnode_amd.h``): hand-written gfx950 kernels for all state-vector arithmetic and a
-C++ host engine for the stepper state machine and the checkpoint schedule.  What stays in
-Python is what is Python in the reference too: the callback shells around the user's
-``nn.Module`` (pa.py:393-412 ``evalRHSFunction``, 52-82 ``RHSJacShell.multTranspose``,
-341-363 ``RHSJacPShell.multTranspose``) and the autograd entry (pa.py:903-947).
+Same surface as the reference (``/root/reference/pnode/petsc_adjoint.py``, "pa.py"): ``ODEPetsc.setupTS / odeint /
+odeint_adjoint`` and ``OdeintAdjointMethod`` with the same arguments, argument meaning and error behaviour -- but no
+PETSc/petsc4py underneath.  The PETSc TS / TSAdapt / TSAdjoint / TSTrajectory / Vec machinery the reference drives (pa.py:370,
+637-656, 766-775, 812-829, 875-878) is replaced by ``libpnode_amd.so`` (``include/pnode_amd.h``): hand-written gfx950 kernels
+for all state-vector arithmetic and a C++ host engine for the stepper state machine and the checkpoint schedule.  This file
+holds construction, ``setupTS`` and the options, process groups, the argument checks of ``odeint`` and its hand-off to a sweep
+(theta / IMEX, per-sample, batch), ``-ts_view``, ``petsc_adjointsolve`` and the autograd entry (pa.py:903-947).  The sweeps are
+mixins: the explicit-RK one, forward and reverse, with the callback shells around the user's ``nn.Module`` (pa.py:393-412,
+52-82, 341-363) in ``_rk_sweep.py``, the per-sample one in ``_rowsweep.py``, their hipGraph replay in ``_sweepgraphs.py``.
 
-The product path has no CPU fallback: states must live on a HIP device and the shared
-library must be present, otherwise an exception is raised.
+The product path has no CPU fallback: states must live on a HIP device and the shared library must be present, otherwise an
+exception is raised.
 """
 import contextlib
 import ctypes
@@ -25,7 +24,7 @@ import torch.nn as nn
 from . import _lib, options
 from ._lib import PnError, check  # noqa: F401
 from .misc import flat_parameters
-from ._rk_sweep import RKSweep
+from ._rk_sweep import RKSweep, _mem_now  # noqa: F401
 from ._rowsweep import RowSweep
 from ._sweepgraphs import SweepGraphs
 from ._trajectory import _DiskTrajectory, _Trajectory, _TwoLevelTrajectory  # noqa: F401
@@ -51,18 +50,6 @@ def _warn_unpinned(key, what):
                   "PETSc produced (no PETSc build and no PETSc-made log exists in the reference): the numbers claim PETSc's "
                   "semantics, not bit-parity with it.  See DESIGN.md section 3 (parity unpinned).  Said once per process."
                   % what, PnUnpinnedWarning, stacklevel=3)
-
-
-
-def _mem_now(device):
-    """(bytes allocated, bytes reserved) by PyTorch's caching allocator on `device`.  torch.cuda.memory_allocated()
-    flattens the whole statistics dictionary in Python (~90 us per call, measured in the eager sweep's profile); the
-    nested dictionary underneath costs a tenth of that."""
-    try:
-        st = torch._C._cuda_memoryStats(device.index if device.index is not None else torch.cuda.current_device())
-        return st["allocated_bytes"]["all"]["current"], st["reserved_bytes"]["all"]["current"]
-    except Exception:
-        return torch.cuda.memory_allocated(device), torch.cuda.memory_reserved(device)
 
 
 class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
@@ -520,9 +507,6 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
         return _Trajectory(self._lib, self._ops, self.n, vecs, mode, self._max_cps)
 
     # ------------------------------------------------------------------ helpers
-    def _flat(self, t):
-        return t.reshape(-1)
-
     def _buf(self, name):
         b = self._work.get(name)
         if b is None:
@@ -533,7 +517,6 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
     def _shaped(self, flat):
         return flat[: self.n].view(self.tensor_size)
 
-
     # ------------------------------------------------------------------ forward (pa.py:777-869)
     def odeint(self, u0, t):
         """Solve du/dt = func(t, u), u(t[0]) = u0; returns the states at the times `t`
@@ -541,35 +524,33 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
         self._tgrad = False
         return self._odeint(u0, t, self.enable_adjoint)
 
-    def _device_guard(self):
-        """The device entry points launch on the calling thread's current HIP device: make it the
-        solver's device for the duration of a sweep (a no-op context for the CPU test stand-in)."""
-        if self.device is not None and self.device.type == "cuda":
-            return self._sweep_context()
-        return contextlib.nullcontext()
-
     @contextlib.contextmanager
-    def _sweep_context(self):
+    def _device_guard(self):
+        """The device entry points launch on the calling thread's current HIP device: make it the solver's device for the
+        duration of a sweep, and pin the backend's launches to the stream that is current now (nothing to do for the CPU test
+        stand-in, nor for a backend without a pinned stream)."""
+        if self.device is None or self.device.type != "cuda":
+            yield
+            return
         with torch.cuda.device(self.device):
             ops = self._ops
-            prev = getattr(ops, "_pinned_stream", None)
-            if ops is not None and hasattr(ops, "_pinned_stream"):
-                ops._pinned_stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            if not hasattr(ops, "_pinned_stream"):
+                yield
+                return
+            prev, ops._pinned_stream = ops._pinned_stream, ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             try:
                 yield
             finally:
-                if ops is not None and hasattr(ops, "_pinned_stream"):
-                    ops._pinned_stream = prev
+                ops._pinned_stream = prev
+
+    def _traced(self, name, fn, *args):
+        """fn(*args) on the solver's device; under -pn_trace inside an nvtx range (a roctx range on ROCm, visible to
+        rocprofv3 --marker-trace)."""
+        with self._device_guard(), (torch.cuda.nvtx.range(name) if self._trace else contextlib.nullcontext()):
+            return fn(*args)
 
     def _odeint(self, u0, t, save):
-        with self._device_guard():
-            if not self._trace:
-                return self._odeint_impl(u0, t, save)
-            torch.cuda.nvtx.range_push("pnode_amd.forward_sweep")      # roctx range on ROCm
-            try:
-                return self._odeint_impl(u0, t, save)
-            finally:
-                torch.cuda.nvtx.range_pop()
+        return self._traced("pnode_amd.forward_sweep", self._odeint_impl, u0, t, save)
 
     def _odeint_impl(self, u0, t, save):
         if self._ops is None:
@@ -581,246 +562,7 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
             return self._theta.odeint(u0, t, save)
         if self._sample:
             return self._rows_odeint(u0, t, save)
-        lib, ops, ts = self._lib, self._ops, self._ts
-        self.sol_times = t.detach().cpu().to(dtype=torch.float64)
-        T = int(t.shape[0])
-        times = self.sol_times.tolist()
-        dt0 = float(self.step_size[0] if isinstance(self.step_size, list) else self.step_size)
-        # -pn_output_times interpolate: the stepper sees the end points only; t[1:-1] are filled by _dense_step
-        dense = self._dense_active = self._dense and T > 2
-        solution = ops.empty((T,) + tuple(self.tensor_size))
-        sol_flat = solution.view(T, -1)
-        if dense:
-            if any(not (b > a) for a, b in zip(times, times[1:])):
-                raise PnError("-pn_output_times interpolate: the output times must be strictly increasing")
-            full_T, full_times, full_sol = T, times, sol_flat
-            T, times, sol_flat = 2, [times[0], times[-1]], sol_flat[:: T - 1]      # rows 0 and T-1 of the solution
-            self._dense_next = 1
-        check(lib.pn_ts_begin(ts, 0.0, dt0, T, (ctypes.c_double * T)(*times)))
-        self._span_begin(T)
-        u0f = u0.detach().contiguous().reshape(-1)
-
-        # where the state at the start of step k lives
-        self._tmode = self._pick_traj_mode(self._s_eff) if save else self._traj_mode
-        if save:
-            vecs = self._s_eff if (self._tmode == _lib.PN_TRAJ_ALL or self._budget_stages) else 1
-            self._traj = self._new_trajectory(vecs, self._tmode)
-            traj = self._traj
-            if self._tmode == _lib.PN_TRAJ_BUDGET and not self._adaptive and not isinstance(self.step_size, list):
-                total = lib.pn_ts_count_fixed_steps(ts)         # fixed step: the sweep length is known
-                if total > 0:
-                    check(lib.pn_traj_set_total(traj.handle, total))
-        else:
-            traj = self._traj = None
-        store_stages = save and self._tmode == _lib.PN_TRAJ_ALL
-        # (per-evaluation graphs, pnode_amd/_stagegraphs.py: a captured evaluation's tape is overwritten by its next replay)
-        keep_tape = store_stages and self._retain_graph != 0 and self._sg is None
-        tape_budget = None
-        if keep_tape and self._retain_graph == 2:
-            tape_budget = self._tape_budget()
-            keep_tape = tape_budget is not None and tape_budget > 0
-        self._tapes = {} if keep_tape else None
-        tape_fsal = None
-        pingpong = [self._buf("u_a"), self._buf("u_b")]
-        pp = 0
-
-        cur_slot = -1                # trajectory slot `cur` lives in, -1 when it is a ping-pong buffer
-
-        def state_home(step):
-            nonlocal pp, home_slot
-            if traj is not None:
-                slot = traj.fwd_slot(step)
-                if slot >= 0:
-                    home_slot = slot
-                    traj.stage_step.pop(slot, None)  # a recycled slot no longer holds the old step's stages
-                    return traj.claim(slot)         # (vecs, npad)
-            home_slot = -1
-            pp ^= 1
-            return pingpong[pp].view(1, -1)
-
-        home_slot = -1
-        cur = state_home(0)
-        cur_slot = home_slot
-        ops.copy(cur[0], u0f)
-        if T > 1:
-            ops.copy(sol_flat[0], u0f)
-        K_fsal = None
-        tt, hh = ctypes.c_double(), ctypes.c_double()
-        acc, hit, done = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(0)
-        finished = not (times[-1] > (0.0 if T == 1 else times[0]))
-        if self._monitor:
-            print("%d TS dt %g time %g" % (0, dt0, 0.0 if T == 1 else times[0]))
-        while not finished:
-            step = lib.pn_ts_steps(ts)
-            nxt = state_home(step + 1)
-            nxt_slot = home_slot
-            K0 = K_fsal
-            tape0 = tape_fsal
-            while True:
-                check(lib.pn_ts_attempt(ts, ctypes.byref(tt), ctypes.byref(hh)))
-                tn, h = tt.value, hh.value
-                if store_stages or (self._budget_stages and cur_slot >= 0):
-                    dest = lambda i, c=cur: c[i]
-                else:
-                    dest = lambda i: self._buf("y_scratch")
-                tapes = [tape0] + [None] * (self._s - 1) if keep_tape else None
-                K = self._rk_step(tn, h, cur[0], K0, nxt[0], dest, self._adaptive, tapes)
-                if keep_tape:
-                    tape0 = tapes[0]
-                enorm = self._global_enorm(ops.read_enorm()) if self._adaptive else -1.0
-                check(lib.pn_ts_judge(ts, enorm, ctypes.byref(acc), ctypes.byref(hit), ctypes.byref(done)))
-                if acc.value:
-                    break
-                K0 = K[0]            # f(t_n, u_n) does not depend on h
-            K_fsal = K[self._s - 1] if self._fsal else None
-            if keep_tape:
-                self._tapes[step] = tapes[: self._s_eff]
-                tape_fsal = tapes[self._s - 1] if self._fsal else None
-                if tape_budget is not None and tape_budget != float("inf"):
-                    if step == 0:                 # one measurement: what a step's tapes (and its slot) take
-                        per_step = max(_mem_now(self.device)[0] - self._tape_mem0, 1)
-                        tape_steps = int(tape_budget // per_step) - 1
-                    if step + 1 >= tape_steps:
-                        keep_tape, tape_fsal = False, None       # later steps re-evaluate f in the reverse sweep
-                        self._tape_all_fit = False
-            if self._budget_stages and cur_slot >= 0 and save:
-                traj.stage_step[cur_slot] = step
-            if traj is not None and cur_slot >= 0:
-                traj.seal(cur_slot)          # the step's checkpoint is complete (a no-op on the HBM tier)
-            u_n = cur[0]
-            cur = nxt
-            cur_slot = nxt_slot
-            stepno = step + 1
-            tnew = lib.pn_ts_time(ts)
-            self._span_post_step(T, times, hit.value, done.value, stepno, tnew, cur[0], sol_flat)
-            if dense:
-                self._dense_step(tn, h, tnew, u_n, K, cur[0], full_times, full_sol)
-            if self._monitor:
-                print("%d TS dt %g time %g" % (stepno, h, tnew))
-            finished = bool(done.value)
-        self._nsteps = lib.pn_ts_steps(ts)
-        if self._view:
-            self._ts_view()
-        if T == 1:
-            ops.copy(sol_flat[0], cur[0])
-        else:
-            self._span_end(T)
-        if dense:
-            if self._dense_next != full_T - 1:
-                raise Exception("TSSolve fails to step on all the specified points")
-            if save and self._fsal:
-                ops.copy(self._buf("dense_yN"), cur[0])       # where the last step's FSAL derivative was evaluated (reverse sweep)
-        return solution
-
-    # ------------------------------------------------------------------ dense output (-pn_output_times interpolate)
-    def _dense_coefs(self, to, tn, h):
-        """h*beta_j(theta) for every stage j, theta = (to - tn)/h, in double (rounded once to the storage type by the kernels)."""
-        th = (to - tn) / h
-        out = []
-        for row in self._dense_P:
-            v = 0.0
-            for p in reversed(row):
-                v = (v + p) * th
-            out.append(h * v)
-        return out
-
-    def _dense_step(self, tn, h, tnew, u, K, unew, times, sol):
-        """After the accepted step [tn, tnew] (stage derivatives K, start state u, end state unew): the output times inside it
-        from the continuous extension in ONE launch, an output time equal to tnew as a copy of the state."""
-        T = len(times)
-        lo = o = self._dense_next
-        while o < T - 1 and times[o] < tnew:
-            o += 1
-        if o > lo:
-            cols = self._dense_cols
-            coefs = []
-            for q in range(lo, o):
-                c = self._dense_coefs(times[q], tn, h)
-                coefs.append([c[j] for j in cols])
-            self._ops.dense_eval(sol[lo:o], u, [K[j] for j in cols], coefs)
-        if o < T - 1 and times[o] == tnew:
-            self._ops.copy(sol[o], unew)
-            o += 1
-        self._dense_next = o
-
-    # ------------------------------------------------------------------ time span (pa.py:518-532, 822-868)
-    def _span_begin(self, T):
-        self.cur_sol_steps = [0] * T      # steps taken from the previous output time to this one
-        self.cur_sol_index = 1
-        self._span_hits = 1               # output times whose solution has been kept (t[0] is u0)
-        self._span_delta = 1e-5 if self.tensor_dtype == torch.double else 1e-3
-
-    def _span_post_step(self, T, times, hit, done, stepno, tnew, cur, sol_flat):
-        """What happens after an accepted step of a multi-output solve.
-
-        * The output itself: the reference reads PETSc's ``getTimeSpanSolutions()`` (pa.py:845), i.e.
-          the state of exactly the step that landed on t[i].  Here: ``pn_ts_judge`` reports that step
-          (`hit` = i) and the state is copied out then.
-        * ``tspanPostStep`` (pa.py:518-532): a ``step_size`` list sets the next step; the steps of
-          each output interval are counted for the reverse sweep.  The reference advances its
-          interval counter when ``|t - t[i]| < 1e-5`` (fp64) / ``1e-3`` (fp32), which is one step
-          early whenever the step is shorter than that window: its backward pass then injects
-          dL/dy(t[i]) one step off and never reverses the sweep's first step.  The default here
-          counts with the exact hit (the discrete adjoint of what the forward sweep computed);
-          ``-pn_span_count reference`` counts as the reference does (identical whenever every step
-          is longer than the window)."""
-        if T <= 1:
-            return
-        if hit >= 0:
-            self._ops.copy(sol_flat[hit], cur)
-            self._span_hits += 1
-        if self.cur_sol_index < T:
-            if isinstance(self.step_size, list) and stepno < len(self.step_size) and not done:
-                check(self._lib.pn_ts_override_next_dt(self._ts, float(self.step_size[stepno])))
-            self.cur_sol_steps[self.cur_sol_index] += 1
-            if self._span_count_reference:
-                if abs(tnew - times[self.cur_sol_index]) < self._span_delta:
-                    self.cur_sol_index += 1
-            elif hit >= 0:
-                self.cur_sol_index = hit + 1
-
-    def _span_end(self, T):
-        if self.cur_sol_index != T or self._span_hits != T:
-            raise Exception("TSSolve fails to step on all the specified points")
-
-    def _pick_traj_mode(self, vecs_all):
-        """Trajectory mode of the solve that was just begun (pn_ts_begin done).  When
-        -ts_trajectory_solution_only is not given PETSc keeps the states only and recomputes a step's
-        stages when it is reversed.  Every mode replays the same arithmetic -- gradients are identical bit
-        for bit -- so on a 288 GB part the stage values are kept as well whenever the step count is known
-        (fixed step) and the whole trajectory fits in a quarter of the HBM that is free right now: the
-        reverse sweep then recomputes nothing.  Give the option (0 or 1) to decide yourself."""
-        mode = self._traj_mode
-        if (mode != _lib.PN_TRAJ_SOLUTION or not self._solution_only_auto or self.device.type != "cuda"
-                or isinstance(self.step_size, list)):
-            return mode
-        if torch.cuda.is_current_stream_capturing():        # no driver query while capturing: as the last eager solve
-            return getattr(self, "_tmode_auto", mode)
-        total = self._lib.pn_ts_count_fixed_steps(self._ts)
-        self._tmode_auto = mode
-        if total > 0:
-            esize = 4 if self.tensor_dtype == torch.float32 else 8
-            need = (total + 1) * vecs_all * self._npad * esize
-            free, _ = torch.cuda.mem_get_info(self.device)
-            allocated, reserved = _mem_now(self.device)
-            if need <= 0.25 * (free + max(reserved - allocated, 0)):
-                self._tmode_auto = _lib.PN_TRAJ_ALL
-        return self._tmode_auto
-
-    def _tape_budget(self):
-        """Bytes the retained tapes of this sweep may take in `auto` mode: half of the HBM that is free now
-        (driver-free + cached-but-unused blocks of PyTorch's allocator); None on the CPU test stand-in.
-        While a hipGraph is being captured no driver query is made: the sweep keeps what the eager
-        warm-up call before it kept."""
-        if self.device.type != "cuda":
-            return None
-        if torch.cuda.is_current_stream_capturing():
-            return float("inf") if getattr(self, "_tape_all_fit", False) else None
-        self._tape_mem0, reserved = _mem_now(self.device)
-        free, _ = torch.cuda.mem_get_info(self.device)
-        self._tape_all_fit = True
-        return 0.5 * (free + max(reserved - self._tape_mem0, 0))
-
+        return self._rk_odeint(u0, t, save)
 
     def _ts_view(self):
         """-ts_view: the solver's settings and counters after a solve (PETSc prints its TS object there)."""
@@ -839,7 +581,6 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
         print("  total number of time steps=%d, rejected=%d;  trajectory: %s"
               % (self._nsteps, self._lib.pn_ts_rejections(self._ts), modes[self._tmode] if self._traj is not None else "not saved"))
 
-
     def petsc_adjointsolve(self, t, i=1):
         """Reverse one output interval (pa.py:871-890): all steps when `t` has one element,
         else the ``cur_sol_steps[i]`` steps that led to output time i."""
@@ -849,14 +590,10 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
         if self._dense and t.shape[0] > 1:
             raise PnError("petsc_adjointsolve by output interval is not available under -pn_output_times interpolate: the output "
                           "times no longer end steps (odeint_adjoint's backward covers all outputs)")
-        if t.shape[0] == 1:
-            self._adjoint_steps(self._nsteps, None)
-        else:
-            self._adjoint_steps(self.cur_sol_steps[i], None)
+        self._adjoint_steps(self._nsteps if t.shape[0] == 1 else self.cur_sol_steps[i], None)
         self._flush_param_accum()
         self._finish_linear_accum()
         return self._shaped(self.adj_u_flat), self.adj_p_tensor
-
 
     # ------------------------------------------------------------------ autograd entry (pa.py:892-900)
     def odeint_adjoint(self, y0, t):
