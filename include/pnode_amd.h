@@ -111,6 +111,23 @@ int64_t pn_wrms_partials(int64_t n);
 /* Blocks until everything enqueued on `stream` is done, then finishes the norm from the host side of the pinned block
  * pn_rk_combine_wrms wrote.  The one host<->device synchronisation of an adaptive step. */
 int pn_stream_wait_wrms(void *stream, const double *result_host, int64_t n, double *value);
+/* pn_rk_combine_wrms under -ts_adapt_wnormtype infinity: the same update, the same err, the same launch geometry, and
+ *   max_i |unew_i - uhat_i| / (atol + rtol*max(|unew_i|,|uhat_i|))   [TSErrorWeightedNorm, NORM_INFINITY]
+ * (uhat = unew + err rounded to the storage type; fp32 states form the ratio in fp32, fp64 ones in double; no square is
+ * taken).  A NaN term makes the norm NaN and an infinite one +inf: every level of the reduction carries NaN explicitly, since
+ * the hardware's max returns the operand that is not NaN.  Replaces TSEvaluateStep_RK(order-1) + TSErrorWeightedNorm with
+ * wnormtype NORM_INFINITY inside TSAdaptChoose_Basic (ts.setFromOptions, pa.py:775, reading -ts_adapt_wnormtype).  Same
+ * signature as pn_rk_combine_wrms, so that it can stand in pn_vec_ops.rk_combine_wrms; `work` as there (untouched);
+ * every workgroup stores the largest of its terms into the pinned block and pn_stream_wait_winf() takes the largest of
+ * those.  Profiled as PN_K_COMBINE_WRMS. */
+int pn_rk_combine_winf(void *stream, int dtype, int64_t n, void *unew, const void *u,
+                       int nk, const void *const *K, const double *coef_b, const double *coef_e,
+                       double atol, double rtol, void *work, double *result_dev);
+/* pn_stream_wait_wrms for the block pn_rk_combine_winf wrote: waits for `stream`, then pn_winf_finish. */
+int pn_stream_wait_winf(void *stream, const double *result_host, int64_t n, double *value);
+/* The host half alone (no device): the largest of the per-workgroup partials of `block` (block[0] = their number), NaN if
+ * any is NaN; 0.0 when every term was zero. */
+int pn_winf_finish(const double *block, int64_t n, double *value);
 /* A stream of the caller's own on the current device: priority > 0 the device's LOWEST priority (background work: the
  * weight-sensitivity products that run beside the reverse sweep's critical chain), < 0 the highest, 0 the default.  Not a
  * replacement of anything in the reference (PETSc's Vec operations run on one stream). */
@@ -267,8 +284,12 @@ int pn_ts_get_tableau_dense(const pn_ts *ts, int *order, int *npow, double P[PN_
 /* Options database subset, PETSc spellings without the leading dash: ts_adapt_type
  * (none|basic), ts_rk_type, ts_rtol, ts_atol, ts_max_steps, ts_max_reject,
  * ts_adapt_safety, ts_adapt_reject_safety, ts_adapt_clip (lo,hi), ts_adapt_dt_min,
- * ts_adapt_dt_max.  Unknown keys return non-zero and are left to the caller. */
+ * ts_adapt_dt_max, ts_adapt_wnormtype (2|infinity).  Unknown keys return non-zero and are left to the caller. */
 int pn_ts_set_option(pn_ts *ts, const char *key, const char *value);
+/* ts_adapt_wnormtype (2|infinity; TSAdapt's -ts_adapt_wnormtype, read by ts.setFromOptions, pa.py:775): which
+ * TSErrorWeightedNorm the callers hand to pn_ts_judge / pn_rows_control -- 2, the weighted RMS (default), or infinity, the
+ * largest term (pn_rk_combine_winf, pn_rows_combine_winf).  The controller itself does not change.  Returns 1 for infinity. */
+int pn_ts_wnorm_infinity(const pn_ts *ts);
 int pn_ts_is_adaptive(const pn_ts *ts);
 /* For steppers whose stage arithmetic lives above the ABI (TS types ARKIMEX / THETA, pa.py:651-656): tell the
  * controller the scheme's order (the exponent TSAdaptChoose_Basic uses) and whether it has an embedded
@@ -420,6 +441,12 @@ int pn_rows_stage(void *stream, int dtype, int64_t B, int64_t d, void *y, const 
  * err = sum (h[r]*coef_e[j]) K[j][r], enorm[r] = sqrt(sum_e (err/(atol + rtol*max(|unew|,|unew+err|)))^2 / d) -- B doubles
  * on the device, finished in the launch (one row is summed by one group of threads in a fixed order). */
 int pn_rows_combine_wrms(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk,
+                         const void *const *K, const double *coef_b, const double *coef_e, const double *h, double atol,
+                         double rtol, double *enorm);
+/* pn_rows_combine_wrms under -ts_adapt_wnormtype infinity (pn_rk_combine_winf per row): the same unew, the same err, the same
+ * group-per-row geometry, enorm[r] = max_e |unew - uhat| / (atol + rtol*max(|unew|,|uhat|)) over the row, NaN if any term of
+ * the row is (of that row only).  Stands for the row's TSErrorWeightedNorm with NORM_INFINITY (ts.solve, pa.py:829). */
+int pn_rows_combine_winf(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk,
                          const void *const *K, const double *coef_b, const double *coef_e, const double *h, double atol,
                          double rtol, double *enorm);
 /* One judgement per unfinished row with the controller constants of `ts` (TSAdaptChoose_Basic, MATCHSTEP, time span:

@@ -85,6 +85,7 @@ PROTOTYPES = {
     "pn_ts_get_tableau_dense": (_i, [_vp, _pi, _pi, _pd]),
     "pn_rows_stage": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _vp]),
     "pn_rows_combine_wrms": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _d, _d, _vp]),
+    "pn_rows_combine_winf": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _d, _d, _vp]),
     "pn_rows_work_bytes": (_i64, [_i64]),
     "pn_rows_control": (_i, [_vp, _vp, _i64, _i, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn_rows_control_host": (_i, [_vp, _i64, _i, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -112,6 +113,9 @@ PROTOTYPES = {
     "pn_wrms_work_bytes": (_i64, [_i64]),
     "pn_wrms_partials": (_i64, [_i64]),
     "pn_stream_wait_wrms": (_i, [_vp, _vp, _i64, _pd]),
+    "pn_rk_combine_winf": (_i, [_vp, _i, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _d, _d, _vp, _vp]),
+    "pn_stream_wait_winf": (_i, [_vp, _vp, _i64, _pd]),
+    "pn_winf_finish": (_i, [_vp, _i64, _pd]),
     "pn_pinned_scalar": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "pn_pinned_free": (_i, [_vp]),
     "pn_stream_create": (_i, [_i, ctypes.POINTER(_vp)]),
@@ -146,6 +150,7 @@ PROTOTYPES = {
     "pn_ts_set_rk_type": (_i, [_vp, _cp]),
     "pn_ts_get_tableau": (_i, [_vp, ctypes.POINTER(Tableau)]),
     "pn_ts_set_option": (_i, [_vp, _cp, _cp]),
+    "pn_ts_wnorm_infinity": (_i, [_vp]),
     "pn_ts_is_adaptive": (_i, [_vp]),
     "pn_ts_set_scheme": (_i, [_vp, _i, _i]),
     "pn_ts_get_tolerances": (_i, [_vp, _pd, _pd]),

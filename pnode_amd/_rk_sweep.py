@@ -121,8 +121,8 @@ class RKSweep(object):
                 K[i] = self._call_func(t_first if (i == 0 and t_first is not None) else t + self._c[i] * h, y, slot=i)
         if want_err:
             idx = [j for j in range(s) if self._e[j] != 0.0 or (not self._fsal and b[j] != 0.0)]
-            ops.combine_wrms(None if self._fsal else unew, unew if self._fsal else u, [K[j] for j in idx],
-                             [h * b[j] for j in idx], [h * self._e[j] for j in idx], self._atol, self._rtol)
+            self._err_combine(None if self._fsal else unew, unew if self._fsal else u, [K[j] for j in idx],
+                              [h * b[j] for j in idx], [h * self._e[j] for j in idx])
         elif not self._fsal:
             idx, coef = plan[s]
             ops.rk_stage(unew, u, [K[j] for j in idx], coef)
@@ -195,7 +195,7 @@ class RKSweep(object):
         K[0] = K0
         self._cbs = (tens, tapes, K)
         work, res = ops.wrms_buffers() if want_err else (None, None)
-        rc = self._lib.pn_rk_attempt(ops.stream(), ops.code, self.n, self._ts, ops.vec_ops, t, h, u.data_ptr(), unew.data_ptr(), ys,
+        rc = self._lib.pn_rk_attempt(ops.stream(), ops.code, self.n, self._ts, self._err_vec_ops(), t, h, u.data_ptr(), unew.data_ptr(), ys,
                                      None if K0 is None else K0.data_ptr(),
                                      1 if (K0 is None and t_first is not None) else 0, 0.0 if t_first is None else t_first,
                                      self._stage_cb_c, None, 1 if want_err else 0, work, res, self._kout)
@@ -333,7 +333,7 @@ class RKSweep(object):
             K = self._rk_advance(cur, cur_slot, nxt, tn, h, K0, adaptive, tapes)
             if keep_tape:
                 tape0 = tapes[0]
-            enorm = self._global_enorm(self._ops.read_enorm()) if adaptive else -1.0
+            enorm = self._global_enorm(self._err_read()) if adaptive else -1.0
             check(lib.pn_ts_judge(ts, enorm, ctypes.byref(acc), ctypes.byref(hit), ctypes.byref(done)))
             if acc.value:
                 break

@@ -280,8 +280,8 @@ class RowSweep(object):
         Y = [cur] + ([ops.empty(n) for _ in range(1, self._s_eff)] if st.store else st.scratch[1:self._s_eff])
         # (first same as last: the last stage value is the new state itself)
         K = self._rows_stages(range(self._s), Y + [unew] if fsal else Y, (), h, tr, sd[PN_ROWS_TFIRST])
-        ops.rows_combine_wrms(B, d, None if fsal else unew, unew if fsal else cur, [K[j] for j in st.ie],
-                              [b[j] for j in st.ie], [e[j] for j in st.ie], h, self._atol, self._rtol, st.enorm)
+        self._err_rows_combine(B, d, None if fsal else unew, unew if fsal else cur, [K[j] for j in st.ie],
+                               [b[j] for j in st.ie], [e[j] for j in st.ie], h, st.enorm)
         ops.rows_control(self._ts, B, st.nspan, st.span, st.tmax, st.enorm, sd, st.si, log.log_d, log.hit, st.accept, st.summary)
         if st.save:
             nxt = ops.empty(n)

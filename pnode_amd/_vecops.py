@@ -97,6 +97,32 @@ class HipVecOps(object):
         check(self.lib.pn_stream_wait_wrms(self.stream(), self._err_host, self.n, ctypes.byref(v)))
         return v.value
 
+    # ---- -ts_adapt_wnormtype infinity (pnode_amd/_errnorm.py decides which of the two norms a solve uses)
+    infinity_norm = True
+
+    def combine_winf(self, unew, u, Ks, cb, ce, atol, rtol):
+        """combine_wrms with the largest term in place of the weighted RMS (pn_rk_combine_winf); read by read_enorm_inf."""
+        self.wrms_buffers()
+        check(self.lib.pn_rk_combine_winf(self.stream(), self.code, self.n,
+                                          None if unew is None else unew.data_ptr(), u.data_ptr(),
+                                          len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce),
+                                          atol, rtol, self.work.data_ptr(), self._err_dev))
+
+    def read_enorm_inf(self):
+        v = ctypes.c_double()
+        check(self.lib.pn_stream_wait_winf(self.stream(), self._err_host, self.n, ctypes.byref(v)))
+        return v.value
+
+    @property
+    def vec_ops_inf(self):
+        """pn_vec_ops for the native step loop under the infinity norm: rk_combine_wrms is pn_rk_combine_winf (the same signature),
+        the other members stay NULL = this library's entry points."""
+        if getattr(self, "_vec_ops_inf", None) is None:
+            self._vec_ops_inf_struct = _lib.VecOps()
+            self._vec_ops_inf_struct.rk_combine_wrms = ctypes.cast(self.lib.pn_rk_combine_winf, _lib.RK_COMBINE_WRMS_FN)
+            self._vec_ops_inf = ctypes.cast(ctypes.pointer(self._vec_ops_inf_struct), ctypes.c_void_p)
+        return self._vec_ops_inf
+
     def adj_theta(self, w, lam, c_lam, dlams, coefs):
         check(self.lib.pn_adj_theta(self.stream(), self.code, self.n, w.data_ptr(),
                                     None if lam is None else lam.data_ptr(), c_lam,
@@ -248,6 +274,12 @@ class HipVecOps(object):
 
     def rows_combine_wrms(self, B, d, unew, u, Ks, cb, ce, h, atol, rtol, enorm):
         check(self.lib.pn_rows_combine_wrms(self.stream(), self.code, B, d, None if unew is None else unew.data_ptr(), u.data_ptr(),
+                                            len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce), h.data_ptr(), atol, rtol,
+                                            enorm.data_ptr()))
+
+    def rows_combine_winf(self, B, d, unew, u, Ks, cb, ce, h, atol, rtol, enorm):
+        """rows_combine_wrms with every row's largest term in `enorm` (pn_rows_combine_winf)."""
+        check(self.lib.pn_rows_combine_winf(self.stream(), self.code, B, d, None if unew is None else unew.data_ptr(), u.data_ptr(),
                                             len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce), h.data_ptr(), atol, rtol,
                                             enorm.data_ptr()))
 

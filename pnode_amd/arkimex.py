@@ -263,7 +263,7 @@ class ArkimexStepper(ThetaStepper):
             self._lincomb_many(E, xs, cs)
         else:
             ops.lincomb(E, [unew], [0.0])
-        ops.combine_wrms(None, unew, [E], [0.0], [1.0], o._atol, o._rtol)
+        o._err_combine(None, unew, [E], [0.0], [1.0])
         return True
 
     # ---------------------------------------------------------------- reverse sweep

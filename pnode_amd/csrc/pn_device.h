@@ -62,6 +62,48 @@ __device__ __forceinline__ double wrms_term<float>(float unew, float err, double
   return (double)q * (double)q;
 }
 
+// one term of TSErrorWeightedNorm's NORM_INFINITY variant (-ts_adapt_wnormtype infinity): |u - uhat| / tol between the two
+// STORED solutions, as wrms_term forms it, without the square -- so the fp32 form has no regime in which it overflows before
+// the ratio itself does.  Never negative: NaN where an operand is, +inf where the ratio is.
+template <typename T>
+__device__ __forceinline__ double winf_term(T unew, T err, double atol, double rtol) {
+  const double un = (double)unew;
+  const double uh = (double)(T)(unew + err);
+  const double tol = atol + rtol * fmax(fabs(un), fabs(uh));
+  return fabs((un - uh) / tol);
+}
+template <>
+__device__ __forceinline__ double winf_term<float>(float unew, float err, double atol, double rtol) {
+  const float uh = unew + err;
+  const float tol = (float)atol + (float)rtol * fmaxf(fabsf(unew), fabsf(uh));
+  return (double)fabsf((unew - uh) / tol);
+}
+
+// The larger of two norm terms, NaN if either is: fmax and v_max_f64 return the operand that is not NaN, so a plain max tree
+// would drop a NaN that the sum-of-squares tree carries to the end.  Every level of the max reductions goes through this.
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = nan_max(v, __shfl_down(v, off, kWave));
+  return v;
+}
+
+// block_sum's tree with nan_max in place of the addition (LDS words of its own)
+__device__ __forceinline__ double block_max(double v) {
+  __shared__ double lds[kBlock / kWave];
+  v = wave_max(v);
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  if (lane == 0) lds[wid] = v;
+  __syncthreads();
+  double s = 0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < kBlock / kWave; ++w) s = nan_max(s, lds[w]);
+  }
+  return s;   // valid in thread 0
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);

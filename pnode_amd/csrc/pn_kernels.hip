@@ -202,6 +202,76 @@ __global__ __launch_bounds__(kBlock) void pn_combine_wrms_kernel(const T *x0, Er
   }
 }
 
+// pn_combine_wrms_kernel under -ts_adapt_wnormtype infinity.  The thread's share first: that kernel's loads, update and err fma
+// chains, stores of unew and ragged tail (block 0), statement for statement, with the thread's LARGEST term (nan_max: NaN if any
+// is) where that kernel adds squares.  (A text of its own: routing both norms through one helper changed the default kernel's
+// instruction schedule, which this norm must leave alone.)
+template <typename T, int NK, int VW, int VPT, bool WRITE, int ST>
+__device__ __forceinline__ double winf_thread_max(const T *x0, const ErrArgs<T, NK> &a, T *unew_out, double atol, double rtol,
+                                                  int64_t nvec, int64_t n) {
+  // x0 / unew_out carry no __restrict__ (the caller may update a state in place); every thread loads all its
+  // elements before it stores any.  Loads are plain (the stage derivatives are recent), the new state is stored
+  // non-temporally (ST = 1: it is not read again before func has run), as in pn_lincomb_kernel.
+  using V = Vec<T, VW>;
+  const int64_t base = (int64_t)blockIdx.x * (kBlock * VPT) + threadIdx.x;
+  V ru[VPT], rk[VPT][NK];
+#pragma unroll
+  for (int p = 0; p < VPT; ++p) {
+    const int64_t i = base + (int64_t)p * kBlock;
+    if (i < nvec) {
+      ru[p] = reinterpret_cast<const V *>(x0)[i];
+#pragma unroll
+      for (int j = 0; j < NK; ++j) rk[p][j] = reinterpret_cast<const V *>(a.k[j])[i];
+    }
+  }
+  double acc = 0;
+#pragma unroll
+  for (int p = 0; p < VPT; ++p) {
+    const int64_t i = base + (int64_t)p * kBlock;
+    if (i < nvec) {
+      V o;
+#pragma unroll
+      for (int e = 0; e < VW; ++e) {
+        T un = ru[p][e], er = (T)0;
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+          if (WRITE) un = fma(a.cb[j], rk[p][j][e], un);
+          er = fma(a.ce[j], rk[p][j][e], er);
+        }
+        o[e] = un;
+        acc = nan_max(acc, winf_term<T>(un, er, atol, rtol));
+      }
+      if (WRITE) pn_store<ST>(reinterpret_cast<V *>(unew_out) + i, o);
+    }
+  }
+  if (VW > 1 && blockIdx.x == 0) {
+    const int64_t i = nvec * VW + threadIdx.x;
+    if (i < n) {
+      T un = x0[i], er = (T)0;
+#pragma unroll
+      for (int j = 0; j < NK; ++j) {
+        if (WRITE) un = fma(a.cb[j], a.k[j][i], un);
+        er = fma(a.ce[j], a.k[j][i], er);
+      }
+      if (WRITE) unew_out[i] = un;
+      acc = nan_max(acc, winf_term<T>(un, er, atol, rtol));
+    }
+  }
+  return acc;
+}
+
+// The block's partial is the largest of its threads' (nan_max again in the wave shuffles and through LDS), stored like the FIN == 0
+// form's; pn_stream_wait_winf takes the largest of the partials.
+template <typename T, int NK, int VW, int VPT, bool WRITE, int ST>
+__global__ __launch_bounds__(kBlock) void pn_combine_winf_kernel(const T *x0, ErrArgs<T, NK> a, T *unew_out, double atol,
+                                                                 double rtol, int64_t nvec, int64_t n, double *result) {
+  const double m = block_max(winf_thread_max<T, NK, VW, VPT, WRITE, ST>(x0, a, unew_out, atol, rtol, nvec, n));
+  if (threadIdx.x == 0) {
+    result[1 + blockIdx.x] = m;
+    if (blockIdx.x == 0) result[0] = (double)gridDim.x;
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // result[j] = <x, y_j>, j < NK: per-thread double partials -> wave shuffle -> LDS -> one double
 // per (block, j); a one-block kernel sums the block partials in index order.
@@ -735,7 +805,7 @@ inline int pick_vpt_wrms(int64_t nvec) {
   return nvec < (int64_t)256 * 256 * 8 ? 1 : 4;
 }
 
-template <typename T, int NK, bool WRITE>
+template <typename T, int NK, bool WRITE, bool INF>
 int launch_wrms_n(hipStream_t st, int64_t n, void *unew, const void *u, const void *const *K, const double *cb,
                   const double *ce, double atol, double rtol, double *work, double *result) {
   ErrArgs<T, NK> a;
@@ -752,6 +822,15 @@ int launch_wrms_n(hipStream_t st, int64_t n, void *unew, const void *u, const vo
     const int64_t nvec = n / VW;
     const int vpt = pick_vpt_wrms(nvec), stp = tune().st[PN_K_COMBINE_WRMS] != 0 ? 1 : 0;
     const int nblocks = (int)pn::blocks_for(nvec, (int64_t)kBlock * vpt);
+    if constexpr (INF) {                       // the same geometry and store policy; finished on the host (no in-launch form)
+#define PN_WGEO(V, S)                                                                                                 \
+  if (vpt == V && stp == S)                                                                                           \
+    return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_winf_kernel<T, NK, VW, V, WRITE, S>, dim3(nblocks), dim3(kBlock), st, \
+                      (const T *)u, a, (T *)unew, atol, rtol, nvec, n, result);
+      PN_WGEO(1, 0) PN_WGEO(1, 1) PN_WGEO(2, 0) PN_WGEO(2, 1) PN_WGEO(4, 0) PN_WGEO(4, 1)
+#undef PN_WGEO
+      return pn::fail("PN_TUNE: wvpt must be 1, 2 or 4");
+    }
     const int fin = tune().wfin != 0 ? 1 : 0;
 #define PN_WGEO(V, S, F)                                                                                              \
   if (vpt == V && stp == S && fin == F)                                                                               \
@@ -762,15 +841,18 @@ int launch_wrms_n(hipStream_t st, int64_t n, void *unew, const void *u, const vo
 #undef PN_WGEO
     return pn::fail("PN_TUNE: wvpt must be 1, 2 or 4 (wfin=1 needs the default store policy)");
   }
+  if constexpr (INF)
+    return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_winf_kernel<T, NK, 1, 1, WRITE, 0>, dim3((unsigned)pn::blocks_for(n, kBlock)),
+                      dim3(kBlock), st, (const T *)u, a, (T *)unew, atol, rtol, n, n, result);
   return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_wrms_kernel<T, NK, 1, 1, WRITE, 0, 0>, dim3((unsigned)pn::blocks_for(n, kBlock)),
                     dim3(kBlock), st, (const T *)u, a, (T *)unew, atol, rtol, work, n, n, inv_n, result);
 }
 
-template <typename T, bool WRITE>
+template <typename T, bool WRITE, bool INF = false>
 int launch_wrms(hipStream_t st, int64_t n, int nk, void *unew, const void *u, const void *const *K, const double *cb,
                 const double *ce, double atol, double rtol, double *partial, double *result) {
   const int rc = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
-    return launch_wrms_n<T, decltype(N)::value, WRITE>(st, n, unew, u, K, cb, ce, atol, rtol, partial, result);
+    return launch_wrms_n<T, decltype(N)::value, WRITE, INF>(st, n, unew, u, K, cb, ce, atol, rtol, partial, result);
   });
   return pn::or_fail(rc, "combine_wrms: between 1 and 7 stage derivatives supported");
 }
@@ -981,6 +1063,21 @@ int pn_rk_combine_wrms(void *stream, int dtype, int64_t n, void *unew, const voi
   return pn::or_fail(rc, kBadDtype);
 }
 
+int pn_rk_combine_winf(void *stream, int dtype, int64_t n, void *unew, const void *u, int nk, const void *const *K,
+                       const double *coef_b, const double *coef_e, double atol, double rtol, void *work,
+                       double *result_dev) {
+  if (n <= 0) return pn::fail("pn_rk_combine_winf: empty vector");
+  if (!work || !result_dev) return pn::fail("pn_rk_combine_winf: work/result buffers required");
+  hipStream_t st = (hipStream_t)stream;
+  double *w = (double *)work;
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return unew ? launch_wrms<T, true, true>(st, n, nk, unew, u, K, coef_b, coef_e, atol, rtol, w, result_dev)
+                : launch_wrms<T, false, true>(st, n, nk, nullptr, u, K, nullptr, coef_e, atol, rtol, w, result_dev);
+  });
+  return pn::or_fail(rc, kBadDtype);
+}
+
 int pn_pinned_scalar(double **host_ptr, double **dev_ptr) {
   void *h = nullptr, *d = nullptr;
   hipError_t err = hipHostMalloc(&h, 64, hipHostMallocMapped);
@@ -1031,7 +1128,8 @@ int pn_stream_destroy(void *stream) {
   return 0;
 }
 
-int64_t pn_wrms_partials(int64_t n) { return (n + kBlock - 1) / kBlock + 2; }
+static_assert(kBlock == pn::kWrmsBlock, "pn_internal.h and pn_device.h disagree on the workgroup of the error-norm kernels");
+int64_t pn_wrms_partials(int64_t n) { return pn::wrms_partials(n); }
 
 int pn_stream_wait_wrms(void *stream, const double *host_ptr, int64_t n, double *value) {
   hipError_t err;
@@ -1055,6 +1153,12 @@ int pn_stream_wait_wrms(void *stream, const double *host_ptr, int64_t n, double 
   for (int64_t i = 0; i < nb; ++i) s += p[1 + i];      // index order: bit-reproducible
   *value = std::sqrt(s * (1.0 / (double)n));           // the expression of the in-launch finish (PN_TUNE wfin=1): same bits
   return 0;
+}
+
+int pn_stream_wait_winf(void *stream, const double *host_ptr, int64_t n, double *value) {
+  const hipError_t err = hipStreamSynchronize((hipStream_t)stream);
+  if (err != hipSuccess) return pn::fail(std::string("pn_stream_wait_winf: ") + hipGetErrorString(err));
+  return pn_winf_finish(host_ptr, n, value);
 }
 
 int pn_stream_wait_scalar(void *stream, const double *host_ptr, double *value) {

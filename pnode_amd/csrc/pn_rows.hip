@@ -237,6 +237,65 @@ __global__ __launch_bounds__(kBlock) void pn_rows_combine_wrms_kernel(RowsErrArg
   }
 }
 
+// pn_rows_combine_wrms_kernel under -ts_adapt_wnormtype infinity: enorm[r] = the largest term of the row, NaN if any is.  That
+// kernel statement for statement -- the same rows per workgroup, chunks, update and err chains, stores and dead rows -- with
+// nan_max (pn_device.h) where it adds, at every level of the same tree (thread, shuffles of width G, the group's waves through LDS),
+// and no sqrt(. / d).  (A text of its own, so that the default kernel's code stays what it was.)
+template <typename T, int NK, bool VEC, bool WRITE>
+__global__ __launch_bounds__(kBlock) void pn_rows_combine_winf_kernel(RowsErrArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  __shared__ double lds[kBlock / kWave];
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < q.B; r0 += (int64_t)gridDim.x * rpb) {
+    const int64_t r = r0 + sub;
+    const bool live = r < q.B;
+    double sum = 0;
+    if (live) {
+      const double h = a.h[r];
+      T cb[NK], ce[NK];
+#pragma unroll
+      for (int j = 0; j < NK; ++j) {
+        cb[j] = (T)(h * a.cb[j]);
+        ce[j] = (T)(h * a.ce[j]);
+      }
+      const int64_t off = r * q.d;
+      for (int64_t ch = g; ch < q.nch; ch += G) {
+        T u[VW], k[NK][VW], o[VW];
+        load_chunk<T, VEC>(a.u + off, ch, q.d, u);
+#pragma unroll
+        for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.k[j] + off, ch, q.d, k[j]);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+          T un = u[e], er = (T)0;
+#pragma unroll
+          for (int j = 0; j < NK; ++j) {
+            if (WRITE) un = fma(cb[j], k[j][e], un);
+            er = fma(ce[j], k[j][e], er);
+          }
+          o[e] = un;
+          if (VEC || ch * VW + e < q.d) sum = nan_max(sum, winf_term<T>(un, er, a.atol, a.rtol));
+        }
+        if (WRITE) store_chunk<T, VEC>(a.unew + off, ch, q.d, o);
+      }
+    }
+    if (G <= kWave) {
+      for (int o = G >> 1; o > 0; o >>= 1) sum = nan_max(sum, __shfl_down(sum, o, G));
+    } else {
+      sum = wave_max(sum);
+      const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+      if (lane == 0) lds[wid] = sum;
+      __syncthreads();
+      if (g == 0) {
+        const int w0 = sub * (G / kWave);
+        sum = 0;
+        for (int w = 0; w < G / kWave; ++w) sum = nan_max(sum, lds[w0 + w]);
+      }
+      __syncthreads();
+    }
+    if (live && g == 0) a.enorm[r] = sum;
+  }
+}
+
 // unext[r] = accept[r] ? unew[r] : u[r];  sol[hit[r]][r] = unew[r] where hit[r] >= 0
 template <typename T, bool VEC>
 __global__ __launch_bounds__(kBlock) void pn_rows_commit_kernel(RowsCommitArgs<T> a, RowsGeom q) {
@@ -670,11 +729,12 @@ dim3 grid_for(const RowsGeom &q) { return dim3((unsigned)pn::blocks_for(q.B, kBl
 // a whole number of chunks, and for the N == n of [LO, HI] the kernel pick(N, V) names (V: std::true_type for the vector form)
 // on the capped grid.  pn::kNoCase when n is outside [LO, HI]: the caller's refusal.
 template <typename T, int LO, int HI, typename Args, typename Pick>
-int rows_launch(const char *name, hipStream_t st, int64_t B, int64_t d, bool aligned, int n, const Args &a, Pick pick) {
+int rows_launch(const char *name, hipStream_t st, int64_t B, int64_t d, bool aligned, int n, const Args &a, Pick pick, int kid = -1,
+                double bytes = 0.0) {
   const bool vec = aligned && d % (int64_t)(16 / sizeof(T)) == 0;
   const RowsGeom q = geom<T>(B, d);
-  return pn::with_count<LO, HI>(n, [&](auto N) {
-    return pn::launch(name, vec ? pick(N, std::true_type{}) : pick(N, std::false_type{}), grid_for(q), dim3(kBlock), st, a, q);
+  return pn::with_count<LO, HI>(n, [&](auto N) {     // kid >= 0: booked under that kernel id while profiling is on
+    return pn::launch_as(name, kid, bytes, vec ? pick(N, std::true_type{}) : pick(N, std::false_type{}), grid_for(q), dim3(kBlock), st, a, q);
   });
 }
 
@@ -702,7 +762,7 @@ int rows_lin(hipStream_t st, int64_t B, int64_t d, void *out, const void *base, 
   return rc;
 }
 
-template <typename T>
+template <typename T, bool INF = false>
 int rows_combine(hipStream_t st, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K, const double *cb,
                  const double *ce, const double *h, double atol, double rtol, double *enorm) {
   RowsErrArgs<T> a = {};
@@ -718,6 +778,16 @@ int rows_combine(hipStream_t st, int64_t B, int64_t d, void *unew, const void *u
     a.ce[j] = ce[j];
   }
   const bool al = pn::aligned16(u, unew) && pn::aligned16(K, nk);
+  if constexpr (INF) {
+    // booked with pn_rk_combine_winf's launches under the error-norm kernels' id: (nk + 1 (+ 1)) vectors of B * d entries
+    const double bytes = (double)B * (double)d * sizeof(T) * (nk + 1 + (unew ? 1 : 0));
+    const int rc = rows_launch<T, 1, PN_MAX_STAGES>("pn_rows_combine_winf", st, B, d, al, nk, a, [&](auto N, auto V) {
+      constexpr int NK = decltype(N)::value;
+      constexpr bool VEC = decltype(V)::value;
+      return unew ? pn_rows_combine_winf_kernel<T, NK, VEC, true> : pn_rows_combine_winf_kernel<T, NK, VEC, false>;
+    }, PN_K_COMBINE_WRMS, bytes);
+    return pn::or_fail(rc, "pn_rows_combine_winf: nk out of range");
+  }
   const int rc = rows_launch<T, 1, PN_MAX_STAGES>("pn_rows_combine_wrms", st, B, d, al, nk, a, [&](auto N, auto V) {
     constexpr int NK = decltype(N)::value;
     constexpr bool VEC = decltype(V)::value;
@@ -914,6 +984,18 @@ int pn_rows_combine_wrms(void *stream, int dtype, int64_t B, int64_t d, void *un
   hipStream_t st = (hipStream_t)stream;
   const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_combine<decltype(t)>(st, B, d, unew, u, nk, K, coef_b, coef_e, h, atol, rtol, enorm); });
   return pn::or_fail(rc, "pn_rows_combine_wrms: unknown dtype");
+}
+
+int pn_rows_combine_winf(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K,
+                         const double *coef_b, const double *coef_e, const double *h, double atol, double rtol, double *enorm) {
+  if (bad_shape("pn_rows_combine_winf", B, d)) return 1;
+  if (!u || !h || !enorm || nk < 1 || nk > PN_MAX_STAGES || !K || !coef_e || (unew && !coef_b))
+    return pn::fail("pn_rows_combine_winf: null argument or nk outside 1..7");
+  for (int j = 0; j < nk; ++j)
+    if (!K[j]) return pn::fail("pn_rows_combine_winf: null stage derivative");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_combine<decltype(t), true>(st, B, d, unew, u, nk, K, coef_b, coef_e, h, atol, rtol, enorm); });
+  return pn::or_fail(rc, "pn_rows_combine_winf: unknown dtype");
 }
 
 int64_t pn_rows_work_bytes(int64_t B) {

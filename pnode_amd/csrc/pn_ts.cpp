@@ -173,6 +173,7 @@ struct pn_ts {
   // controller (PETSc TSAdapt defaults)
   bool adapt_basic = true;
   double atol = 1e-4, rtol = 1e-4;
+  bool wnorm_infinity = false;          // -ts_adapt_wnormtype infinity: the callers' error norm is the largest term, not the WRMS
   double safety = 0.9, reject_safety = 0.5, clip_lo = 0.1, clip_hi = 10.0;
   double dt_min = 1e-20, dt_max = 1e50;
   double match_stretch = 0.01, match_halve = 2.0;   // matchstepfac
@@ -323,6 +324,13 @@ int pn_ts_set_option(pn_ts *ts, const char *key, const char *value) {
     else return pn::fail("ts_adapt_type: only 'none' and 'basic' are implemented");
     return 0;
   }
+  if (k == "ts_adapt_wnormtype") {
+    const std::string v = value ? value : "";
+    if (v == "2") ts->wnorm_infinity = false;
+    else if (v == "infinity") ts->wnorm_infinity = true;
+    else return pn::fail("ts_adapt_wnormtype: '" + v + "' is not implemented; the error norm is '2' (weighted RMS, the default) or 'infinity'");
+    return 0;
+  }
   if (k == "ts_rk_type") return pn_ts_set_rk_type(ts, value);
   if (k == "ts_type") {
     if (std::string(value ? value : "") != "rk") return pn::fail("ts_type: only 'rk' is implemented on this path");
@@ -344,6 +352,23 @@ int pn_ts_set_option(pn_ts *ts, const char *key, const char *value) {
   else if (k == "ts_adapt_dt_min") ts->dt_min = d;
   else if (k == "ts_adapt_dt_max") ts->dt_max = d;
   else return pn::fail("unknown option '" + k + "'");
+  return 0;
+}
+
+int pn_ts_wnorm_infinity(const pn_ts *ts) { return ts && ts->wnorm_infinity ? 1 : 0; }
+
+int pn_winf_finish(const double *block, int64_t n, double *value) {
+  if (!block || !value || n <= 0) return pn::fail("pn_winf_finish: null argument or empty vector");
+  const volatile double *p = (const volatile double *)block;
+  const int64_t nb = (int64_t)p[0];
+  // the block holds pn_wrms_partials(n) doubles: the count and at most that many minus one partials
+  if (nb <= 0 || nb + 1 > pn::wrms_partials(n)) return pn::fail("pn_winf_finish: corrupt block count");
+  double m = 0;
+  for (int64_t i = 0; i < nb; ++i) {
+    const double v = p[1 + i];
+    if (v > m || v != v) m = v;          // the kernels' nan_max: a NaN partial stays
+  }
+  *value = m;
   return 0;
 }
 

@@ -8,7 +8,7 @@ import sys
 
 from . import _lib
 
-_state = {"on": False, "solves": 0, "backward": 0, "steps": 0, "rejections": 0, "nfe_f": 0, "nfe_b": 0}
+_state = {"on": False, "solves": 0, "backward": 0, "steps": 0, "rejections": 0, "nfe_f": 0, "nfe_b": 0, "winf": False}
 
 
 def enable():
@@ -24,6 +24,7 @@ def note_forward(ode):
         _state["solves"] += 1
         _state["steps"] += int(ode.num_steps)
         _state["rejections"] += int(ode.num_rejections)
+        _state["winf"] = _state["winf"] or bool(getattr(ode, "_winf", False))
 
 
 def note_backward(ode):
@@ -46,6 +47,9 @@ def report(file=None):
             "pn_adj_theta": "VecMAXPY + VecScale (adjoint stage)", "pn_adj_accum": "closing VecMAXPY of TSAdjointStep",
             "pn_param_accum": "VecAXPY on the parameter sensitivities", "pn_copy": "VecCopy", "pn_dots": "VecMDot / VecNorm",
             "pn_lincomb": "VecMAXPY / VecWAXPY (implicit steppers)"}
+    if _state["winf"]:
+        # the infinity-norm kernels are booked under the error-norm id (the enum does not grow): name them in its row
+        what["pn_rk_combine_wrms"] = "TSEvaluateStep + TSErrorWeightedNorm (-ts_adapt_wnormtype infinity: pn_rk_combine_winf / pn_rows_combine_winf)"
     tot = 0.0
     for i, name in enumerate(_lib.KERNEL_IDS):
         if not L[i]:

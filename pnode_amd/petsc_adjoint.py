@@ -24,6 +24,7 @@ import torch.nn as nn
 from . import _lib, options
 from ._lib import PnError, check  # noqa: F401
 from .misc import flat_parameters
+from ._errnorm import ErrorNorm
 from ._rk_sweep import RKSweep, _mem_now  # noqa: F401
 from ._rowsweep import RowSweep
 from ._sweepgraphs import SweepGraphs
@@ -52,7 +53,7 @@ def _warn_unpinned(key, what):
                   % what, PnUnpinnedWarning, stacklevel=3)
 
 
-class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
+class ODEPetsc(RowSweep, RKSweep, SweepGraphs, ErrorNorm):
     """Explicit-RK neural-ODE solver with discrete adjoint (drop-in for pa.py:366-900).  How its sweeps are launched
     (eagerly, or replayed from hipGraphs) lives in the SweepGraphs mixin, pnode_amd/_sweepgraphs.py."""
 
@@ -141,7 +142,8 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
         contiguous batch shard with replicated parameters; the only data-path exchange is ONE
         all-reduce of the flat parameter-gradient buffer per backward.  ``average`` divides by
         the world size (loss = mean over the global batch).  With an adaptive method
-        ``global_error_norm`` additionally all-reduces one scalar (sum of squares) per step
+        ``global_error_norm`` additionally all-reduces one scalar (sum of squares; under
+        ``-ts_adapt_wnormtype infinity`` the maximum, _errnorm.py) per step
         attempt so that every rank takes the reference's step sequence, whose WRMS norm spans
         the whole flattened batch; turning it off gives per-shard controllers (not parity).
         The reference has no counterpart (it is single-process, pa.py:367 COMM_SELF)."""
@@ -159,16 +161,6 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
     def _world(self):
         import torch.distributed as dist
         return dist.get_world_size(self._pg) if self._sharded() else 1
-
-    def _global_enorm(self, enorm):
-        """sqrt(sum_r n_r*enorm_r^2 / sum_r n_r): the WRMS norm over the global batch."""
-        import torch.distributed as dist
-        if not self._sharded() or not self._pg_global_norm:
-            return enorm
-        v = torch.tensor([enorm * enorm * self.n, float(self.n)], dtype=torch.float64, device=self.device)
-        dist.all_reduce(v, op=dist.ReduceOp.SUM, group=self._pg)
-        s, n = v.tolist()
-        return (s / n) ** 0.5
 
     def _allreduce_adj_p(self, tgrad=False):
         """mu summed (and averaged) over the ranks; with `tgrad` (this backward computes dL/dt) the per-rank dL/dt accumulators too."""
@@ -468,7 +460,8 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
                 except PnError as exc:
                     raise PnError("PETSc option -%s %s is not implemented by pnode_amd (%s). Implemented: -ts_type, -ts_rk_type, "
                                   "-ts_adapt_type none|basic, -ts_rtol, -ts_atol, -ts_max_steps, -ts_max_reject, -ts_adapt_safety, "
-                                  "-ts_adapt_reject_safety, -ts_adapt_clip, -ts_adapt_dt_min, -ts_adapt_dt_max, -ts_arkimex_type, "
+                                  "-ts_adapt_reject_safety, -ts_adapt_clip, -ts_adapt_dt_min, -ts_adapt_dt_max, -ts_adapt_wnormtype 2|infinity, "
+                                  "-ts_arkimex_type, "
                                   "-ts_trajectory_*, -ts_monitor, -ts_view, -snes_*, -ksp_*, -log_view; an option that could change "
                                   "the numbers is refused rather than ignored" % (key, val, exc)) from None
         tab = _lib.Tableau()
@@ -486,6 +479,7 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
         a, r = ctypes.c_double(), ctypes.c_double()
         check(self._lib.pn_ts_get_tolerances(self._ts, ctypes.byref(a), ctypes.byref(r)))
         self._atol, self._rtol = a.value, r.value
+        self._errnorm_from_options()          # -ts_adapt_wnormtype: which norm, and whether the backend has it
         # budgeted checkpoints with -ts_trajectory_solution_only 0: a checkpoint holds the stage values
         # of its step as well (PETSc's checkpoints do), so reversing a checkpointed step recomputes nothing
         self._budget_stages = self._max_cps > 0 and not self._solution_only
@@ -572,7 +566,8 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs):
         check(self._lib.pn_ts_get_tableau(self._ts, ctypes.byref(tab)))
         print("TS Object (pnode_amd): type rk, order %d, %d stages%s%s"
               % (tab.order, tab.s, ", first same as last" if tab.fsal else "", ", embedded error estimate" if tab.has_embed else ""))
-        print("  adapt: %s%s" % ("basic, atol %g rtol %g" % (self._atol, self._rtol) if self._adaptive else "none (fixed steps)",
+        print("  adapt: %s%s" % ("basic, atol %g rtol %g, error norm %s" % (self._atol, self._rtol, self._wnorm_name()) if self._adaptive
+                                 else "none (fixed steps)",
                                  "; final time matched exactly (MATCHSTEP)"))
         print("  state: %s %s on %s;  trainable parameters: %d" % (tuple(self.tensor_size), str(self.tensor_dtype).replace("torch.", ""), self.device, self.np))
         print("  launches: %s;  step loop: %s" % (self._graph_status, "C++ (pn_rk_attempt / pn_rk_adjoint_step)" if self._native else "Python"))

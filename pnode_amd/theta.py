@@ -1024,7 +1024,7 @@ class ThetaStepper(object):
         a = 1.0 + h_prev / h
         E = self._buf("E")
         ops.lincomb(E, [unew, u, xprev], [1.0 / a, -1.0 / (a - 1.0), 1.0 / (a * (a - 1.0))])
-        ops.combine_wrms(None, unew, [E], [0.0], [1.0], o._atol, o._rtol)
+        o._err_combine(None, unew, [E], [0.0], [1.0])
         return True
 
     def error_accept(self, h, u):
@@ -1124,7 +1124,7 @@ class ThetaStepper(object):
                 self._do_step(tn, h, cur[0], nxt[0], dest)
                 enorm = -1.0
                 if adaptive and self.error_norm(h, cur[0], nxt[0]):
-                    enorm = o._global_enorm(ops.read_enorm())
+                    enorm = o._global_enorm(o._err_read())
                 check(lib.pn_ts_judge(ts, enorm, ctypes.byref(acc), ctypes.byref(hit), ctypes.byref(done)))
                 if acc.value:
                     break
