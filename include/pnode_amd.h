@@ -226,6 +226,21 @@ int pn_linear_wgrad(void *stream, int dtype, int64_t rows, int64_t out_f, int64_
 int pn_linear_wgrad_group(void *stream, int dtype, int64_t rows, int npairs, const pn_wgrad_pair *pairs, int flags);
 int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f, void *pw, void *pb, void *mu_w, void *mu_b);
 
+/* The forward of a Linear layer with its activation in one launch (csrc/pn_linear.hip):  y = act(x w^T + b)  for x rows x in_f, w out_f x
+ * in_f, b out_f values or NULL, y rows x out_f, all row-major fp32; act = PN_ACT_IDENTITY or PN_ACT_TANH (tanhf of the device library,
+ * applied in fp32 to the biased sum: exactly +-1 once it saturates, NaN for NaN).  The product is the split-bf16 one of pn_linear_wgrad
+ * (three exact bf16 terms per operand, the six largest cross products, fp32 accumulation on v_mfma_f32_32x32x16_bf16; an infinite
+ * operand gives NaN); one workgroup owns a 64 x 128 tile of y over all of in_f and writes it once: no atomics, no work buffers, the
+ * same bits on every launch.  x, w, y 16-byte aligned, y != x.  Replaces, inside the solver's own evaluations of func (the body of
+ * evalRHSFunction, pa.py:393-412), the library GEMM and the elementwise kernel of an nn.Linear -> nn.Tanh pair.
+ * pn_linear_fwd_supported: fp32, rows >= 256 (any number), out_f % 64 == 0, in_f % 64 == 0; everything else is the caller's to run
+ * through the library. */
+#define PN_ACT_IDENTITY 0
+#define PN_ACT_TANH 1
+int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
+int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
+                  void *y);
+
 /* result_dev[j] = <x, y_j> for j < nk <= PN_MAX_TERMS, accumulated in double, reduced in a fixed
  * order (bit-reproducible).  ||x||^2 is the case y_0 == x.  Replaces VecMDot / VecNorm inside
  * the KSP(GMRES) and SNES that PETSc's implicit steppers run (TS type BE/CN, pa.py:651-654;

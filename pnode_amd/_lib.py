@@ -45,6 +45,7 @@ class WgradPair(ctypes.Structure):
 PN_WGRAD_MAX_PAIRS = 8
 PN_WGRAD_EXACT_FP32 = 1
 PN_WGRAD_TILE_64 = 2
+PN_ACT_IDENTITY, PN_ACT_TANH = 0, 1
 PN_ABI_VERSION = 4
 PN_DENSE_MAX_POW = 4          # columns of a continuous extension's P matrix (pn_tableau_dense)
 PN_DENSE_CHUNK = 32           # output rows per launch of pn_rk_dense_eval / pn_rk_dense_adjoint
@@ -135,6 +136,8 @@ PROTOTYPES = {
     "pn_linear_wgrad": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _d, _vp, _vp]),
     "pn_linear_wgrad_group": (_i, [_vp, _i, _i64, _i, ctypes.POINTER(WgradPair), _i]),
     "pn_linear_wgrad_finish": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "pn_linear_fwd_supported": (_i, [_i, _i64, _i64, _i64]),
+    "pn_linear_fwd": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp]),
     "pn_colsum_accum": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _d, _vp]),
     "pn_colsum_accum_multi": (_i, [_vp, _i, _i, _pi64, _pi64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _pd, _vp]),
     "pn_colsum_work_bytes": (_i64, [_i, _pi64, _pi64]),

@@ -1,0 +1,287 @@
+"""func's ``nn.Linear -> nn.Tanh`` pairs as ONE launch in the solver's own evaluations of func (``pn_linear_fwd``, csrc/pn_linear.hip).
+
+The body of ``evalRHSFunction`` (pa.py:393-412) at BASELINE's target configuration is four library GEMMs and three elementwise
+``tanh`` launches; each ``tanh`` moves 16 MiB in about 6 us, twice what its traffic needs -- mostly dispatch floor.  A pair is
+therefore run as one MFMA kernel with the bias and ``tanhf`` in its epilogue, where ALL of this holds:
+
+* the pair is two consecutive children of an ``nn.Sequential`` whose ``forward`` is ``nn.Sequential``'s own; the first is exactly
+  ``nn.Linear`` (no subclass; weight and bias trainable parameters of the solver, owned by no other module -- the rules of
+  ``LinearParamGrads.install``), the second exactly ``nn.Tanh``;
+* neither module nor the container carries a hook that is not the engine's own, and no global module hook is registered;
+* at call time: the input is a contiguous CUDA fp32 tensor of the state's dtype, autocast is off, ``pn_linear_fwd_supported``.
+
+Anything else runs the stock modules.  Only evaluations inside ``LinearFwd.window`` are affected -- the solver opens it around its own
+calls of func; for its duration the eligible containers carry an instance-level ``forward`` (the runner below), removed when the window
+closes, also when func raises: func is left exactly as found (pnode_amd/_funcguard.py sees no change between two calls).
+
+Autograd: the pair is one ``torch.autograd.Function``.  Its backward forms ``g_z = tanh_backward(g_a, a)`` and ``dx = g_z W`` with
+the torch operations autograd runs for the stock modules -- the reverse sweep's kernels do not change -- and hands ``(g_z, x)`` to
+``LinearParamGrads._grad_hook`` (the queue, the grouped launch, the side stream, the deferral under per-evaluation graphs) when that
+is active for the evaluation; otherwise it returns ``dW = g_z^T x`` and ``db = colsum(g_z)`` to autograd.  ``Evaluation.clean`` sees
+the pair's node as it sees a hooked layer: the walk goes on along the input edge only.
+
+At a solver's first fused evaluation outside a capture the pair is computed through torch as well; a difference above 1e-6 of
+``sum |x w| + |b|`` (the library path's own 1.0e-7, the split product's 5.7e-8 and a few ulp of the two tanh, with room) switches
+fusing off for that solver, ``why`` recorded.  ``-pn_linear_fwd auto|0|1``."""
+import contextlib
+import warnings
+import weakref
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+CHECK_TOL = 1e-6
+
+
+def _global_hooks():
+    mod = torch.nn.modules.module
+    for name in ("_global_forward_hooks", "_global_forward_pre_hooks", "_global_backward_hooks", "_global_backward_pre_hooks",
+                 "_global_forward_hooks_always_called"):
+        if getattr(mod, name, None):
+            return True
+    return False
+
+
+def _autocast_on(device_type):
+    try:
+        return bool(torch.is_autocast_enabled(device_type))
+    except TypeError:                                  # (an older spelling: the HIP device's state, and the host's)
+        return bool(torch.is_autocast_enabled() or (device_type == "cpu" and torch.is_autocast_cpu_enabled()))
+
+
+def _user_hooked(m):
+    """True when `m` carries a forward, pre-forward or backward hook that is not the engine's own (the forward hook of a solver's
+    LinearParamGrads -- this solver's or another's on the same func: it acts only while ITS solver records an evaluation)."""
+    from ._lineargrad import LinearParamGrads
+    for name in ("_forward_hooks", "_forward_pre_hooks", "_backward_hooks", "_backward_pre_hooks"):
+        for h in (getattr(m, name, None) or {}).values():
+            if not isinstance(getattr(h, "__self__", None), LinearParamGrads):
+                return True
+    return False
+
+
+def find_pairs(func, params):
+    """[(sequential, {index of the Linear child: (linear, tanh)})] of func, and {class name of a container: reason} for the
+    Linear -> Tanh pairs that cannot be fused (what -pn_linear_fwd 1 warns about)."""
+    plans, refused = [], {}
+    if not isinstance(func, nn.Module):
+        return plans, refused
+    index = {id(p) for p in params}
+    owners = {}
+    for m in func.modules():
+        for p in m._parameters.values():
+            if p is not None:
+                owners[id(p)] = owners.get(id(p), 0) + 1
+    seen = set()
+    for seq in func.modules():
+        if not isinstance(seq, nn.Sequential) or id(seq) in seen:
+            continue
+        seen.add(id(seq))
+        kids = list(seq._modules.values())
+        pairs = {}
+        for i in range(len(kids) - 1):
+            lin, act = kids[i], kids[i + 1]
+            if not (isinstance(lin, nn.Linear) and isinstance(act, nn.Tanh)):
+                continue
+            why = None
+            if type(seq) is not nn.Sequential or "forward" in seq.__dict__:
+                why = "the container's forward is not nn.Sequential's own"
+            elif type(lin) is not nn.Linear or type(act) is not nn.Tanh:
+                why = "a subclass of nn.Linear or nn.Tanh"
+            elif "forward" in lin.__dict__ or "forward" in act.__dict__:
+                why = "an instance-level forward on the layer"
+            else:
+                for p in (lin.weight, lin.bias):
+                    if p is None:
+                        continue
+                    if not isinstance(p, nn.Parameter) or not p.requires_grad or id(p) not in index:
+                        why = "a weight or bias that is not a trainable parameter of the solver"
+                    elif owners.get(id(p), 0) != 1:
+                        why = "a weight or bias shared with another module"
+                if why is None and kids.count(lin) + kids.count(act) != 2:
+                    why = "the layer appears twice in the container"
+            if why is None:
+                pairs[i] = (lin, act)
+            else:
+                refused.setdefault(type(seq).__name__, why)
+        if pairs:
+            plans.append((seq, pairs))
+    return plans, refused
+
+
+class _Call(object):
+    """What one fused call carries into its backward."""
+    __slots__ = ("owner", "module", "grads", "ev", "version")
+
+
+class _LinearTanh(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, call):
+        a = call.owner.kernel(x.reshape(-1, w.shape[1]), w, b).view(x.shape[:-1] + (w.shape[0],))
+        ctx.save_for_backward(x, w, a)
+        ctx.call = call
+        ctx.has_bias = b is not None
+        return a
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, a = ctx.saved_tensors
+        call = ctx.call
+        g_z = torch.ops.aten.tanh_backward(g, a)
+        dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
+        lg, ev = call.grads, call.ev
+        taken = False
+        if lg is not None and ev is not None and id(call.module) in lg.slots and not (lg.muted or lg.disabled or ev.muted):
+            # the path of a hooked layer's output hook (pnode_amd/_lineargrad.py): queued for the stage's grouped launch
+            lg._grad_hook(call.module, x.detach(), call.version, ev, g_z)
+            taken = not lg.disabled              # (a backward pass that is not a stage VJP of the solver switches the engine off there)
+        dw = db = None
+        if not taken:
+            g2 = g_z.reshape(-1, w.shape[0])
+            if ctx.needs_input_grad[1]:
+                dw = g2.t().mm(x.reshape(-1, w.shape[1]))
+            if ctx.has_bias and ctx.needs_input_grad[2]:
+                db = g2.sum(0)
+        return dx, dw, db, None
+
+
+class LinearFwd(object):
+    device_type = "cuda"           # (the tests of the eligibility rules run the rules on host tensors)
+
+    def __init__(self, ode):
+        self._ode = weakref.ref(ode)
+        self.plans = []            # [(sequential, {child index: (linear, tanh)})]
+        self.mode = "auto"
+        self.disabled = False      # the forward check failed
+        self.why = None
+        self.checked = False
+        self.n_fused = 0           # pair calls that ran as one launch
+        self._warned = False
+        self._ok = {}              # (rows, out_f, in_f) -> pn_linear_fwd_supported
+
+    def install(self, func, params, mode="auto"):
+        """Find the eligible pairs of `func`; returns True when there is at least one."""
+        self.mode = mode
+        self.plans, refused = find_pairs(func, params)
+        if mode == "1" and refused and not self._warned:
+            self._warned = True
+            for cls, why in refused.items():
+                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> Tanh pair of %s runs the stock modules: %s" % (cls, why), RuntimeWarning)
+        return bool(self.plans)
+
+    @property
+    def active(self):
+        return bool(self.plans) and not self.disabled
+
+    # the one place the device is touched: tests of the eligibility rules replace it by the torch expression
+    def kernel(self, x2, w, b):
+        return self._ode()._ops.linear_fwd(x2, w, b, True)
+
+    def supported(self, rows, out_f, in_f):
+        key = (rows, out_f, in_f)
+        ok = self._ok.get(key)
+        if ok is None:
+            ops = self._ode()._ops
+            ok = self._ok[key] = bool(hasattr(ops, "linear_fwd_supported") and ops.linear_fwd_supported(rows, out_f, in_f))
+        return ok
+
+    def _refuse(self, why):
+        if self.mode == "1" and not self._warned:
+            self._warned = True
+            warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> Tanh pair runs the stock modules: %s" % why, RuntimeWarning)
+        return None
+
+    def _fusable(self, lin, x):
+        """The call-time half of the eligibility rules; None or the reason as a string."""
+        ode = self._ode()
+        if ode is None or not isinstance(x, torch.Tensor):
+            return "the input is no tensor"
+        w, b = lin.weight, lin.bias
+        if _autocast_on(x.device.type):
+            return "autocast is on"
+        if x.device.type != self.device_type or x.dtype != torch.float32 or x.dtype != ode.tensor_dtype or w.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
+            return "not a CUDA fp32 tensor of the state's dtype"
+        if x.dim() < 1 or x.shape[-1] != w.shape[1] or not x.is_contiguous() or not w.is_contiguous() or (b is not None and not b.is_contiguous()):
+            return "operands are not contiguous"
+        if w.device != x.device or x.data_ptr() % 16 or w.data_ptr() % 16:
+            return "operands are not 16-byte aligned on one device"
+        if not self.supported(x.numel() // w.shape[1], w.shape[0], w.shape[1]):
+            return "outside pn_linear_fwd_supported"
+        return None
+
+    def _check(self, x, w, b, a):
+        """First fused call of a solver: the pair through torch as well."""
+        self.checked = True
+        with torch.no_grad():
+            x2 = x.reshape(-1, w.shape[1])
+            ref = torch.tanh(F.linear(x2, w, b))
+            scale = x2.abs() @ w.abs().t()
+            if b is not None:
+                scale = scale + b.abs()
+            ok = torch.isfinite(ref) & (scale > 0)
+            if not bool(ok.any()):
+                self.checked = False
+                return True
+            err = float(((a.reshape(ref.shape) - ref).abs() / scale)[ok].max())
+        if not err <= CHECK_TOL:
+            self.disabled = True
+            self.why = "pn_linear_fwd and torch.tanh(F.linear) differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
+            warnings.warn("pnode_amd: the fused Linear -> Tanh forward is switched off for this solver: " + self.why, RuntimeWarning)
+            return False
+        return True
+
+    def _pair(self, lin, act, x, grads):
+        why = self._fusable(lin, x)
+        if why is not None:
+            self._refuse(why)
+            return act(lin(x))
+        w, b = lin.weight, lin.bias
+        ev = grads.recording if grads is not None else None
+        if ev is not None and not grads.note_fused(lin, x):
+            ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
+        call = _Call()
+        call.owner, call.module, call.grads, call.ev, call.version = self, lin, grads, ev, x._version
+        a = _LinearTanh.apply(x, w, b, call)
+        if not self.checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            if not self._check(x.detach(), w.detach(), None if b is None else b.detach(), a.detach()):
+                return act(lin(x))
+        if ev is not None and a.grad_fn is not None:
+            ev.through[a.grad_fn] = x.grad_fn     # Evaluation.clean passes the pair along its input edge only
+        self.n_fused += 1
+        return a
+
+    def _runner(self, seq, pairs, grads):
+        def forward(inp):
+            kids = list(seq._modules.values())
+            i, n = 0, len(kids)
+            while i < n:
+                p = pairs.get(i)
+                if p is not None and i + 1 < n and kids[i] is p[0] and kids[i + 1] is p[1] and not self.disabled:
+                    inp = self._pair(p[0], p[1], inp, grads)
+                    i += 2
+                else:
+                    inp = kids[i](inp)
+                    i += 1
+            return inp
+        return forward
+
+    @contextlib.contextmanager
+    def window(self, grads=None):
+        """The solver evaluates func: until the window closes the eligible containers run their pairs fused.  `grads`: the
+        solver's LinearParamGrads when it records this evaluation, else None."""
+        put = []
+        try:
+            if self.active and not _global_hooks():
+                for seq, pairs in self.plans:
+                    if "forward" in seq.__dict__ or type(seq) is not nn.Sequential:
+                        continue
+                    if _user_hooked(seq) or any(_user_hooked(m) for pr in pairs.values() for m in pr):
+                        self._refuse("a forward, pre-forward or backward hook on the pair or its container")
+                        continue
+                    seq.__dict__["forward"] = self._runner(seq, pairs, grads)
+                    put.append(seq)
+            yield
+        finally:
+            for seq in put:
+                seq.__dict__.pop("forward", None)

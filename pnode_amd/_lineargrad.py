@@ -230,20 +230,35 @@ class LinearParamGrads(object):
             # but NOT what differentiating func gives: left to autograd
             ev.unfused = True
             return None
-        if self.unit_capture:
-            out_f, in_f = module.weight.shape
-            rows = x.numel() // max(in_f, 1)
-            ode = self._ode()
-            st = self.partials.get(id(module))
-            if not (self.fused and st is not None and ode is not None and x.is_cuda and x.dtype == ode.tensor_dtype
-                    and ode._ops.linear_wgrad_supported(rows, out_f, in_f)):
-                ev.unfused = True
-                return None
+        if self.unit_capture and not self._unit_ok(module, x):
+            ev.unfused = True
+            return None
         # the hook keeps an alias of the input outside autograd's saved tensors: the version is checked by hand, as
         # autograd checks its own ("modified by an inplace operation")
         output.register_hook(functools.partial(self._grad_hook, module, x.detach(), x._version, ev))
         ev.through[output.grad_fn] = x.grad_fn
         return None
+
+    def _unit_ok(self, module, x):
+        """Inside a per-evaluation graph: this call's sensitivities go through the fused kernel (whose scale is no host scalar)."""
+        out_f, in_f = module.weight.shape
+        rows = x.numel() // max(in_f, 1)
+        ode = self._ode()
+        st = self.partials.get(id(module))
+        return bool(self.fused and st is not None and ode is not None and x.is_cuda and x.dtype == ode.tensor_dtype
+                    and ode._ops.linear_wgrad_supported(rows, out_f, in_f))
+
+    def note_fused(self, module, x):
+        """A call of `module` inside the evaluation being recorded ran as a fused Linear -> Tanh pair (pnode_amd/_linearfwd.py), which
+        calls no forward hook: what `_forward_hook` decides for a hooked call.  True: the pair's backward hands its (G, x) to
+        `_grad_hook`; False: its parameters are autograd's in this evaluation."""
+        ev = self.recording
+        if ev is None or id(module) not in self.slots:
+            return False
+        if self.unit_capture and not self._unit_ok(module, x):
+            ev.unfused = True
+            return False
+        return True
 
     def _grad_hook(self, module, x, version, ev, g):
         if self.muted or self.disabled or ev.muted:

@@ -42,12 +42,15 @@ class RKSweep(object):
         seen = tuple(p.detach().requires_grad_(True) for p in params) if capturing else params
         if lin is not None:
             lin.begin()                # func's Linear layers hook their outputs: dW / db are accumulated by the engine
+        fwd = self._fwd if (which == "EX" and self._fwd is not None and self._fwd.active) else None
         out = None
         try:
-            if capturing:
-                out = torch.func.functional_call(fn, dict(zip(names, seen)), (t, y))
-            else:
-                out = fn(t, y)
+            # (the window: eligible Linear -> Tanh pairs of func run as one launch each, pnode_amd/_linearfwd.py)
+            with (fwd.window(lin) if fwd is not None else contextlib.nullcontext()):
+                if capturing:
+                    out = torch.func.functional_call(fn, dict(zip(names, seen)), (t, y))
+                else:
+                    out = fn(t, y)
         finally:
             if lin is not None and out is None:
                 lin.abort()
@@ -71,6 +74,9 @@ class RKSweep(object):
                 y = y.detach().requires_grad_(True)
                 k, wrt = self._func_with_grad(t, y)
             tape.append((y, k, wrt, t) if self._tgrad else (y, k, wrt))
+        elif self._fwd is not None and self._fwd.active:
+            with self._fwd.window():
+                k = self.funcEX(t, y)
         else:
             k = self.funcEX(t, y)
         k = self._func_result(k, y_flat)
@@ -891,6 +897,7 @@ class RKSweep(object):
         # 869 against 958 time-steps/s; with 64 x 64 tiles the second stream is worth +1.5 %, profiles/r06_side_stream.txt)
         if hasattr(self._ops, "wgrad_flags"):
             self._ops.wgrad_flags = (_lib.PN_WGRAD_EXACT_FP32 if exact else 0) | (_lib.PN_WGRAD_TILE_64 if tile64 else 0)
+        self._setup_linear_fwd()
         sig = (id(self.funcEX), on, self._stepper_kind in (None, "imex"), tuple(id(p) for p in self._paramsE), gemm, side_on, exact, tile64)
         if sig == self._lin_sig:
             return
@@ -906,6 +913,34 @@ class RKSweep(object):
             lin.side_priority = side != "same-priority"
             if lin.install(self.funcEX, self._paramsE, self._poffE if self._stepper_kind == "imex" else self._poff):
                 self._lin = lin
+
+    def _setup_linear_fwd(self):
+        """(Re)install the fused forward of func's Linear -> Tanh pairs (pnode_amd/_linearfwd.py): explicit RK path and ARKIMEX's
+        func2, as the engine-side sensitivities; -pn_linear_fwd auto|0|1 (not a PETSc option)."""
+        mode = str(options.get_all().get("pn_linear_fwd", "auto"))
+        mode = "auto" if mode == "auto" else ("1" if options.truthy(mode, False) else "0")
+        from ._linearfwd import LinearFwd
+        on = mode != "0" and self._stepper_kind in (None, "imex") and self.device.type == LinearFwd.device_type \
+            and self.tensor_dtype == torch.float32 and hasattr(self._ops, "linear_fwd")
+        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE))
+        if sig == self._fwd_sig:
+            return
+        self._fwd_sig = sig
+        self._fwd = None
+        if on and self._paramsE:
+            fwd = LinearFwd(self)
+            if fwd.install(self.funcEX, self._paramsE, mode):
+                self._fwd = fwd
+
+    @property
+    def linear_fwd(self):
+        """How func's Linear -> Tanh pairs run in the solver's evaluations: "fused (N pairs)" or "stock modules (why)"."""
+        fwd = self._fwd
+        if fwd is None:
+            return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)"
+        if fwd.disabled:
+            return "stock modules (%s)" % fwd.why
+        return "fused (%d pairs, %d calls so far)" % (sum(len(p) for _, p in fwd.plans), fwd.n_fused)
 
     def _flush_param_accum(self):
         self._flush_bias_accum()

@@ -107,6 +107,7 @@ class RowSweep(object):
             if self._lin is not None:
                 self._lin.remove()
             self._lin, self._lin_sig = None, None
+            self._fwd, self._fwd_sig = None, None
             return
         return super(RowSweep, self)._setup_linear_grads()
 

@@ -220,6 +220,28 @@ class HipVecOps(object):
         check(self.lib.pn_linear_wgrad_finish(self.stream(), self.code, out_f, in_f, pw.data_ptr(), None if pb is None else pb.data_ptr(),
                                               mu_w.data_ptr(), None if mu_b is None else mu_b.data_ptr()))
 
+    # ---- the forward of a Linear layer with its activation (pn_linear_fwd, csrc/pn_linear.hip)
+    def linear_fwd_supported(self, rows, out_f, in_f):
+        return bool(self.lib.pn_linear_fwd_supported(self.code, rows, out_f, in_f))
+
+    def linear_fwd(self, x, w, b, tanh, y=None):
+        """y = act(x w^T + b), act = tanh or the identity; x (rows, in_f), w (out_f, in_f), b (out_f,) or None: contiguous fp32 on this device.
+        Refused (PnError), never run another way, outside pn_linear_fwd_supported."""
+        rows, in_f = x.shape
+        out_f = w.shape[0]
+        for v in (x, w, b, y):
+            if v is not None and not (v.is_contiguous() and v.dtype == torch.float32 and v.device == x.device and x.is_cuda):
+                raise PnError("pn_linear_fwd: contiguous fp32 tensors on one HIP device")
+        if w.shape[1] != in_f or (b is not None and b.numel() != out_f):
+            raise PnError("pn_linear_fwd: x (rows, in_f), w (out_f, in_f), b (out_f,)")
+        if y is None:
+            y = torch.empty((rows, out_f), dtype=x.dtype, device=x.device)
+        elif tuple(y.shape) != (rows, out_f):
+            raise PnError("pn_linear_fwd: y (rows, out_f)")
+        check(self.lib.pn_linear_fwd(self.stream(), _lib.dtype_code(x.dtype), rows, out_f, in_f, x.data_ptr(), w.data_ptr(),
+                                     None if b is None else b.data_ptr(), _lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY, y.data_ptr()))
+        return y
+
     # ---- dense output (-pn_output_times interpolate; csrc/pn_dense.hip)
     dense_flags = _lib.PN_DENSE_NONTEMPORAL      # output rows are not read again by the sweep: non-temporal stores
 

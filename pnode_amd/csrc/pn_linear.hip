@@ -271,6 +271,43 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
+// The helpers every split-bf16 kernel of this file shares (the two wgrad forms below, pn_linear_fwd further down).
+// Four fp32 values -> their three bf16 terms, packed four to a u32x2 in element order.
+struct Split3 {
+  u32x2 hi, mid, lo;
+};
+__device__ __forceinline__ Split3 split3(const f32x4 v) {
+  unsigned a[4], r1[4], r2[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    a[e] = __float_as_uint(v[e]);
+    const float f1 = v[e] - __uint_as_float(a[e] & 0xFFFF0000u);               // exact
+    r1[e] = __float_as_uint(f1);
+    r2[e] = __float_as_uint(f1 - __uint_as_float(r1[e] & 0xFFFF0000u));       // exact; at most 8 significant bits are left
+  }
+  // v_perm_b32 with this selector: the top halves of two patterns side by side = two bf16, truncated
+  Split3 s;
+  s.hi = u32x2{__builtin_amdgcn_perm(a[1], a[0], 0x07060302u), __builtin_amdgcn_perm(a[3], a[2], 0x07060302u)};
+  s.mid = u32x2{__builtin_amdgcn_perm(r1[1], r1[0], 0x07060302u), __builtin_amdgcn_perm(r1[3], r1[2], 0x07060302u)};
+  s.lo = u32x2{__builtin_amdgcn_perm(r2[1], r2[0], 0x07060302u), __builtin_amdgcn_perm(r2[3], r2[2], 0x07060302u)};
+  return s;
+}
+// the six largest of the nine cross terms, the small ones first
+__device__ __forceinline__ void six_products(f32x16 &acc, const s16x8 ah, const s16x8 am, const s16x8 al, const s16x8 bh, const s16x8 bm,
+                                             const s16x8 bl) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+// [k][64 bf16] images read transposed (wgrad: the operands are k-major): the two 64-byte halves of a row swapped on rows with (k >> 1) & 1
+__device__ __forceinline__ int swz_tr(int k, int c) { return c ^ (((k >> 1) & 1) << 5); }
+// [row][32 bf16] images read along the row by ds_read_b128 (fwd: the operands are k-contiguous): the four 16-byte slots of a 64-byte
+// row rotated by (row >> 2) & 3, so that the 16 rows of a ds_read_b128 lane group fall on the 16 slots of the 256-byte bank row
+__device__ __forceinline__ int swz_row(int row, int slot) { return slot ^ ((row >> 2) & 3); }
+
 template <bool RAGGED>
 __device__ __forceinline__ void wgrad_body_x3(const GroupArgs &ga_) {
   constexpr int BK = 32, ROWB = 128, PART = BK * ROWB, BUF = 2 * 3 * PART;      // bytes: row, (operand, part), buffer
@@ -302,7 +339,7 @@ __device__ __forceinline__ void wgrad_body_x3(const GroupArgs &ga_) {
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;
   double *pbp = bias && t < BM ? PB + ((size_t)split * ntn + tn) * M + tm * BM + t : nullptr;
-  auto swz = [](int k, int c) { return c ^ (((k >> 1) & 1) << 5); };
+  auto swz = [](int k, int c) { return swz_tr(k, c); };
 
   auto gload = [&](int slab) {
     const int row = k0 + slab * BK + lrow;
@@ -314,25 +351,14 @@ __device__ __forceinline__ void wgrad_body_x3(const GroupArgs &ga_) {
     }
   };
   auto split_store = [&](const f32x4 v, char *base) {
-    unsigned a[4], r1[4], r2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      a[e] = __float_as_uint(v[e]);
-      const float f1 = v[e] - __uint_as_float(a[e] & 0xFFFF0000u);               // exact
-      r1[e] = __float_as_uint(f1);
-      r2[e] = __float_as_uint(f1 - __uint_as_float(r1[e] & 0xFFFF0000u));       // exact; at most 8 significant bits are left
-    }
-    // v_perm_b32 with this selector: the top halves of two patterns side by side = two bf16, truncated
-    const u32x2 hi = {__builtin_amdgcn_perm(a[1], a[0], 0x07060302u), __builtin_amdgcn_perm(a[3], a[2], 0x07060302u)};
-    const u32x2 mid = {__builtin_amdgcn_perm(r1[1], r1[0], 0x07060302u), __builtin_amdgcn_perm(r1[3], r1[2], 0x07060302u)};
-    const u32x2 lo = {__builtin_amdgcn_perm(r2[1], r2[0], 0x07060302u), __builtin_amdgcn_perm(r2[3], r2[2], 0x07060302u)};
+    const Split3 s = split3(v);
     const int off = lrow * ROWB + swz(lrow, lc * 4) * 2;
-    *reinterpret_cast<u32x2 *>(base + off) = hi;
-    *reinterpret_cast<u32x2 *>(base + PART + off) = mid;
-    *reinterpret_cast<u32x2 *>(base + 2 * PART + off) = lo;
+    *reinterpret_cast<u32x2 *>(base + off) = s.hi;
+    *reinterpret_cast<u32x2 *>(base + PART + off) = s.mid;
+    *reinterpret_cast<u32x2 *>(base + 2 * PART + off) = s.lo;
   };
   // The workgroups of a tile row (tn = 0..ntn-1) see the same G slabs: slab s is added up by the one with tn == s % ntn.
-  int mine = tn;                                                 // the next slab whose column sums are this workgroup's
+  int mine = tn;                                                // the next slab whose column sums are this workgroup's
   auto lstore = [&](int slab, int buf) {
     char *b = smem + buf * BUF;
     const f32x4 g = alpha * gv;
@@ -365,12 +391,7 @@ __device__ __forceinline__ void wgrad_body_x3(const GroupArgs &ga_) {
     const char *b = smem + buf * BUF;
     const s16x8 ah = frag(b, wm * 32), am = frag(b + PART, wm * 32), al = frag(b + 2 * PART, wm * 32);
     const s16x8 bh = frag(b + 3 * PART, wn * 32), bm = frag(b + 4 * PART, wn * 32), bl = frag(b + 5 * PART, wn * 32);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);      // the small terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+    six_products(acc, ah, am, al, bh, bm, bl);
   };
   auto tile_row = [&](int e) { return (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); };      // (C/D map of the 32 x 32 MFMAs: dtype-independent)
 
@@ -464,7 +485,7 @@ __device__ __forceinline__ void wgrad_body_x3_wide(const GroupArgs &ga_) {
   for (int e = 0; e < 16; ++e) acc0[e] = 0.f, acc1[e] = 0.f;
   // db: this workgroup stands for the 64-wide tile columns 2 tn and 2 tn + 1 of its tile row -- their slots of PB, their slabs
   double *pbp = bias && t < 2 * TM ? PB + ((size_t)split * ntn64 + 2 * tn + (t >> 7)) * M + tm * TM + (t & 127) : nullptr;
-  auto swz = [](int k, int c) { return c ^ (((k >> 1) & 1) << 5); };
+  auto swz = [](int k, int c) { return swz_tr(k, c); };
 
   auto gload = [&](int slab) {
     const int row = k0 + slab * BK + lrow;
@@ -476,21 +497,11 @@ __device__ __forceinline__ void wgrad_body_x3_wide(const GroupArgs &ga_) {
     }
   };
   auto split_store = [&](const f32x4 v, char *base) {
-    unsigned a[4], r1[4], r2[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      a[e] = __float_as_uint(v[e]);
-      const float f1 = v[e] - __uint_as_float(a[e] & 0xFFFF0000u);
-      r1[e] = __float_as_uint(f1);
-      r2[e] = __float_as_uint(f1 - __uint_as_float(r1[e] & 0xFFFF0000u));
-    }
-    const u32x2 hi = {__builtin_amdgcn_perm(a[1], a[0], 0x07060302u), __builtin_amdgcn_perm(a[3], a[2], 0x07060302u)};
-    const u32x2 mid = {__builtin_amdgcn_perm(r1[1], r1[0], 0x07060302u), __builtin_amdgcn_perm(r1[3], r1[2], 0x07060302u)};
-    const u32x2 lo = {__builtin_amdgcn_perm(r2[1], r2[0], 0x07060302u), __builtin_amdgcn_perm(r2[3], r2[2], 0x07060302u)};
+    const Split3 s = split3(v);
     const int off = lrow * ROWB + swz(lrow, lc * 4) * 2;
-    *reinterpret_cast<u32x2 *>(base + off) = hi;
-    *reinterpret_cast<u32x2 *>(base + PART + off) = mid;
-    *reinterpret_cast<u32x2 *>(base + 2 * PART + off) = lo;
+    *reinterpret_cast<u32x2 *>(base + off) = s.hi;
+    *reinterpret_cast<u32x2 *>(base + PART + off) = s.mid;
+    *reinterpret_cast<u32x2 *>(base + 2 * PART + off) = s.lo;
   };
   int mine0 = 2 * tn, mine1 = 2 * tn + 1;                        // the next slabs of the two 64-wide tile columns
   auto lstore = [&](int slab, int buf) {
@@ -526,12 +537,7 @@ __device__ __forceinline__ void wgrad_body_x3_wide(const GroupArgs &ga_) {
     return f;
   };
   auto six = [&](f32x16 &acc, const s16x8 ah, const s16x8 am, const s16x8 al, const s16x8 bh, const s16x8 bm, const s16x8 bl) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);      // the order of the 64 x 64 form
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+    six_products(acc, ah, am, al, bh, bm, bl);                                 // the order of the 64 x 64 form
   };
   auto compute = [&](int buf) {
     const char *b = smem + buf * BUF;
@@ -656,6 +662,130 @@ __global__ __launch_bounds__(256) void pn_linear_bgrad_finish_kernel(double *__r
   for (k = 0; k < parts; ++k) PB[(size_t)k * M + m] = 0.0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The forward product of a Linear layer with its activation: Y = act(X W^T + b), X rows x in, W out x in, Y rows x out, row-major
+// fp32 (pn_linear_fwd) -- func's Linear -> Tanh pairs in ONE launch instead of a library GEMM and an elementwise kernel.
+// The arithmetic is the split-bf16 product above (split3, six_products).  What differs from wgrad is the shape: K = in is short
+// (64 to a few thousand) and BOTH operands are k-contiguous, so
+//   * no K split across workgroups: a workgroup of eight waves owns a 64 x 128 tile of Y over all of K and writes it once (4096 x 512:
+//     256 workgroups, one per CU; workgroups are dealt to the XCDs round-robin, so the tile index is rotated to give each XCD a
+//     contiguous range of tile rows: the four workgroups that share a 64-row slab of X share an L2);
+//   * slabs of 32 k through two LDS buffers, one barrier per slab, as wgrad; LDS image per (operand, part): [row][32 bf16], 64-byte rows
+//     whose 16-byte slots are rotated by swz_row; operand fragments by plain ds_read_b128 (lane l: row l & 31, k 8 (l >> 5) .. + 7 -- what
+//     v_mfma_f32_32x32x16_bf16 takes as it lies in memory), conflict-free;
+//   * waves 0-3 take k 0..15 of every slab, waves 4-7 k 16..31; a wave owns 32 x 64 of the tile (two accumulators, the three X
+//     fragments feed both: 0.75 KB of fragments per MFMA).  At the end the two K halves swap one accumulator each through LDS and
+//     each finishes ONE 32 x 32 block: (first half + second half) + bias, tanhf, one store -- all eight waves share the epilogue.
+// Fixed order, no atomics: the same bits on every launch.  tanhf is the device library's (at most 2 ulp by its documentation; exactly +-1
+// from |z| of about 9 on, NaN for NaN).  An infinite X or W gives NaN in the rows / columns it takes part in (inf - inf in the split).
+// RAGGED: rows % 64 != 0 or out % 128 != 0 -- rows of X / W that do not exist are loaded as zeros, their outputs not stored.
+constexpr int FM = 64, FN = 128, FK = 32, kFwdThreads = 512;
+
+struct FwdArgs {
+  const float *x, *w, *b;
+  float *y;
+  int rows, out_f, in_f, act, ntn;
+};
+
+template <bool RAGGED>
+__device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
+  constexpr int ROWB = 2 * FK, XPART = FM * ROWB, WPART = FN * ROWB, BUF = 3 * XPART + 3 * WPART;      // bytes: 64, 4 K, 8 K, 36 K
+  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];                                          // 72 KB
+  const float *__restrict__ X = a.x;
+  const float *__restrict__ W = a.w;
+  const int rows = a.rows, out_f = a.out_f, in_f = a.in_f, ntn = a.ntn;
+  const int nblk = (int)gridDim.x, bid = (int)blockIdx.x;
+  const int tile = nblk % 8 == 0 ? (bid & 7) * (nblk >> 3) + (bid >> 3) : bid;
+  const int tm = tile / ntn, tn = tile % ntn;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int kh = w >> 2, wm = w & 1, wn = (w >> 1) & 1;          // K half; rows 32 wm .. + 31, columns 64 wn .. + 63 of the tile
+  const int lrow = t >> 3, lc = t & 7;                           // this thread's vectors of a slab: rows lrow (X, W) and 64 + lrow (W), k 4 lc .. + 3
+  const int nslab = in_f / FK;
+  const bool xok = !RAGGED || tm * FM + lrow < rows;
+  const bool wok0 = !RAGGED || tn * FN + lrow < out_f, wok1 = !RAGGED || tn * FN + 64 + lrow < out_f;
+  const float *xp = X + (size_t)(tm * FM + lrow) * in_f + lc * 4;
+  const float *wp0 = W + (size_t)(tn * FN + lrow) * in_f + lc * 4;
+  const float *wp1 = wp0 + (size_t)64 * in_f;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 xv, wv0, wv1;
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc0[e] = 0.f, acc1[e] = 0.f;
+
+  auto gload = [&](int slab) {
+    xv = xok ? *reinterpret_cast<const f32x4 *>(xp + slab * FK) : zero4;
+    wv0 = wok0 ? *reinterpret_cast<const f32x4 *>(wp0 + slab * FK) : zero4;
+    wv1 = wok1 ? *reinterpret_cast<const f32x4 *>(wp1 + slab * FK) : zero4;
+  };
+  // (rows lrow and 64 + lrow rotate alike)
+  const int soff = lrow * ROWB + (swz_row(lrow, lc >> 1) << 4) + ((lc & 1) << 3);
+  auto split_store = [&](const f32x4 v, char *base, int part) {
+    const Split3 s = split3(v);
+    *reinterpret_cast<u32x2 *>(base + soff) = s.hi;
+    *reinterpret_cast<u32x2 *>(base + part + soff) = s.mid;
+    *reinterpret_cast<u32x2 *>(base + 2 * part + soff) = s.lo;
+  };
+  auto lstore = [&](int buf) {
+    char *b = smem + buf * BUF;
+    split_store(xv, b, XPART);
+    split_store(wv0, b + 3 * XPART, WPART);
+    split_store(wv1, b + 3 * XPART + 64 * ROWB, WPART);
+  };
+  // lane l: row r0 + (l & 31), this wave's K half, k 8 (l >> 5) .. + 7 of it
+  auto frag = [&](const char *part, int r0) -> s16x8 {
+    const int row = r0 + (lane & 31);
+    return *reinterpret_cast<const s16x8 *>(part + row * ROWB + (swz_row(row, 2 * kh + (lane >> 5)) << 4));
+  };
+  auto compute = [&](int buf) {
+    const char *xb = smem + buf * BUF, *wb = xb + 3 * XPART;
+    const s16x8 ah = frag(xb, wm * 32), am = frag(xb + XPART, wm * 32), al = frag(xb + 2 * XPART, wm * 32);
+    {
+      const s16x8 bh = frag(wb, wn * 64), bm = frag(wb + WPART, wn * 64), bl = frag(wb + 2 * WPART, wn * 64);
+      six_products(acc0, ah, am, al, bh, bm, bl);
+    }
+    {
+      const s16x8 bh = frag(wb, wn * 64 + 32), bm = frag(wb + WPART, wn * 64 + 32), bl = frag(wb + 2 * WPART, wn * 64 + 32);
+      six_products(acc1, ah, am, al, bh, bm, bl);
+    }
+  };
+
+  gload(0);
+  lstore(0);
+  if (nslab > 1) gload(1);
+  __syncthreads();
+  for (int s = 0; s < nslab; ++s) {
+    if (s + 1 < nslab) lstore((s + 1) & 1);           // the other buffer: its last readers passed the barrier of slab s - 1
+    compute(s & 1);
+    if (s + 2 < nslab) gload(s + 2);
+    __syncthreads();
+  }
+  // ---- the end (the slab buffers are free): K half 0 finishes block 0 of its wave tile, K half 1 block 1 of the same tile (waves w and
+  // w ^ 4 hold the two halves of one tile): each hands the accumulator it does not finish to the other, [8 waves x 16 registers][64 lanes]
+  float(*red)[64] = reinterpret_cast<float(*)[64]>(smem);
+  static_assert(sizeof(smem) >= 8 * 16 * 64 * sizeof(float), "the exchange is staged in the slab buffers");
+#pragma unroll
+  for (int e = 0; e < 16; ++e) red[w * 16 + e][lane] = kh == 0 ? acc1[e] : acc0[e];
+  __syncthreads();
+  const int col = tn * FN + wn * 64 + kh * 32 + (lane & 31);
+  const bool colok = !RAGGED || col < out_f;
+  const float bias = (a.b != nullptr && colok) ? a.b[col] : 0.f;
+  const int row0 = tm * FM + wm * 32 + 4 * (lane >> 5);          // (C/D map of the 32 x 32 MFMAs: register e is row (e & 3) + 8 (e >> 2) + 4 (lane >> 5))
+  float *yp = a.y + (size_t)row0 * out_f + col;
+  const bool tanh_act = a.act == PN_ACT_TANH;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const float other = red[(w ^ 4) * 16 + e][lane];
+    const float first = kh == 0 ? acc0[e] : other, second = kh == 0 ? other : acc1[e];
+    float z = (first + second) + bias;
+    if (tanh_act) z = tanhf(z);
+    const int r = (e & 3) + 8 * (e >> 2);
+    if (colok && (!RAGGED || row0 + r < rows)) yp[(size_t)r * out_f] = z;
+  }
+}
+
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_fwd_kernel_f32x3(FwdArgs a) { linear_fwd_body<false>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_fwd_kernel_f32x3_ragged(FwdArgs a) { linear_fwd_body<true>(a); }
+
 int cu_count() {
   static int n = 0;              // (the calling thread's current device; every device of a node is the same part)
   if (n == 0) {
@@ -757,6 +887,30 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
   if (dtype != PN_F32 && dtype != PN_F64) return pn::fail("pn_linear_wgrad_finish: fp32 or fp64");
   if (!pn::aligned16(pw, mu_w)) return pn::fail("pn_linear_wgrad_finish: operands must be 16-byte aligned");
   return pn::with_dtype(dtype, [&](auto t) { return finish_t<decltype(t)>((hipStream_t)stream, out_f, in_f, pw, pb, mu_w, mu_b); });
+}
+
+int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f) {
+  if (dtype != PN_F32) return 0;
+  const int64_t lim = (int64_t)1 << 30;
+  if (!(rows >= 256 && rows < lim && out_f > 0 && out_f < lim && out_f % 64 == 0 && in_f > 0 && in_f < lim && in_f % 64 == 0)) return 0;
+  return ((rows + FM - 1) / FM) * ((out_f + FN - 1) / FN) < lim ? 1 : 0;
+}
+
+int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
+                  void *y) {
+  if (!pn_linear_fwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_fwd: unsupported dtype or shape (see pn_linear_fwd_supported)");
+  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH) return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY or PN_ACT_TANH");
+  if (x == nullptr || w == nullptr || y == nullptr) return pn::fail("pn_linear_fwd: null operand");
+  if (!pn::aligned16(x, w, y) || (reinterpret_cast<uintptr_t>(b) & 3)) return pn::fail("pn_linear_fwd: operands must be 16-byte aligned");
+  if (x == y) return pn::fail("pn_linear_fwd: y must not be x (other workgroups still read the rows a workgroup writes)");
+  FwdArgs a;
+  a.x = (const float *)x, a.w = (const float *)w, a.b = (const float *)b, a.y = (float *)y;
+  a.rows = (int)rows, a.out_f = (int)out_f, a.in_f = (int)in_f, a.act = act;
+  a.ntn = (int)((out_f + FN - 1) / FN);
+  const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)a.ntn;
+  const bool ragged = rows % FM != 0 || out_f % FN != 0;
+  return pn::launch("pn_linear_fwd", ragged ? pn_linear_fwd_kernel_f32x3_ragged : pn_linear_fwd_kernel_f32x3, dim3(blocks), dim3(kFwdThreads),
+                    (hipStream_t)stream, a);
 }
 
 }  // extern "C"

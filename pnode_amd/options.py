@@ -7,6 +7,11 @@ override the ``method`` keyword, the controller, tolerances and the checkpointin
 same spellings are honoured here: call ``pnode_amd.init(sys.argv)`` where the reference calls
 ``petsc4py.init(sys.argv)``; options can also come from the ``PETSC_OPTIONS`` environment
 variable (PETSc reads it too) or ``set_option``.
+
+The engine's own options (``-pn_*``, no PETSc spelling) are read from the same database where they act; README.md lists
+them.  ``-pn_linear_fwd auto|0|1`` (pnode_amd/_linearfwd.py, read in ``RKSweep._setup_linear_fwd``): ``auto``, the default, runs the
+eligible ``nn.Linear -> nn.Tanh`` pairs of func as one ``pn_linear_fwd`` launch each inside the solver's own evaluations; ``0`` runs
+the stock modules everywhere; ``1`` is ``auto`` and warns once, with the reason, about a pair that cannot be fused.
 """
 import os
 import shlex

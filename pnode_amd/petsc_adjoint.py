@@ -91,6 +91,8 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs, ErrorNorm):
         self._sg = None                # the per-evaluation hipGraphs the sweep in progress replays (pnode_amd/_stagegraphs.py)
         self._unit_capture = False
         self._lin_sig = None
+        self._fwd = None               # func's Linear -> Tanh pairs as one launch in the solver's own evaluations (_linearfwd.py)
+        self._fwd_sig = None
         self._theta = None
         self._tgrad = False            # the solve in progress differentiates with respect to t
         self._tg = None                # ... and the reverse sweep in progress accumulates dL/dt (RKSweep._tg_begin)
