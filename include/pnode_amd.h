@@ -241,6 +241,22 @@ int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f
 int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
                   void *y);
 
+/* The backward of such a pair with respect to its input in one launch (csrc/pn_linear.hip): for g (the cotangent at the pair's output)
+ * and a (the pair's output, tanh of the biased sum) rows x out_f, w out_f x in_f AS IT LIES (no transposed copy is read or kept: an
+ * optimiser changes w in place between two replays of a captured sweep), all row-major fp32:
+ *   gz[r][k] = g[r][k] (1 - a[r][k]^2)   rows x out_f, written once -- the cotangent pn_linear_wgrad consumes
+ *   dx[r][n] = sum_k gz[r][k] w[k][n]     rows x in_f,  written once
+ * gz is formed in fp32 (1 - a a may contract to an fma: not aten.tanh_backward bit for bit, within 3 * 2^-24 |g| of the exact value); the
+ * product is the split-bf16 one of pn_linear_fwd on the same 64 x 128 tiles over all of out_f.  No atomics, no work buffers, the same bits
+ * on every launch.  A NaN or Inf in g or a stays in its own rows of gz and dx; a == +-1 with finite g gives gz == 0; an infinite gz or w
+ * gives NaN in the products it takes part in.  All five operands non-NULL and 16-byte aligned; gz and dx share no byte with each other
+ * or with an input (other workgroups still read them): refused otherwise, nothing launched.  Replaces, in the reverse sweep's stage VJPs,
+ * the tanh_backward kernel and the library GEMM of the pair.
+ * pn_linear_bwd_supported: fp32, rows >= 256 (any number), out_f % 64 == 0, in_f % 64 == 0, the size limits of pn_linear_fwd_supported. */
+int pn_linear_bwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
+int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, void *gz,
+                  void *dx);
+
 /* result_dev[j] = <x, y_j> for j < nk <= PN_MAX_TERMS, accumulated in double, reduced in a fixed
  * order (bit-reproducible).  ||x||^2 is the case y_0 == x.  Replaces VecMDot / VecNorm inside
  * the KSP(GMRES) and SNES that PETSc's implicit steppers run (TS type BE/CN, pa.py:651-654;

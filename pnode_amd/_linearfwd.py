@@ -14,15 +14,21 @@ Anything else runs the stock modules.  Only evaluations inside ``LinearFwd.windo
 calls of func; for its duration the eligible containers carry an instance-level ``forward`` (the runner below), removed when the window
 closes, also when func raises: func is left exactly as found (pnode_amd/_funcguard.py sees no change between two calls).
 
-Autograd: the pair is one ``torch.autograd.Function``.  Its backward forms ``g_z = tanh_backward(g_a, a)`` and ``dx = g_z W`` with
-the torch operations autograd runs for the stock modules -- the reverse sweep's kernels do not change -- and hands ``(g_z, x)`` to
+Autograd: the pair is one ``torch.autograd.Function``.  Its backward forms ``g_z = g_a (1 - a^2)`` and ``dx = g_z W`` in ONE launch
+(``pn_linear_bwd``: the tanh' prologue in registers, W read as it lies) where the backend has ``linear_bwd``, ``-pn_linear_bwd`` is not
+``0``, the input needs a gradient, ``g_a`` is a contiguous, 16-byte aligned fp32 tensor of the pair's shape on the weight's device,
+autocast is off, the backward is not itself differentiated and ``pn_linear_bwd_supported``; otherwise with the torch operations
+autograd runs for the stock modules (``tanh_backward``, ``matmul``).  A solver's first fused backward outside a capture is formed both
+ways: ``g_z`` must agree to ``3 * 2^-24 |g_a|`` (two roundings in ``1 - a^2``, one in the product, with or without an fma) and ``dx``
+to 1e-6 of ``|g_z| |W|``; a miss switches the fused BACKWARD off for that solver (the forward stays), ``bwd_why`` recorded, and the
+torch results are returned.  Either way the backward hands ``(g_z, x)`` to
 ``LinearParamGrads._grad_hook`` (the queue, the grouped launch, the side stream, the deferral under per-evaluation graphs) when that
 is active for the evaluation; otherwise it returns ``dW = g_z^T x`` and ``db = colsum(g_z)`` to autograd.  ``Evaluation.clean`` sees
 the pair's node as it sees a hooked layer: the walk goes on along the input edge only.
 
 At a solver's first fused evaluation outside a capture the pair is computed through torch as well; a difference above 1e-6 of
 ``sum |x w| + |b|`` (the library path's own 1.0e-7, the split product's 5.7e-8 and a few ulp of the two tanh, with room) switches
-fusing off for that solver, ``why`` recorded.  ``-pn_linear_fwd auto|0|1``."""
+fusing off for that solver, ``why`` recorded.  ``-pn_linear_fwd auto|0|1``, ``-pn_linear_bwd auto|0|1``."""
 import contextlib
 import warnings
 import weakref
@@ -128,8 +134,13 @@ class _LinearTanh(torch.autograd.Function):
     def backward(ctx, g):
         x, w, a = ctx.saved_tensors
         call = ctx.call
-        g_z = torch.ops.aten.tanh_backward(g, a)
-        dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
+        # both in one launch (pn_linear_bwd) where LinearFwd._bwd_fusable allows it, else the two torch operations
+        fused = call.owner._backward(g, a, w) if ctx.needs_input_grad[0] else None
+        if fused is not None:
+            g_z, dx = fused
+        else:
+            g_z = torch.ops.aten.tanh_backward(g, a)
+            dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
         lg, ev = call.grads, call.ev
         taken = False
         if lg is not None and ev is not None and id(call.module) in lg.slots and not (lg.muted or lg.disabled or ev.muted):
@@ -159,10 +170,19 @@ class LinearFwd(object):
         self.n_fused = 0           # pair calls that ran as one launch
         self._warned = False
         self._ok = {}              # (rows, out_f, in_f) -> pn_linear_fwd_supported
+        # the pair's backward as one launch (pn_linear_bwd): -pn_linear_bwd auto|0|1
+        self.bwd_mode = "auto"
+        self.bwd_disabled = False  # the backward check failed (the forward stays fused)
+        self.bwd_why = None
+        self.bwd_checked = False
+        self.n_fused_bwd = 0       # pair backwards that ran as one launch
+        self._warned_bwd = False
+        self._ok_bwd = {}          # (rows, out_f, in_f) -> pn_linear_bwd_supported
 
-    def install(self, func, params, mode="auto"):
+    def install(self, func, params, mode="auto", bwd_mode="auto"):
         """Find the eligible pairs of `func`; returns True when there is at least one."""
         self.mode = mode
+        self.bwd_mode = bwd_mode
         self.plans, refused = find_pairs(func, params)
         if mode == "1" and refused and not self._warned:
             self._warned = True
@@ -230,6 +250,96 @@ class LinearFwd(object):
             warnings.warn("pnode_amd: the fused Linear -> Tanh forward is switched off for this solver: " + self.why, RuntimeWarning)
             return False
         return True
+
+    # ---- the backward of a pair (called from _LinearTanh.backward)
+    def kernel_bwd(self, g2, a2, w):
+        return self._ode()._ops.linear_bwd(g2, a2, w)
+
+    def supported_bwd(self, rows, out_f, in_f):
+        key = (rows, out_f, in_f)
+        ok = self._ok_bwd.get(key)
+        if ok is None:
+            ops = self._ode()._ops
+            ok = self._ok_bwd[key] = bool(hasattr(ops, "linear_bwd_supported") and ops.linear_bwd_supported(rows, out_f, in_f))
+        return ok
+
+    def _bwd_fusable(self, g, a, w):
+        """None, or the reason (a string) this backward runs the two torch operations."""
+        ode = self._ode()
+        if ode is None or not hasattr(ode._ops, "linear_bwd"):
+            return "the backend has no linear_bwd"
+        if self.bwd_mode == "0":
+            return "-pn_linear_bwd 0"
+        if self.bwd_disabled:
+            return self.bwd_why
+        if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != w.device or g.device.type != self.device_type \
+                or g.shape != a.shape:
+            return "the cotangent is no fp32 tensor of the pair's shape on the weight's device"
+        if not (g.is_contiguous() and a.is_contiguous() and w.is_contiguous()):
+            return "the cotangent is not contiguous"
+        if g.data_ptr() % 16 or a.data_ptr() % 16 or w.data_ptr() % 16:
+            return "operands are not 16-byte aligned"
+        if _autocast_on(g.device.type):
+            return "autocast is on"
+        if torch.is_grad_enabled():
+            return "the backward pass is itself differentiated (create_graph)"
+        if not self.supported_bwd(g.numel() // w.shape[0], w.shape[0], w.shape[1]):
+            return "outside pn_linear_bwd_supported"
+        return None
+
+    def _check_bwd(self, g2, a2, w, gz, dx):
+        """First fused backward of a solver: both results through torch as well.  gz to 3 * 2^-24 |g| (two roundings in 1 - a^2, one in
+        the product, with or without an fma), dx to CHECK_TOL of |gz| |w| (the forward's bar in the forward's measure).  Returns None, or
+        the torch results after switching the fused backward -- only it -- off."""
+        self.bwd_checked = True
+        gz_t = torch.ops.aten.tanh_backward(g2, a2)
+        dx_t = torch.matmul(gz_t, w)
+        scale = gz_t.abs() @ w.abs()
+        fin = torch.isfinite(gz_t)
+        ok = torch.isfinite(dx_t) & (scale > 0)
+        if not bool(fin.any()) or not bool(ok.any()):
+            self.bwd_checked = False               # nothing to judge by: the next call is checked
+            return None
+        bad_z = bool((~((gz - gz_t).abs() <= 3.0 * 2.0 ** -24 * g2.abs()) & fin).any())
+        err = float(((dx - dx_t).abs() / scale)[ok].max())
+        if bad_z or not err <= CHECK_TOL:
+            self.bwd_disabled = True
+            self.bwd_why = "pn_linear_bwd and tanh_backward + matmul differ: " + (
+                "g_z by more than 3 * 2^-24 |g|" if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
+            warnings.warn("pnode_amd: the fused Linear -> Tanh backward is switched off for this solver: " + self.bwd_why, RuntimeWarning)
+            return gz_t, dx_t
+        return None
+
+    def _backward(self, g, a, w):
+        """(g_z, dx) of one pair by pn_linear_bwd, or None: the caller runs tanh_backward and matmul."""
+        why = self._bwd_fusable(g, a, w)
+        if why is not None:
+            if self.bwd_mode == "1" and not self._warned_bwd:
+                self._warned_bwd = True
+                warnings.warn("pnode_amd: -pn_linear_bwd 1: the backward of a Linear -> Tanh pair runs the torch operations: %s" % why, RuntimeWarning)
+            return None
+        out_f, in_f = w.shape
+        g2, a2 = g.reshape(-1, out_f), a.reshape(-1, out_f)
+        with torch.no_grad():
+            gz, dx = self.kernel_bwd(g2, a2, w)
+            if not self.bwd_checked and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
+                torch_way = self._check_bwd(g2, a2, w, gz, dx)
+                if torch_way is not None:
+                    gz, dx = torch_way
+                    return gz.view(g.shape), dx.view(g.shape[:-1] + (in_f,))
+        self.n_fused_bwd += 1
+        return gz.view(g.shape), dx.view(g.shape[:-1] + (in_f,))
+
+    @property
+    def bwd_status(self):
+        if self.bwd_mode == "0":
+            return "torch operations (-pn_linear_bwd 0)"
+        ode = self._ode()
+        if ode is None or not hasattr(ode._ops, "linear_bwd"):
+            return "torch operations (the backend has no linear_bwd)"
+        if self.bwd_disabled:
+            return "torch operations (%s)" % self.bwd_why
+        return "fused (%d calls so far)" % self.n_fused_bwd
 
     def _pair(self, lin, act, x, grads):
         why = self._fusable(lin, x)

@@ -916,20 +916,23 @@ class RKSweep(object):
 
     def _setup_linear_fwd(self):
         """(Re)install the fused forward of func's Linear -> Tanh pairs (pnode_amd/_linearfwd.py): explicit RK path and ARKIMEX's
-        func2, as the engine-side sensitivities; -pn_linear_fwd auto|0|1 (not a PETSc option)."""
+        func2, as the engine-side sensitivities; -pn_linear_fwd auto|0|1 (not a PETSc option).  -pn_linear_bwd auto|0|1: the backward
+        of the same pairs as one launch each (pn_linear_bwd); it lives in the pair's Function, so it has no effect without the forward."""
         mode = str(options.get_all().get("pn_linear_fwd", "auto"))
         mode = "auto" if mode == "auto" else ("1" if options.truthy(mode, False) else "0")
+        bwd = str(options.get_all().get("pn_linear_bwd", "auto"))
+        bwd = "auto" if bwd == "auto" else ("1" if options.truthy(bwd, False) else "0")
         from ._linearfwd import LinearFwd
         on = mode != "0" and self._stepper_kind in (None, "imex") and self.device.type == LinearFwd.device_type \
             and self.tensor_dtype == torch.float32 and hasattr(self._ops, "linear_fwd")
-        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE))
+        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd)
         if sig == self._fwd_sig:
             return
         self._fwd_sig = sig
         self._fwd = None
         if on and self._paramsE:
             fwd = LinearFwd(self)
-            if fwd.install(self.funcEX, self._paramsE, mode):
+            if fwd.install(self.funcEX, self._paramsE, mode, bwd):
                 self._fwd = fwd
 
     @property
@@ -941,6 +944,14 @@ class RKSweep(object):
         if fwd.disabled:
             return "stock modules (%s)" % fwd.why
         return "fused (%d pairs, %d calls so far)" % (sum(len(p) for _, p in fwd.plans), fwd.n_fused)
+
+    @property
+    def linear_bwd(self):
+        """How the backward of those pairs runs: "fused (N calls so far)" or "torch operations (why)"."""
+        fwd = self._fwd
+        if fwd is None or fwd.disabled:
+            return "torch operations (the pairs run the stock modules: see linear_fwd)"
+        return fwd.bwd_status
 
     def _flush_param_accum(self):
         self._flush_bias_accum()

@@ -242,6 +242,32 @@ class HipVecOps(object):
                                      None if b is None else b.data_ptr(), _lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY, y.data_ptr()))
         return y
 
+    # ---- the backward of a Linear -> Tanh pair with respect to its input (pn_linear_bwd, csrc/pn_linear.hip)
+    def linear_bwd_supported(self, rows, out_f, in_f):
+        return bool(self.lib.pn_linear_bwd_supported(self.code, rows, out_f, in_f))
+
+    def linear_bwd(self, g, a, w, gz=None, dx=None):
+        """(gz, dx) = (g (1 - a^2), gz w); g, a (rows, out_f), w (out_f, in_f): contiguous fp32 on this device.  Refused (PnError), never
+        run another way, outside pn_linear_bwd_supported, for an fp64 state, and where gz or dx shares memory with an input."""
+        rows, out_f = g.shape
+        in_f = w.shape[1]
+        for v in (g, a, w, gz, dx):
+            if v is not None and not (v.is_contiguous() and v.dtype == torch.float32 and v.device == g.device and g.is_cuda):
+                raise PnError("pn_linear_bwd: contiguous fp32 tensors on one HIP device")
+        if tuple(a.shape) != (rows, out_f) or w.shape[0] != out_f:
+            raise PnError("pn_linear_bwd: g and a (rows, out_f), w (out_f, in_f)")
+        if gz is None:
+            gz = torch.empty((rows, out_f), dtype=g.dtype, device=g.device)
+        elif tuple(gz.shape) != (rows, out_f):
+            raise PnError("pn_linear_bwd: gz (rows, out_f)")
+        if dx is None:
+            dx = torch.empty((rows, in_f), dtype=g.dtype, device=g.device)
+        elif tuple(dx.shape) != (rows, in_f):
+            raise PnError("pn_linear_bwd: dx (rows, in_f)")
+        check(self.lib.pn_linear_bwd(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), gz.data_ptr(),
+                                     dx.data_ptr()))
+        return gz, dx
+
     # ---- dense output (-pn_output_times interpolate; csrc/pn_dense.hip)
     dense_flags = _lib.PN_DENSE_NONTEMPORAL      # output rows are not read again by the sweep: non-temporal stores
 

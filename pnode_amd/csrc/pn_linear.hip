@@ -271,7 +271,7 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-// The helpers every split-bf16 kernel of this file shares (the two wgrad forms below, pn_linear_fwd further down).
+// The helpers every split-bf16 kernel of this file shares (the two wgrad forms below, pn_linear_fwd and pn_linear_bwd further down).
 // Four fp32 values -> their three bf16 terms, packed four to a u32x2 in element order.
 struct Split3 {
   u32x2 hi, mid, lo;
@@ -786,8 +786,145 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_fwd_kernel_f32x3(FwdArgs a) { linear_fwd_body<false>(a); }
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_fwd_kernel_f32x3_ragged(FwdArgs a) { linear_fwd_body<true>(a); }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The backward of the same pair with respect to its input (pn_linear_bwd): for g, a rows x out, W out x in AS IT LIES,
+//   gz[r][k] = g[r][k] (1 - a[r][k]^2)      dx[r][n] = sum_k gz[r][k] W[k][n]
+// in ONE launch instead of an elementwise kernel and a library GEMM.  The sibling of linear_fwd_body: the same 64 x 128 tile of the
+// output over all of K (= out here) per workgroup of eight waves, the same slabs of 32 k through two LDS buffers, the same XCD rotation,
+// K halves, exchange at the end and ragged form; 36 KB per buffer as there.  What differs is where the operands come from:
+//   * A = gz is k-contiguous like the forward's x: a thread loads the f32x4 of g and of a, forms gz in fp32 in registers (1 - a a may
+//     contract to an fma), splits it into the [row][32 bf16] image (swz_row, ds_read_b128 fragments).  The workgroups of tile column 0
+//     also store that f32x4 to gz in HBM: every element of gz is written by exactly one workgroup -- the cotangent pn_linear_wgrad reads;
+//   * B = W is NOT k-contiguous: a slab is 32 rows k of W, 128 columns n, read along n (coalesced f32x4) and stored as two
+//     [32 k][64 bf16] images per part -- wgrad's layout (swz_tr) -- whose fragments are wgrad's transposed reads.  No transposed copy
+//     of W is kept anywhere: an optimiser changes W in place between two replays of a captured sweep.
+// Fixed order, no atomics, no work buffers: the same bits on every launch.  A NaN or Inf in g or a stays in its row of gz and dx (an
+// infinite gz gives NaN in its row of dx: inf - inf in the split, as an infinite W does in its columns); a == +-1 with finite g: gz == 0.
+struct BwdArgs {
+  const float *g, *a, *w;
+  float *gz, *dx;
+  int rows, out_f, in_f, ntn;
+};
+
+template <bool RAGGED>
+__device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
+  constexpr int AROWB = 2 * FK, APART = FM * AROWB;              // gz: [64 rows][32 bf16], 4 KB per part
+  constexpr int WROWB = 128, WIMG = FK * WROWB, WPART = 2 * WIMG;      // W: two [32 k][64 bf16] images, 8 KB per part
+  constexpr int BUF = 3 * APART + 3 * WPART;                     // 36 KB
+  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];    // 72 KB
+  const float *__restrict__ G = q.g;
+  const float *__restrict__ A = q.a;
+  const float *__restrict__ W = q.w;
+  const int rows = q.rows, out_f = q.out_f, in_f = q.in_f, ntn = q.ntn;
+  const int nblk = (int)gridDim.x, bid = (int)blockIdx.x;
+  const int tile = nblk % 8 == 0 ? (bid & 7) * (nblk >> 3) + (bid >> 3) : bid;
+  const int tm = tile / ntn, tn = tile % ntn;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int kh = w >> 2, wm = w & 1, wn = (w >> 1) & 1;          // K half; rows 32 wm .. + 31, columns 64 wn .. + 63 of the tile
+  const int lrow = t >> 3, lc = t & 7;                           // gz: row lrow of the tile, k 4 lc .. + 3 of the slab
+  const int krow = t >> 5, sub = (t >> 4) & 1, kc = t & 15;      // W: rows k krow and 16 + krow of the slab, columns 64 sub + 4 kc .. + 3 of the tile
+  const int nslab = out_f / FK;
+  const bool aok = !RAGGED || tm * FM + lrow < rows;
+  const bool wok = !RAGGED || tn * FN + sub * 64 + kc * 4 < in_f;
+  const bool keep = tn == 0 && aok;                              // this workgroup writes gz
+  const size_t aoff = (size_t)(tm * FM + lrow) * out_f + lc * 4;
+  const float *wp = W + (size_t)krow * in_f + tn * FN + sub * 64 + kc * 4;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 gv, av, wv0, wv1;
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc0[e] = 0.f, acc1[e] = 0.f;
+
+  auto gload = [&](int slab) {
+    gv = aok ? *reinterpret_cast<const f32x4 *>(G + aoff + slab * FK) : zero4;
+    av = aok ? *reinterpret_cast<const f32x4 *>(A + aoff + slab * FK) : zero4;
+    wv0 = wok ? *reinterpret_cast<const f32x4 *>(wp + (size_t)(slab * FK) * in_f) : zero4;
+    wv1 = wok ? *reinterpret_cast<const f32x4 *>(wp + (size_t)(slab * FK + 16) * in_f) : zero4;
+  };
+  const int aso = lrow * AROWB + (swz_row(lrow, lc >> 1) << 4) + ((lc & 1) << 3);
+  // (rows k krow and 16 + krow swap alike)
+  const int wso = sub * WIMG + krow * WROWB + swz_tr(krow, kc * 4) * 2;
+  auto split_store = [&](const f32x4 v, char *base, int part) {
+    const Split3 s = split3(v);
+    *reinterpret_cast<u32x2 *>(base) = s.hi;
+    *reinterpret_cast<u32x2 *>(base + part) = s.mid;
+    *reinterpret_cast<u32x2 *>(base + 2 * part) = s.lo;
+  };
+  auto lstore = [&](int slab, int buf) {
+    char *b = smem + buf * BUF;
+    f32x4 z;                                                     // here, not at the load: the products would wait for the loads in front of the MFMAs
+#pragma unroll
+    for (int e = 0; e < 4; ++e) z[e] = gv[e] * (1.f - av[e] * av[e]);
+    if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
+    split_store(z, b + aso, APART);
+    split_store(wv0, b + 3 * APART + wso, WPART);
+    split_store(wv1, b + 3 * APART + wso + 16 * WROWB, WPART);
+  };
+  // gz, lane l: row r0 + (l & 31), this wave's K half, k 8 (l >> 5) .. + 7 of it (linear_fwd_body::frag)
+  auto afrag = [&](const char *part, int r0) -> s16x8 {
+    const int row = r0 + (lane & 31);
+    return *reinterpret_cast<const s16x8 *>(part + row * AROWB + (swz_row(row, 2 * kh + (lane >> 5)) << 4));
+  };
+  // W, lane l: element [k = 8 (l >> 5) + j][col0 + (l & 31)] of this wave's K half of a [32 k][64] image, j = 0..7 (wgrad_body_x3::frag)
+  const int g4 = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
+  auto wfrag = [&](const char *img, int col0) -> s16x8 {
+    s16x4 r[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int k = kh * 16 + 8 * (g4 >> 1) + 4 * u + q4;
+      const int c = col0 + (g4 & 1) * 16 + 4 * p4;
+      r[u] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(img + k * WROWB + swz_tr(k, c) * 2));
+    }
+    const s16x8 f = {r[0][0], r[0][1], r[0][2], r[0][3], r[1][0], r[1][1], r[1][2], r[1][3]};
+    return f;
+  };
+  auto compute = [&](int buf) {
+    const char *ab = smem + buf * BUF, *wb = ab + 3 * APART + wn * WIMG;      // this wave's 64 columns: image wn
+    const s16x8 ah = afrag(ab, wm * 32), am = afrag(ab + APART, wm * 32), al = afrag(ab + 2 * APART, wm * 32);
+    {
+      const s16x8 bh = wfrag(wb, 0), bm = wfrag(wb + WPART, 0), bl = wfrag(wb + 2 * WPART, 0);
+      six_products(acc0, ah, am, al, bh, bm, bl);
+    }
+    {
+      const s16x8 bh = wfrag(wb, 32), bm = wfrag(wb + WPART, 32), bl = wfrag(wb + 2 * WPART, 32);
+      six_products(acc1, ah, am, al, bh, bm, bl);
+    }
+  };
+
+  gload(0);
+  lstore(0, 0);
+  if (nslab > 1) gload(1);
+  __syncthreads();
+  for (int s = 0; s < nslab; ++s) {
+    if (s + 1 < nslab) lstore(s + 1, (s + 1) & 1);    // the other buffer: its last readers passed the barrier of slab s - 1
+    compute(s & 1);
+    if (s + 2 < nslab) gload(s + 2);
+    __syncthreads();
+  }
+  // ---- the end, as the forward's: K half 0 finishes block 0 of its wave tile, K half 1 block 1; each hands the other its accumulator
+  float(*red)[64] = reinterpret_cast<float(*)[64]>(smem);
+  static_assert(sizeof(smem) >= 8 * 16 * 64 * sizeof(float), "the exchange is staged in the slab buffers");
+#pragma unroll
+  for (int e = 0; e < 16; ++e) red[w * 16 + e][lane] = kh == 0 ? acc1[e] : acc0[e];
+  __syncthreads();
+  const int col = tn * FN + wn * 64 + kh * 32 + (lane & 31);
+  const bool colok = !RAGGED || col < in_f;
+  const int row0 = tm * FM + wm * 32 + 4 * (lane >> 5);
+  float *dp = q.dx + (size_t)row0 * in_f + col;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const float other = red[(w ^ 4) * 16 + e][lane];
+    const float first = kh == 0 ? acc0[e] : other, second = kh == 0 ? other : acc1[e];
+    const int r = (e & 3) + 8 * (e >> 2);
+    if (colok && (!RAGGED || row0 + r < rows)) dp[(size_t)r * in_f] = first + second;
+  }
+}
+
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3(BwdArgs a) { linear_bwd_body<false>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true>(a); }
+
 int cu_count() {
-  static int n = 0;              // (the calling thread's current device; every device of a node is the same part)
+  static int n = 0;             // (the calling thread's current device; every device of a node is the same part)
   if (n == 0) {
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
@@ -911,6 +1048,39 @@ int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
   const bool ragged = rows % FM != 0 || out_f % FN != 0;
   return pn::launch("pn_linear_fwd", ragged ? pn_linear_fwd_kernel_f32x3_ragged : pn_linear_fwd_kernel_f32x3, dim3(blocks), dim3(kFwdThreads),
                     (hipStream_t)stream, a);
+}
+
+int pn_linear_bwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f) {
+  if (dtype != PN_F32) return 0;
+  const int64_t lim = (int64_t)1 << 30;
+  if (!(rows >= 256 && rows < lim && out_f > 0 && out_f < lim && out_f % 64 == 0 && in_f > 0 && in_f < lim && in_f % 64 == 0)) return 0;
+  return ((rows + FM - 1) / FM) * ((in_f + FN - 1) / FN) < lim ? 1 : 0;
+}
+
+int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, void *gz,
+                  void *dx) {
+  if (!pn_linear_bwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_bwd: unsupported dtype or shape (see pn_linear_bwd_supported)");
+  if (g == nullptr || a == nullptr || w == nullptr || gz == nullptr || dx == nullptr) return pn::fail("pn_linear_bwd: null operand");
+  if (!pn::aligned16(g, a, w, gz, dx)) return pn::fail("pn_linear_bwd: operands must be 16-byte aligned");
+  // an output that shares bytes with anything else the launch touches: other workgroups still read (or also write) them
+  const size_t nz = (size_t)rows * (size_t)out_f * sizeof(float), nw = (size_t)out_f * (size_t)in_f * sizeof(float),
+               nx = (size_t)rows * (size_t)in_f * sizeof(float);
+  auto overlap = [](const void *p, size_t np, const void *r, size_t nr) {
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), r0 = reinterpret_cast<uintptr_t>(r);
+    return p0 < r0 + nr && r0 < p0 + np;
+  };
+  if (overlap(gz, nz, g, nz) || overlap(gz, nz, a, nz) || overlap(gz, nz, w, nw))
+    return pn::fail("pn_linear_bwd: gz must not alias g, a or w (other workgroups still read them)");
+  if (overlap(dx, nx, g, nz) || overlap(dx, nx, a, nz) || overlap(dx, nx, w, nw) || overlap(dx, nx, gz, nz))
+    return pn::fail("pn_linear_bwd: dx must not alias g, a, w or gz");
+  BwdArgs q;
+  q.g = (const float *)g, q.a = (const float *)a, q.w = (const float *)w, q.gz = (float *)gz, q.dx = (float *)dx;
+  q.rows = (int)rows, q.out_f = (int)out_f, q.in_f = (int)in_f;
+  q.ntn = (int)((in_f + FN - 1) / FN);
+  const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)q.ntn;
+  const bool ragged = rows % FM != 0 || in_f % FN != 0;
+  return pn::launch("pn_linear_bwd", ragged ? pn_linear_bwd_kernel_f32x3_ragged : pn_linear_bwd_kernel_f32x3, dim3(blocks), dim3(kFwdThreads),
+                    (hipStream_t)stream, q);
 }
 
 }  // extern "C"

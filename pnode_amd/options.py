@@ -12,6 +12,10 @@ The engine's own options (``-pn_*``, no PETSc spelling) are read from the same d
 them.  ``-pn_linear_fwd auto|0|1`` (pnode_amd/_linearfwd.py, read in ``RKSweep._setup_linear_fwd``): ``auto``, the default, runs the
 eligible ``nn.Linear -> nn.Tanh`` pairs of func as one ``pn_linear_fwd`` launch each inside the solver's own evaluations; ``0`` runs
 the stock modules everywhere; ``1`` is ``auto`` and warns once, with the reason, about a pair that cannot be fused.
+``-pn_linear_bwd auto|0|1`` (read in the same place): ``auto``, the default, runs the backward of such a pair -- ``g_z = g (1 - a^2)``
+and ``dx = g_z W`` -- as one ``pn_linear_bwd`` launch; ``0`` runs ``tanh_backward`` and ``matmul`` by torch; ``1`` is ``auto`` and
+warns once with the reason a pair's backward runs through torch.  It has no effect where ``-pn_linear_fwd`` leaves the stock modules
+in place: the backward lives in the pair's ``autograd.Function``.
 """
 import os
 import shlex
