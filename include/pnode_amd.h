@@ -575,6 +575,25 @@ int pn_rows_tgrad_scatter_host(int64_t B, int nout, double *dtrow, const double 
                                double *held, int32_t *iv, int flush);
 int64_t pn_rows_tgrad_work_bytes(int64_t B, int nout);
 int pn_rows_tgrad_reduce(void *stream, int64_t B, int nout, const double *dtrow, double *dt, void *work);
+/* -pn_rows_compact 1: func is evaluated and differentiated on the rows of a round that have work to
+ * do.  The reference has no counterpart: its TSStep_RK evaluates func on the whole vector (ts.solve, pa.py:829).  Nothing
+ * here computes; values travel as bits (NaN payloads and -0.0 included).
+ * pn_rows_list: the ordered list of such rows.  kind 0, the open rows: src = the int32 `finished` row of si, row r is listed
+ * when src[r] == 0.  kind 1, the stepped rows: src = the fp64 h_eff row of a round's log_d, listed when src[r] > 0 (NaN is
+ * not).  Written: idx[0..m) = the listed rows in ascending order, idx[m..B) = -1, pos[r] = the place of row r in idx or -1,
+ * count[0] = m.  One workgroup; a row's place is the number of listed rows before it, so the list does not depend on
+ * scheduling.  `work` is not used (no arrival counters; may be NULL).  B <= 0x7fffff00.  pn_rows_list_host: the same list
+ * on host arrays (no device), the shared text of csrc/pn_adapt.h.
+ * pn_rows_gather: out[k] = src[idx[k]] for k < m, rows of d entries; a row with idx[k] < 0 is written as zeros and nothing
+ * is read for it.  m == 0 launches nothing.  d == 1 with PN_F64 gathers the rows' times.
+ * pn_rows_scatter: out[r] = pos[r] >= 0 ? src[pos[r]] : +0 for every r < B: every row of out is written, none is read (no
+ * atomics, no read-modify-write).  src == NULL: every row is +0.
+ * Both copy 16 bytes per access when d * sizeof(T) is a multiple of 16 and out and src are 16-byte aligned, else element by
+ * element; unprofiled, as the other row kernels are. */
+int pn_rows_list(void *stream, int64_t B, int kind, const void *src, int32_t *idx, int32_t *pos, int32_t *count, void *work);
+int pn_rows_list_host(int64_t B, int kind, const void *src, int32_t *idx, int32_t *pos, int32_t *count);
+int pn_rows_gather(void *stream, int dtype, int64_t m, int64_t d, void *out, const void *src, const int32_t *idx);
+int pn_rows_scatter(void *stream, int dtype, int64_t B, int64_t d, void *out, const void *src, const int32_t *pos);
 
 /* ------------------------------------------------------------------------------------------
  * 3b. GMRES core for the implicit (theta-method) stage solves: the small dense part of

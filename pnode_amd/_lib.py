@@ -105,6 +105,10 @@ PROTOTYPES = {
     "pn_rows_tgrad_scatter_host": (_i, [_i64, _i, _vp, _vp, _i, _pvp, _pd, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "pn_rows_tgrad_work_bytes": (_i64, [_i64, _i]),
     "pn_rows_tgrad_reduce": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
+    "pn_rows_list": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pn_rows_list_host": (_i, [_i64, _i, _vp, _vp, _vp, _vp]),
+    "pn_rows_gather": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp]),
+    "pn_rows_scatter": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp]),
     "pn_last_error": (_cp, []),
     "pn_abi_version": (_i, []),
     "pn_tableau_get": (_i, [_cp, ctypes.POINTER(Tableau)]),

@@ -83,10 +83,11 @@ class RKSweep(object):
         self.nfe_forward += 1
         return k
 
-    def _func_result(self, k, y_flat):
+    def _func_result(self, k, y_flat, numel=None):
         """func's result as both sweeps take it: refused unless it has the state's shape, dtype and device; flat, detached,
-        contiguous, and a copy when func returned (a view of) its input -- the input buffer is recycled."""
-        if k.dtype != self.tensor_dtype or k.device != self.device or k.numel() != self.n:
+        contiguous, and a copy when func returned (a view of) its input -- the input buffer is recycled.  `numel`: the entries
+        of the state func was called with, where that is a part of the batch (-pn_rows_compact 1)."""
+        if k.dtype != self.tensor_dtype or k.device != self.device or k.numel() != (self.n if numel is None else numel):
             raise ValueError("func must return a tensor with the state's shape, dtype and device")
         k = k.detach()
         if not k.is_contiguous():

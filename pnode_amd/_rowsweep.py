@@ -15,7 +15,13 @@ output" counter live on the device; the round's log grows by the range [lo, hi) 
 
 dL/dt (``t.requires_grad``, a backend with ``rows_tgrad``): every row's dL/dt is DESIGN.md section 5.6's rule on its own logged
 steps.  Per reversed round the rows' <w_j, K_j> and <w_j, df/dt> are gathered on the device and pn_rows_tgrad_scatter sends them
-into the row's own column of an fp64 [T][B] matrix (``sample_time_grads``); one ordered sum over the rows at the end is t.grad."""
+into the row's own column of an fp64 [T][B] matrix (``sample_time_grads``); one ordered sum over the rows at the end is t.grad.
+
+``-pn_rows_compact 1`` (a backend with ``rows_compact``): func is evaluated, and differentiated, on the rows of a round that have
+work to do -- forward the rows still unfinished at the round's start, backward the rows whose attempt was accepted (h_eff > 0).
+pn_rows_list writes the ordered list, pn_rows_gather packs the stage value, the times and the cotangent of those rows into a dense
+sub-batch of m <= B rows, pn_rows_scatter writes func's result (J^T w, <w, df/dt>) back into a full-size buffer whose other rows
+are +0.  Every pn_rows_* kernel of the step itself stays at full size."""
 import collections
 import ctypes
 import types
@@ -29,28 +35,42 @@ from ._lib import PN_ROWS_CACHED, PN_ROWS_H, PN_ROWS_REJ, PN_ROWS_SPANCTR, PN_RO
 _LOG_BLOCK = 64          # rounds per allocation of the round log
 
 # One round of the log, an entry per row in every field: h_eff, the time and the first-stage time at the round's start (`log_d`: the
-# packed [3][B] tensor of the three, as the entry points take it), the output the row landed on or -1, [2][B] the outputs [lo, hi) it interpolated
-_Round = collections.namedtuple("_Round", "heff t tfirst hit range log_d")
+# packed [3][B] tensor of the three, as the entry points take it), the output the row landed on or -1, [2][B] the outputs [lo, hi) it interpolated,
+# and under -pn_rows_compact 1 [2][B] the list of the rows with h_eff > 0 (idx, pos: what the reversed round gathers and scatters by)
+_Round = collections.namedtuple("_Round", "heff t tfirst hit range log_d lists")
 
 
 class _RoundLog(object):
-    """The rounds of a per-sample solve, allocated _LOG_BLOCK rounds at a time (the range block only with interpolated outputs)."""
+    """The rounds of a per-sample solve, allocated _LOG_BLOCK rounds at a time (the range block only with interpolated outputs, the
+    list block only where a reverse sweep under -pn_rows_compact 1 will read it).  `counts`: with lists, ONE device int32 array of
+    the lists' lengths, a round an entry (it doubles when it is full); the reverse sweep reads it once."""
 
-    def __init__(self, ops, B, ranges):
-        self._new = lambda: (ops.f64(_LOG_BLOCK, 3, B), ops.i32(_LOG_BLOCK, B), ops.i32(_LOG_BLOCK, 2, B) if ranges else None)
+    def __init__(self, ops, B, ranges, lists=False):
+        self._new = lambda: (ops.f64(_LOG_BLOCK, 3, B), ops.i32(_LOG_BLOCK, B), ops.i32(_LOG_BLOCK, 2, B) if ranges else None,
+                             ops.i32(_LOG_BLOCK, 2, B) if lists else None)
         self._blocks, self._n = [], 0
+        self._i32 = ops.i32
+        self.counts = ops.i32(_LOG_BLOCK) if lists else None
 
     def append(self):
         if self._n % _LOG_BLOCK == 0:
             self._blocks.append(self._new())
+        if self.counts is not None and self._n == self.counts.numel():
+            grown = self._i32(2 * self._n)
+            grown[: self._n] = self.counts
+            self.counts = grown
         self._n += 1
         return self[self._n - 1]
 
     def __getitem__(self, k):
-        log_d, hit, rng = self._blocks[k // _LOG_BLOCK]
+        log_d, hit, rng, lists = self._blocks[k // _LOG_BLOCK]
         i = k % _LOG_BLOCK
         d = log_d[i]
-        return _Round(d[0], d[1], d[2], hit[i], None if rng is None else rng[i], d)
+        return _Round(d[0], d[1], d[2], hit[i], None if rng is None else rng[i], d, None if lists is None else lists[i])
+
+
+# the rows a func call works on under -pn_rows_compact 1: m of them, idx their numbers in ascending order, pos the inverse
+_Sub = collections.namedtuple("_Sub", "m idx pos")
 
 
 class RowSweep(object):
@@ -61,6 +81,12 @@ class RowSweep(object):
     sample_steps = None
     sample_rejections = None
     sample_time_grads = None      # after a backward with t.requires_grad: fp64 [T][B], what row r sends to dL/dt_i (its sum over r is t.grad)
+    _compact = False              # -pn_rows_compact 1
+    # the rows passed to func, summed over the calls nfe_forward / nfe_backward count (from the solver's creation, as they are);
+    # without -pn_rows_compact 1 every call passes the B rows of the batch
+    rows_evaluated = 0
+    rows_evaluated_backward = 0
+    _rows_full = (0, 0)           # what the two would be with every call at full size
 
     # ------------------------------------------------------------------ surface
     def _rows_refusals(self):
@@ -82,6 +108,28 @@ class RowSweep(object):
             raise PnError("%s cannot be combined with -ts_trajectory_type basic" % opt)
         if isinstance(self.step_size, list):
             raise PnError("%s: a list step_size prescribes the steps of the whole batch; give one initial step size" % opt)
+        if self._compact and not getattr(self._ops, "rows_compact", False):
+            raise PnError("-pn_rows_compact 1 is not built on this backend (no pn_rows_list / pn_rows_gather / pn_rows_scatter); "
+                          "%s runs with -pn_rows_compact 0" % opt)
+
+    def _rows_compact_from_options(self, db):
+        """-pn_rows_compact 0|1 (not a PETSc option): 1 evaluates and differentiates func on the rows of a
+        round that have work to do.  Unknown pn_* keys are skipped by _set_from_options, so the value is checked here."""
+        val = str(db.get("pn_rows_compact", "0"))
+        if val not in ("0", "1"):
+            raise PnError("-pn_rows_compact must be 0 or 1 (got '%s')" % val)
+        self._compact = val == "1"
+        if self._compact and not self._sample:
+            raise PnError("-pn_rows_compact 1 needs -pn_adapt_scope sample: only a per-sample solve has rows that finish, or are "
+                          "rejected, on their own")
+
+    @property
+    def rows_compact(self):
+        """Status of -pn_rows_compact: "off", or the rows func was called with against what full-size calls would have passed."""
+        if not self._compact:
+            return "off"
+        return ("on (rows evaluated %d of %d forward, %d of %d backward)"
+                % (self.rows_evaluated, self._rows_full[0], self.rows_evaluated_backward, self._rows_full[1]))
 
     def _graph_entry(self, y0, t, need):
         if self._sample:
@@ -128,11 +176,26 @@ class RowSweep(object):
         return out
 
     # ------------------------------------------------------------------ helpers
-    def _rows_func(self, tvec, y_flat, tape=None):
+    def _rows_func(self, tvec, y_flat, tape=None, sub=None):
         """evalRHSFunction for the whole batch with per-row times; with `tape` (a list) recorded by autograd.  The time argument
-        of func: float64, one entry per row, broadcastable against the state."""
-        targ = tvec.view((self._rB,) + (1,) * (len(self.tensor_size) - 1))
-        y = self._shaped(y_flat)
+        of func: float64, one entry per row, broadcastable against the state.  With `sub` (-pn_rows_compact 1, fewer than B rows
+        have work to do) func sees those rows only, state (m, ...) and times (m, 1, ..., 1), and the result is a full-size buffer
+        whose other rows are +0; the tape is the sub-batch's."""
+        B, d = self._rB, self.n // self._rB
+        if sub is not None:
+            ops, m = self._ops, sub.m
+            y_full, y_flat = y_flat, ops.empty(m * d)
+            ops.rows_gather(m, d, y_flat, y_full, sub.idx)
+            t_full, tvec = tvec, tvec.new_empty(m)
+            ops.rows_gather(m, 1, tvec, t_full, sub.idx)
+            y = y_flat.view((m,) + tuple(self.tensor_size[1:]))
+        else:
+            m = B
+            y = self._shaped(y_flat)
+        targ = tvec.view((m,) + (1,) * (len(self.tensor_size) - 1))
+        back = tape is not None
+        self.rows_evaluated, self.rows_evaluated_backward = self.rows_evaluated + (0 if back else m), self.rows_evaluated_backward + (m if back else 0)
+        self._rows_full = (self._rows_full[0] + (0 if back else B), self._rows_full[1] + (B if back else 0))
         try:
             if tape is not None:
                 with torch.enable_grad():
@@ -159,19 +222,24 @@ class RowSweep(object):
                               % (type(exc).__name__, exc)) from exc
             raise
         self._rows_probe = False
-        return self._func_result(k, y_flat)
+        if sub is None:
+            return self._func_result(k, y_flat)
+        full = self._ops.empty(self.n)
+        self._ops.rows_scatter(B, d, full, self._func_result(k, y_flat, m * d), sub.pos)
+        return full
 
-    def _rows_stages(self, stages, Y, held, h, t, tfirst, tapes=None):
+    def _rows_stages(self, stages, Y, held, h, t, tfirst, tapes=None, sub=None):
         """K_i = f(t_r + c_i h_r, Y_i) for `stages` in order, the whole batch per call.  Y[0] is the round's state, evaluated at the rows'
         first-stage times; Y_i = u + h_r sum_j a_ij K_j is formed into Y[i] unless it is `held` there already.  With `tapes` (a dict)
-        the evaluations are the reverse sweep's, recorded by autograd: tapes[i] = (input, output, parameters)."""
+        the evaluations are the reverse sweep's, recorded by autograd: tapes[i] = (input, output, parameters).  `sub`: the rows func
+        is called with (_rows_func); the stage values are formed at full size all the same."""
         A, K = self._A, {}
         for i in stages:
             if i and i not in held:
                 idx = [j for j in range(i) if A[i][j] != 0.0]
                 self._ops.rows_stage(self._rB, self.n // self._rB, Y[i], Y[0], [K[j] for j in idx], [A[i][j] for j in idx], h)
             rec = None if tapes is None else []
-            K[i] = self._rows_func(t + self._c[i] * h if i else tfirst.clone(), Y[i], rec)
+            K[i] = self._rows_func(t + self._c[i] * h if i else tfirst.clone(), Y[i], rec, sub)
             if tapes is None:
                 self.nfe_forward += 1
             else:
@@ -202,11 +270,11 @@ class RowSweep(object):
                 raise Exception("TSSolve fails to step on all the specified points (-pn_adapt_scope sample: row %d)" % int(short[0]))
         if self._view and self.rounds:
             print("TS Object (pnode_amd): type rk, -pn_adapt_scope sample: %d rounds for %d rows, accepted steps per row %d..%d, "
-                  "rejected %d..%d; output times: %s; launches: %s"
+                  "rejected %d..%d; output times: %s; launches: %s%s"
                   % (self.rounds, st.B, int(self.sample_steps.min()), int(self.sample_steps.max()),
                      int(self.sample_rejections.min()), int(self.sample_rejections.max()),
                      "interpolate (per row, continuous extension of order %d)" % self._dense_order if st.dense is not None else "match",
-                     self._graph_status))
+                     self._graph_status, "; -pn_rows_compact: " + self.rows_compact if self._compact else ""))
         return st.solution
 
     def _rows_begin(self, u0, t, save):
@@ -237,7 +305,13 @@ class RowSweep(object):
         nt = len(times)
         check(lib.pn_ts_begin(ts, 0.0, float(self.step_size), nt, (ctypes.c_double * nt)(*times)))
         st.t0, st.tmax = (0.0 if nt == 1 else times[0]), times[-1]
-        self._round_log = _RoundLog(ops, B, st.dense is not None)
+        # -pn_rows_compact 1: the forward rounds' list of open rows (rewritten every round) and, where a reverse sweep follows, every
+        # round's list of stepped rows in the log
+        st.compact = self._compact
+        st.nopen = B
+        st.lists = ops.i32(2, B) if st.compact else None
+        st.nlist = ops.i32(1) if st.compact else None
+        self._round_log = _RoundLog(ops, B, st.dense is not None, st.compact and save)
         # the stage values of every round are kept for the reverse sweep, or live in scratch that every round rewrites
         st.store = save and not self._solution_only and not self._solution_only_auto
         self._rtraj, self._rY = ([] if save else None), ([] if st.store else None)
@@ -280,10 +354,18 @@ class RowSweep(object):
         unew = st.unew[k % 2]
         Y = [cur] + ([ops.empty(n) for _ in range(1, self._s_eff)] if st.store else st.scratch[1:self._s_eff])
         # (first same as last: the last stage value is the new state itself)
-        K = self._rows_stages(range(self._s), Y + [unew] if fsal else Y, (), h, tr, sd[PN_ROWS_TFIRST])
+        sub = None
+        if st.compact and st.nopen < B:
+            # the rows unfinished at this round's start: their number is what the last round's summary read back
+            ops.rows_list(B, 0, st.si[_lib.PN_ROWS_FINISHED], st.lists[0], st.lists[1], st.nlist)
+            sub = _Sub(st.nopen, st.lists[0], st.lists[1])
+        K = self._rows_stages(range(self._s), Y + [unew] if fsal else Y, (), h, tr, sd[PN_ROWS_TFIRST], None, sub)
         self._err_rows_combine(B, d, None if fsal else unew, unew if fsal else cur, [K[j] for j in st.ie],
                                [b[j] for j in st.ie], [e[j] for j in st.ie], h, st.enorm)
         ops.rows_control(self._ts, B, st.nspan, st.span, st.tmax, st.enorm, sd, st.si, log.log_d, log.hit, st.accept, st.summary)
+        if log.lists is not None:
+            # what the reversed round will work on: the rows this attempt moved (h_eff > 0); the count stays on the device
+            ops.rows_list(B, 1, log.heff, log.lists[0], log.lists[1], self._round_log.counts[k:k + 1])
         if st.save:
             nxt = ops.empty(n)
             self._rtraj.append(cur)
@@ -303,6 +385,7 @@ class RowSweep(object):
         st.cur = nxt
         self.rounds = k + 1
         nopen, frow, fcode = ops.rows_summary(st.summary)          # the one read-back of the round
+        st.nopen = nopen
         if frow >= 0:
             self._lib.pn_rows_failure(fcode, frow)
             raise PnError(self._lib.pn_last_error().decode())
@@ -334,6 +417,8 @@ class RowSweep(object):
         ld = g.stride(0)
         R = self.rounds
         tg = self._rows_tg_begin(T) if self._tgrad else None
+        # -pn_rows_compact 1: how many rows every round moved -- the one read-back of this sweep
+        moved = log.counts[:R].tolist() if log.counts is not None and R else None
         if R == 0:
             ops.rows_adj_accum(B, d, lam, lam, [], g, ld, ops.i32(B), T)
             self._rows_tg_end(tg)
@@ -347,8 +432,22 @@ class RowSweep(object):
             # the round's stage evaluations again, recorded by autograd: on the stage values the forward sweep kept, else on
             # ones recomputed from the round's state with the logged h_eff
             kept = self._rY[k] if self._rY is not None else [self._rtraj[k]]
+            sub = _Sub(moved[k], rnd.lists[0], rnd.lists[1]) if moved is not None and moved[k] < B else None
+            if sub is not None and sub.m == 0:
+                # every open row was rejected in this round: the identity on every row.  Nothing is evaluated or differentiated and
+                # the stage cotangents are zero; what is left is the forcing of the output the previous round landed on, and the
+                # dL/dt bookkeeping (every row has h_eff = 0: nothing is sent)
+                if tg is not None:
+                    tg.tbar = {}
+                    self._rows_tg_round(tg, rnd, g, None)
+                hit_prev = log[k - 1].hit if k > 0 else hit0
+                ops.rows_adj_accum(B, d, lam, lam, [], g if hit_prev is not None else None, ld, hit_prev, T)
+                self._rtraj[k] = None
+                if self._rY is not None:
+                    self._rY[k] = None
+                continue
             tapes = {}
-            K = self._rows_stages(stages, kept + rv.y[len(kept):], range(len(kept)), rnd.heff, rnd.t, rnd.tfirst, tapes)
+            K = self._rows_stages(stages, kept + rv.y[len(kept):], range(len(kept)), rnd.heff, rnd.t, rnd.tfirst, tapes, sub)
             if tg is not None:
                 tg.K, tg.first, tg.tbar = K, True, {}
             if dn is not None:
@@ -358,7 +457,7 @@ class RowSweep(object):
             for i in reversed(stages):
                 w = self._rows_cotangent(rv, i, dlam, rnd.heff)
                 if w is not None:
-                    dlam[i] = self._rows_vjp(tapes, i, w, tg)
+                    dlam[i] = self._rows_vjp(tapes, i, w, tg, sub)
             self._flush_param_accum()
             if tg is not None:
                 self._rows_tg_round(tg, rnd, g, K)
@@ -390,16 +489,36 @@ class RowSweep(object):
                                  [A[j][i] for j in js], heff, **kw)
         return rv.w
 
-    def _rows_vjp(self, tapes, i, w, tg=None):
+    def _rows_vjp(self, tapes, i, w, tg=None, sub=None):
         """The backward half of stage i with cotangent `w`: returns J^T w; the parameter cotangents are queued for mu.  With `tg`
         (this backward computes dL/dt) the rows' <w, K_i> are taken first -- the cotangent buffer is rewritten for the next
-        stage -- and the rows' times are one more input of autograd.grad: their gradient is <w, df/dt> per row."""
+        stage -- and the rows' times are one more input of autograd.grad: their gradient is <w, df/dt> per row.  With `sub` the tape
+        is the sub-batch's: the cotangent's rows are gathered for it, and J^T w and <w, df/dt> are scattered into full-size buffers of
+        their own (the other rows +0)."""
         y, out, wrt = tapes[i][:3]
         tt = () if tg is None else (tapes[i][3],)
         tapes[i] = None
         if tg is not None:
             self._ops.rows_tgrad_dots(self._rB, self.n // self._rB, tg.rowacc, [w], [tg.K[i]], [1.0], accumulate=not tg.first)
             tg.first = False
+        if sub is not None:
+            ops, B, d = self._ops, self._rB, self.n // self._rB
+            wc = ops.empty(sub.m * d)
+            ops.rows_gather(sub.m, d, wc, w, sub.idx)
+            grads = torch.autograd.grad(out, (y,) + tuple(wrt) + tt, wc.view(out.shape), allow_unused=True)
+            if tt:
+                gt, grads = grads[-1], grads[:-1]
+                if gt is not None:
+                    tg.tbar[i] = gt.new_empty(B, dtype=torch.float64)
+                    ops.rows_scatter(B, 1, tg.tbar[i], gt.to(torch.float64).contiguous().reshape(-1), sub.pos)
+            # (the gathered cotangent is this stage's alone and is not rewritten: nothing that shares its storage needs a copy)
+            gc, gp = self._vjp_results(grads[0], grads[1:], wc, deferred=False)
+            gy = None
+            if gc is not None:
+                gy = ops.empty(self.n)
+                ops.rows_scatter(B, d, gy, gc, sub.pos)
+            self._take_param_grads(1.0, gp)
+            return gy
         grads = torch.autograd.grad(out, (y,) + tuple(wrt) + tt, self._shaped(w).view(out.shape), allow_unused=True)
         if tt:
             gt, grads = grads[-1], grads[:-1]
@@ -425,7 +544,7 @@ class RowSweep(object):
         """A reversed round's share of dL/dt, once its stage VJPs have run: the interpolated outputs' e_o, then the scatter into the
         rows' columns of dtrow (pn_rows_dense_tgrad, pn_rows_tgrad_scatter)."""
         ops, B, dn = self._ops, self._rB, self._rdense
-        if dn is not None:
+        if dn is not None and K is not None:         # (K None: no row moved in this round, no output of it was interpolated)
             ops.rows_dense_tgrad(B, self.n // B, tg.erow, g, [K[j] for j in dn.cols], dn.times, dn.P, rnd.range, rnd.log_d)
         own = [j for j in sorted(tg.tbar) if not (self._fsal and j == 0)]
         ops.rows_tgrad_scatter(B, tg.dtrow, tg.rowacc, [tg.tbar[j] for j in own], [self._c[j] for j in own],

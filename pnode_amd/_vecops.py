@@ -411,6 +411,23 @@ class HipVecOps(object):
             w = self._rows_tg_work = torch.zeros(need // 8, dtype=torch.float64, device=self.device)
         check(self.lib.pn_rows_tgrad_reduce(self.stream(), B, T, dtrow.data_ptr(), dt.data_ptr(), w.data_ptr()))
 
+    # ... and -pn_rows_compact 1: func sees the rows of a round that have work to do
+    rows_compact = True
+
+    def rows_list(self, B, kind, src, idx, pos, count):
+        """The ordered list of the rows with work to do (pn_rows_list): kind 0, `src` the int32 `finished` row of si (listed: 0);
+        kind 1, `src` the fp64 h_eff row of a round's log (listed: > 0).  idx, pos: int32 [B]; count: int32, one entry."""
+        check(self.lib.pn_rows_list(self.stream(), B, kind, src.data_ptr(), idx.data_ptr(), pos.data_ptr(), count.data_ptr(), None))
+
+    def rows_gather(self, m, d, out, src, idx):
+        """out[k] = src[idx[k]] for k < m, rows of d entries of out's dtype (pn_rows_gather)."""
+        check(self.lib.pn_rows_gather(self.stream(), _lib.dtype_code(out.dtype), m, d, out.data_ptr(), src.data_ptr(), idx.data_ptr()))
+
+    def rows_scatter(self, B, d, out, src, pos):
+        """out[r] = src[pos[r]] where pos[r] >= 0, else +0, for every r < B (pn_rows_scatter)."""
+        check(self.lib.pn_rows_scatter(self.stream(), _lib.dtype_code(out.dtype), B, d, out.data_ptr(),
+                                       src.data_ptr() if src.numel() else None, pos.data_ptr()))
+
     def rows_adj_accum(self, B, d, lam_out, lam, dlams, g, ld, hit, nout):
         check(self.lib.pn_rows_adj_accum(self.stream(), self.code, B, d, lam_out.data_ptr(), lam.data_ptr(), len(dlams),
                                          self._ptrs(dlams), None if g is None else g.data_ptr(), ld,

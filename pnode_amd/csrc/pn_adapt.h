@@ -378,6 +378,30 @@ PN_HD void pn_rows_tgrad_scatter_row(const PnRowsTgScatter &a, int64_t B, int64_
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// -pn_rows_compact 1: which rows of a round have work to do, and the ordered list of them (pn_rows_list on the device,
+// pn_rows_list_host on host arrays).  kind 0, the open rows: `src` is the int32 PN_ROWS_FINISHED row of si and a row is listed
+// when its entry is 0.  kind 1, the stepped rows: `src` is the fp64 h_eff row of a round's log and a row is listed when its
+// entry is > 0 (a NaN is not).  The list is the listed row numbers in ascending order: idx[0..m), -1 behind them up to B;
+// pos[r] is row r's place in idx or -1; count[0] = m.  The device forms the same list from the same predicate, every row's
+// place being the number of listed rows before it.
+// ------------------------------------------------------------------------------------------
+PN_HD bool pn_rows_listed(int kind, const void *src, int64_t r) {
+  if (kind == 0) return static_cast<const int32_t *>(src)[r] == 0;
+  return static_cast<const double *>(src)[r] > 0.0;
+}
+
+inline void pn_rows_list_rows(int kind, const void *src, int64_t B, int32_t *idx, int32_t *pos, int32_t *count) {
+  int32_t m = 0;
+  for (int64_t r = 0; r < B; ++r) {
+    const bool on = pn_rows_listed(kind, src, r);
+    pos[r] = on ? m : -1;
+    if (on) idx[m++] = (int32_t)r;
+  }
+  for (int64_t k = m; k < B; ++k) idx[k] = -1;
+  count[0] = m;
+}
+
 namespace pn {
 // the controller constants of `ts` and what the row controllers need of its tableau (pn_ts.cpp)
 void rows_ctl_config(const pn_ts *ts, int nspan, double max_time, PnRowsCtl *out);

@@ -126,14 +126,15 @@ __device__ __forceinline__ void load_chunk(const T *row, int64_t c, int64_t d, T
 }
 // (vector path: stored non-temporally, the policy pn_lincomb_kernel / pn_combine_wrms_kernel run with by default -- the
 // outputs are not read again before func has run)
-template <typename T, bool VEC>
+// (ST = 0, plain stores: the row copies around func below, whose outputs func or autograd reads next)
+template <typename T, bool VEC, int ST = 1>
 __device__ __forceinline__ void store_chunk(T *row, int64_t c, int64_t d, const T (&v)[16 / sizeof(T)]) {
   constexpr int VW = 16 / sizeof(T);
   if (VEC) {
     Vec<T, VW> x;
 #pragma unroll
     for (int e = 0; e < VW; ++e) x[e] = v[e];
-    pn_store<1>(reinterpret_cast<Vec<T, VW> *>(row) + c, x);
+    pn_store<ST>(reinterpret_cast<Vec<T, VW> *>(row) + c, x);
   } else {
 #pragma unroll
     for (int e = 0; e < VW; ++e) {
@@ -711,6 +712,96 @@ __global__ __launch_bounds__(kBlock) void pn_rows_tgrad_reduce_kernel(const doub
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// -pn_rows_compact 1: the ordered list of the rows with work to do, and the two row copies that carry
+// func's operands into a dense sub-batch and its results back.  Nothing here computes: values travel as bits.
+// ------------------------------------------------------------------------------------------
+// The list.  ONE workgroup of kListBlock threads; wave w owns the contiguous rows [w*seg, (w+1)*seg), seg a multiple of 64.
+// Pass 1: every wave counts its listed rows, 64 rows a step (a ballot and a population count: no shuffles, no LDS).  One
+// barrier; a wave's first place is the sum of the counts of the waves before it.  Pass 2: the wave walks its rows again;
+// a listed row's place is the wave's running offset plus the listed lanes below it.  Places depend on the row numbers
+// alone -- never on which wave ran first -- so idx is ascending and two launches write the same bytes; no atomics, no
+// hand-off between workgroups, no work area.  Places written are < m, the -1 tail is >= m: the two never meet.
+constexpr int kListBlock = 1024;
+
+__global__ __launch_bounds__(kListBlock) void pn_rows_list_kernel(int kind, const void *src, int64_t B, int32_t *idx, int32_t *pos,
+                                                                  int32_t *count) {
+  constexpr int kWaves = kListBlock / kWave;
+  __shared__ int s_cnt[kWaves];
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  const int64_t seg = ((B + kWaves - 1) / kWaves + kWave - 1) / kWave * kWave;
+  const int64_t lo = (int64_t)wid * seg;
+  const int64_t hi = lo + seg < B ? lo + seg : B;
+  int cnt = 0;
+  for (int64_t r0 = lo; r0 < hi; r0 += kWave) {
+    const int64_t r = r0 + lane;
+    const bool on = r < hi && pn_rows_listed(kind, src, r);
+    cnt += __popcll(__ballot(on));
+  }
+  if (lane == 0) s_cnt[wid] = cnt;
+  __syncthreads();
+  int off = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    const int c = s_cnt[w];
+    off += w < wid ? c : 0;
+    total += c;
+  }
+  for (int64_t r0 = lo; r0 < hi; r0 += kWave) {
+    const int64_t r = r0 + lane;
+    const bool on = r < hi && pn_rows_listed(kind, src, r);
+    const unsigned long long mask = __ballot(on);
+    if (r < hi) {
+      const int p = on ? off + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+      pos[r] = p;
+      if (on) idx[p] = (int32_t)r;
+    }
+    off += __popcll(mask);
+  }
+  for (int64_t k = (int64_t)total + threadIdx.x; k < B; k += kListBlock) idx[k] = -1;
+  if (threadIdx.x == 0) count[0] = total;
+}
+
+// out[k] = src[idx[k]] for the m rows of `out` (a row with idx[k] < 0 is written as zeros and nothing is read for it)
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void pn_rows_gather_kernel(T *out, const T *src, const int32_t *idx, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t k = (int64_t)blockIdx.x * rpb + sub; k < q.B; k += (int64_t)gridDim.x * rpb) {
+    const int64_t from = idx[k];
+    for (int64_t ch = g; ch < q.nch; ch += G) {
+      T v[VW];
+      if (from >= 0) {
+        load_chunk<T, VEC>(src + from * q.d, ch, q.d, v);
+      } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) v[e] = (T)0;
+      }
+      store_chunk<T, VEC, 0>(out + k * q.d, ch, q.d, v);
+    }
+  }
+}
+
+// out[r] = pos[r] >= 0 ? src[pos[r]] : +0 for all B rows of `out`: every row is written, none is read
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void pn_rows_scatter_kernel(T *out, const T *src, const int32_t *pos, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r = (int64_t)blockIdx.x * rpb + sub; r < q.B; r += (int64_t)gridDim.x * rpb) {
+    const int64_t from = src ? pos[r] : -1;
+    for (int64_t ch = g; ch < q.nch; ch += G) {
+      T v[VW];
+      if (from >= 0) {
+        load_chunk<T, VEC>(src + from * q.d, ch, q.d, v);
+      } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) v[e] = (T)0;
+      }
+      store_chunk<T, VEC, 0>(out + r * q.d, ch, q.d, v);
+    }
+  }
+}
+
 template <typename T>
 RowsGeom geom(int64_t B, int64_t d) {
   constexpr int VW = 16 / sizeof(T);
@@ -929,6 +1020,17 @@ int rows_dense_tgrad(hipStream_t st, int64_t B, int64_t d, const void *g, int64_
   return pn::or_fail(rc, "pn_rows_dense_tgrad: nk out of range");
 }
 
+// the two row copies of -pn_rows_compact: `rows` rows of `out` are written; unprofiled, as pn_rows_stage / pn_rows_commit are
+template <typename T, bool GATHER>
+int rows_copy(const char *name, hipStream_t st, int64_t rows, int64_t d, void *out, const void *src, const int32_t *map) {
+  constexpr int VW = 16 / sizeof(T);
+  const bool vec = (d % VW) == 0 && pn::aligned16(out, src);
+  const RowsGeom q = geom<T>(rows, d);
+  auto kern = GATHER ? (vec ? pn_rows_gather_kernel<T, true> : pn_rows_gather_kernel<T, false>)
+                     : (vec ? pn_rows_scatter_kernel<T, true> : pn_rows_scatter_kernel<T, false>);
+  return pn::launch(name, kern, grid_for(q), dim3(kBlock), st, (T *)out, (const T *)src, map, q);
+}
+
 int tgrad_reduce_blocks(int64_t B) { return (int)pn::blocks_for(B, kBlock, kTgReduceBlocks); }
 
 int bad_shape(const char *name, int64_t B, int64_t d) {
@@ -1099,6 +1201,39 @@ int pn_rows_dense_plan_host(int64_t B, int nout, const double *times, const doub
       for (int j = 0; j < nk; ++j) coef[((int64_t)o * B + r) * nk + j] = pn_rows_dense_coef(P + j * PN_DENSE_MAX_POW, times[o], tr, h);
   }
   return 0;
+}
+
+/* -pn_rows_compact 1: the ordered list of the rows with work to do (one workgroup; `work` is not used: the list needs no
+ * arrival counters) and the row copies around func. */
+int pn_rows_list(void *stream, int64_t B, int kind, const void *src, int32_t *idx, int32_t *pos, int32_t *count, void *work) {
+  (void)work;
+  if (B < 1 || B > 0x7fffff00 || (kind != 0 && kind != 1) || !src || !idx || !pos || !count)
+    return pn::fail("pn_rows_list: null argument, B not positive or kind outside 0..1");
+  return pn::launch("pn_rows_list", pn_rows_list_kernel, dim3(1), dim3(kListBlock), (hipStream_t)stream, kind, src, B, idx, pos, count);
+}
+
+int pn_rows_list_host(int64_t B, int kind, const void *src, int32_t *idx, int32_t *pos, int32_t *count) {
+  if (B < 1 || B > 0x7fffff00 || (kind != 0 && kind != 1) || !src || !idx || !pos || !count)
+    return pn::fail("pn_rows_list_host: null argument, B not positive or kind outside 0..1");
+  pn_rows_list_rows(kind, src, B, idx, pos, count);
+  return 0;
+}
+
+int pn_rows_gather(void *stream, int dtype, int64_t m, int64_t d, void *out, const void *src, const int32_t *idx) {
+  if (m == 0) return 0;
+  if (bad_shape("pn_rows_gather", m, d)) return 1;
+  if (!out || !src || !idx) return pn::fail("pn_rows_gather: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_copy<decltype(t), true>("pn_rows_gather", st, m, d, out, src, idx); });
+  return pn::or_fail(rc, "pn_rows_gather: unknown dtype");
+}
+
+int pn_rows_scatter(void *stream, int dtype, int64_t B, int64_t d, void *out, const void *src, const int32_t *pos) {
+  if (bad_shape("pn_rows_scatter", B, d)) return 1;
+  if (!out || !pos) return pn::fail("pn_rows_scatter: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_copy<decltype(t), false>("pn_rows_scatter", st, B, d, out, src, pos); });
+  return pn::or_fail(rc, "pn_rows_scatter: unknown dtype");
 }
 
 int pn_rows_tgrad_dots(void *stream, int dtype, int64_t B, int64_t d, int np, const void *const *x, const void *const *y,

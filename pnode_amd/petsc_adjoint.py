@@ -449,6 +449,7 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs, ErrorNorm):
         self._sample = sc == "sample"
         if self._sample:
             self._graph_status = "eager (-pn_adapt_scope sample: the rounds of a per-sample solve are launched eagerly)"
+        self._rows_compact_from_options(db)
         for key, val in db.items():
             if key.startswith("ts_trajectory") or key in ("ts_monitor", "ts_view") or key.startswith("pn_"):
                 continue
