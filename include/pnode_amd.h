@@ -240,6 +240,14 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
 int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
 int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
                   void *y);
+/* The K loop of pn_linear_fwd and pn_linear_bwd has two forms with the same bits in every output: the PIPELINED one (three LDS buffers,
+ * two sets of fragment registers: the MFMAs of a slab run while the next slab's fragments are read and the one after it is split and
+ * stored) that aligned shapes -- rows % 64 == 0 and the output's columns % 128 == 0 -- take by themselves, and the PLAIN one, which
+ * ragged shapes always take.  pn_linear_fwd_form / pn_linear_bwd_form are pn_linear_fwd / pn_linear_bwd with `flags`: 0, or
+ * PN_LINEAR_FORM_PLAIN for the plain loop on an aligned shape too (for comparisons); any other bit is refused. */
+#define PN_LINEAR_FORM_PLAIN 1
+int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b,
+                       int act, void *y, int flags);
 
 /* The backward of such a pair with respect to its input in one launch (csrc/pn_linear.hip): for g (the cotangent at the pair's output)
  * and a (the pair's output, tanh of the biased sum) rows x out_f, w out_f x in_f AS IT LIES (no transposed copy is read or kept: an
@@ -256,6 +264,8 @@ int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
 int pn_linear_bwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
 int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, void *gz,
                   void *dx);
+int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w,
+                       void *gz, void *dx, int flags);
 
 /* result_dev[j] = <x, y_j> for j < nk <= PN_MAX_TERMS, accumulated in double, reduced in a fixed
  * order (bit-reproducible).  ||x||^2 is the case y_0 == x.  Replaces VecMDot / VecNorm inside

@@ -46,6 +46,7 @@ PN_WGRAD_MAX_PAIRS = 8
 PN_WGRAD_EXACT_FP32 = 1
 PN_WGRAD_TILE_64 = 2
 PN_ACT_IDENTITY, PN_ACT_TANH = 0, 1
+PN_LINEAR_FORM_PLAIN = 1      # pn_linear_fwd_form / pn_linear_bwd_form flag: the plain K loop on an aligned shape too
 PN_ABI_VERSION = 4
 PN_DENSE_MAX_POW = 4          # columns of a continuous extension's P matrix (pn_tableau_dense)
 PN_DENSE_CHUNK = 32           # output rows per launch of pn_rk_dense_eval / pn_rk_dense_adjoint
@@ -142,8 +143,10 @@ PROTOTYPES = {
     "pn_linear_wgrad_finish": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pn_linear_fwd_supported": (_i, [_i, _i64, _i64, _i64]),
     "pn_linear_fwd": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp]),
+    "pn_linear_fwd_form": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp, _i]),
     "pn_linear_bwd_supported": (_i, [_i, _i64, _i64, _i64]),
     "pn_linear_bwd": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "pn_linear_bwd_form": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i]),
     "pn_colsum_accum": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _d, _vp]),
     "pn_colsum_accum_multi": (_i, [_vp, _i, _i, _pi64, _pi64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _pd, _vp]),
     "pn_colsum_work_bytes": (_i64, [_i, _pi64, _pi64]),

@@ -923,10 +923,15 @@ class RKSweep(object):
         mode = "auto" if mode == "auto" else ("1" if options.truthy(mode, False) else "0")
         bwd = str(options.get_all().get("pn_linear_bwd", "auto"))
         bwd = "auto" if bwd == "auto" else ("1" if options.truthy(bwd, False) else "0")
+        # -pn_linear_form auto|plain: `plain` keeps the plain K loop of both kernels on aligned shapes too (PN_LINEAR_FORM_PLAIN; the
+        # same bits as the pipelined loop they take by themselves) -- for comparisons inside one tree
+        form = options.linear_form()
+        if hasattr(self._ops, "linear_flags"):
+            self._ops.linear_flags = _lib.PN_LINEAR_FORM_PLAIN if form == "plain" else 0
         from ._linearfwd import LinearFwd
         on = mode != "0" and self._stepper_kind in (None, "imex") and self.device.type == LinearFwd.device_type \
             and self.tensor_dtype == torch.float32 and hasattr(self._ops, "linear_fwd")
-        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd)
+        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form)
         if sig == self._fwd_sig:
             return
         self._fwd_sig = sig

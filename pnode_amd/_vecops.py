@@ -224,9 +224,11 @@ class HipVecOps(object):
     def linear_fwd_supported(self, rows, out_f, in_f):
         return bool(self.lib.pn_linear_fwd_supported(self.code, rows, out_f, in_f))
 
-    def linear_fwd(self, x, w, b, tanh, y=None):
+    linear_flags = 0           # PN_LINEAR_FORM_PLAIN with -pn_linear_form plain: the K loop of linear_fwd / linear_bwd (the same bits)
+
+    def linear_fwd(self, x, w, b, tanh, y=None, flags=None):
         """y = act(x w^T + b), act = tanh or the identity; x (rows, in_f), w (out_f, in_f), b (out_f,) or None: contiguous fp32 on this device.
-        Refused (PnError), never run another way, outside pn_linear_fwd_supported."""
+        Refused (PnError), never run another way, outside pn_linear_fwd_supported.  flags: pn_linear_fwd_form's (default: linear_flags)."""
         rows, in_f = x.shape
         out_f = w.shape[0]
         for v in (x, w, b, y):
@@ -238,17 +240,19 @@ class HipVecOps(object):
             y = torch.empty((rows, out_f), dtype=x.dtype, device=x.device)
         elif tuple(y.shape) != (rows, out_f):
             raise PnError("pn_linear_fwd: y (rows, out_f)")
-        check(self.lib.pn_linear_fwd(self.stream(), _lib.dtype_code(x.dtype), rows, out_f, in_f, x.data_ptr(), w.data_ptr(),
-                                     None if b is None else b.data_ptr(), _lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY, y.data_ptr()))
+        check(self.lib.pn_linear_fwd_form(self.stream(), _lib.dtype_code(x.dtype), rows, out_f, in_f, x.data_ptr(), w.data_ptr(),
+                                          None if b is None else b.data_ptr(), _lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY, y.data_ptr(),
+                                          self.linear_flags if flags is None else flags))
         return y
 
     # ---- the backward of a Linear -> Tanh pair with respect to its input (pn_linear_bwd, csrc/pn_linear.hip)
     def linear_bwd_supported(self, rows, out_f, in_f):
         return bool(self.lib.pn_linear_bwd_supported(self.code, rows, out_f, in_f))
 
-    def linear_bwd(self, g, a, w, gz=None, dx=None):
+    def linear_bwd(self, g, a, w, gz=None, dx=None, flags=None):
         """(gz, dx) = (g (1 - a^2), gz w); g, a (rows, out_f), w (out_f, in_f): contiguous fp32 on this device.  Refused (PnError), never
-        run another way, outside pn_linear_bwd_supported, for an fp64 state, and where gz or dx shares memory with an input."""
+        run another way, outside pn_linear_bwd_supported, for an fp64 state, and where gz or dx shares memory with an input.
+        flags: pn_linear_bwd_form's (default: linear_flags)."""
         rows, out_f = g.shape
         in_f = w.shape[1]
         for v in (g, a, w, gz, dx):
@@ -264,8 +268,8 @@ class HipVecOps(object):
             dx = torch.empty((rows, in_f), dtype=g.dtype, device=g.device)
         elif tuple(dx.shape) != (rows, in_f):
             raise PnError("pn_linear_bwd: dx (rows, in_f)")
-        check(self.lib.pn_linear_bwd(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), gz.data_ptr(),
-                                     dx.data_ptr()))
+        check(self.lib.pn_linear_bwd_form(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), gz.data_ptr(),
+                                          dx.data_ptr(), self.linear_flags if flags is None else flags))
         return gz, dx
 
     # ---- dense output (-pn_output_times interpolate; csrc/pn_dense.hip)

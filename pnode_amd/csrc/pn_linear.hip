@@ -663,6 +663,93 @@ __global__ __launch_bounds__(256) void pn_linear_bgrad_finish_kernel(double *__r
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The PIPELINED K loop of pn_linear_fwd / pn_linear_bwd on aligned shapes (the plain loops further down stay: the ragged bodies, and
+// PN_LINEAR_FORM_PLAIN).  The plain loop runs three phases per slab that all eight waves enter together after the barrier -- split and
+// store of the next slab (VALU), fragment reads (LDS latency, exposed), twelve MFMAs -- and the matrix pipe idles through the first two.
+// Here every wave keeps TWO sets of fragment registers and TWO sets of load registers, and the slabs go through THREE LDS buffers.
+// Step s, between two barriers:
+//   * global loads of slab s + 3 are issued (they have two steps to arrive);
+//   * the fragments of slab s + 1 are read from buffer (s + 1) % 3 into the set the MFMAs of slab s - 1 have left;
+//   * the twelve MFMAs of slab s run from the set read one step ago -- no LDS read stands in front of an MFMA;
+//   * slab s + 2 is split and stored to buffer (s + 2) % 3, spread between the MFMAs (__builtin_amdgcn_sched_group_barrier: per MFMA
+//     one or two fragment reads, eight VALU, one ds_write_b64).
+// What orders LDS: a buffer is read one step after the barrier that follows its stores, and stored again two steps after the barrier
+// that follows its reads (__syncthreads waits for this wave's LDS operations before it signals) -- no read or store is ordered by
+// anything but a barrier.  Every accumulator takes exactly the MFMAs of the plain loop in its order (slabs ascending, six_products,
+// acc0 before acc1 is immaterial: they are separate chains), so the results are the plain loop's bit for bit.
+struct Frags {                   // one slab's operand fragments of a wave: A (hi, mid, lo), B of accumulator 0, B of accumulator 1
+  s16x8 ah, am, al, b0h, b0m, b0l, b1h, b1m, b1l;
+};
+
+template <int I, int NREAD, int RPG, bool RD, bool ST>
+__device__ __forceinline__ void pipe_groups() {
+  if constexpr (I < 12) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          // one MFMA
+    constexpr int left = NREAD - I * RPG, nr = left < 0 ? 0 : (left < RPG ? left : RPG);
+    if constexpr (ST) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);        // the split's VALU work
+    if constexpr (RD && nr > 0) __builtin_amdgcn_sched_group_barrier(0x100, nr, 0);      // fragment reads of the next slab
+    if constexpr (ST) {
+      // its LDS stores (the nine ds_write_b64 of a thread leave the compiler as five: pairs a part apart go as ds_write2st64_b64)
+      if constexpr (I >= 3 && (I & 1)) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+    }
+    pipe_groups<I + 1, NREAD, RPG, RD, ST>();
+  }
+}
+
+// NREAD: LDS read instructions per slab and wave (9 ds_read_b128 forward; 3 + 12 transposed ones backward); NLOAD: global loads per slab
+// and thread.  gload(G &, slab), lstore(const G &, slab, byte offset of the buffer), read(Frags &, byte offset of the buffer).
+// nslab is even and >= 2.
+template <int NREAD, int NLOAD, typename G, typename GL, typename LS, typename RF>
+__device__ __forceinline__ void pipelined_slabs(const int nslab, const int BUF, f32x16 &acc0, f32x16 &acc1, GL gload, LS lstore, RF read) {
+  constexpr int RPG = NREAD > 12 ? 2 : 1;
+  G g0, g1;
+  Frags f0, f1;
+  int rb = BUF, wb = 2 * BUF, fb = 0;            // step s reads slab s + 1 from rb and stores slab s + 2 to wb
+  // step s: loads slab s + 3 into gnxt, reads slab s + 1 into nxt, multiplies slab s from cur, splits and stores slab s + 2 from gcur
+  auto step = [&](auto ld, auto rd, auto st, const Frags &cur, Frags &nxt, const G &gcur, G &gnxt, int s) {
+    constexpr bool LD = decltype(ld)::value, RD = decltype(rd)::value, ST = decltype(st)::value;
+    if constexpr (LD) gload(gnxt, s + 3);
+    if constexpr (RD) read(nxt, rb);
+    if constexpr (ST) lstore(gcur, s + 2, wb);
+    six_products(acc0, cur.ah, cur.am, cur.al, cur.b0h, cur.b0m, cur.b0l);
+    six_products(acc1, cur.ah, cur.am, cur.al, cur.b1h, cur.b1m, cur.b1l);
+    if constexpr (LD) {                          // the global loads first, behind their addresses: they have two steps to arrive
+      __builtin_amdgcn_sched_group_barrier(0x002, 2 * NLOAD, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, NLOAD, 0);
+    }
+    pipe_groups<0, NREAD, RPG, RD, ST>();
+    // nothing of a step moves across its barrier: the MFMAs of the next step would wait for fragments that were read just now
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    const int r = rb;
+    rb = wb, wb = fb, fb = r;
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  gload(g0, 0);
+  gload(g1, 1);
+  lstore(g0, 0, 0);
+  if (nslab > 2) gload(g0, 2);
+  lstore(g1, 1, BUF);
+  __syncthreads();
+  read(f0, 0);
+  __builtin_amdgcn_sched_barrier(0);
+  int s = 0;
+  for (; s + 4 < nslab; s += 2) {
+    step(yes, yes, yes, f0, f1, g0, g1, s);
+    step(yes, yes, yes, f1, f0, g1, g0, s + 1);
+  }
+  if (nslab >= 4) {                              // s == nslab - 4: the last two stores, the last load
+    step(yes, yes, yes, f0, f1, g0, g1, s);
+    step(no, yes, yes, f1, f0, g1, g0, s + 1);
+    s += 2;
+  }
+  step(no, yes, no, f0, f1, g0, g1, s);          // s == nslab - 2
+  step(no, no, no, f1, f0, g1, g0, s + 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // The forward product of a Linear layer with its activation: Y = act(X W^T + b), X rows x in, W out x in, Y rows x out, row-major
 // fp32 (pn_linear_fwd) -- func's Linear -> Tanh pairs in ONE launch instead of a library GEMM and an elementwise kernel.
 // The arithmetic is the split-bf16 product above (split3, six_products).  What differs from wgrad is the shape: K = in is short
@@ -687,10 +774,16 @@ struct FwdArgs {
   int rows, out_f, in_f, act, ntn;
 };
 
-template <bool RAGGED>
+struct FwdLoads {                // one slab's global loads of a thread
+  f32x4 x, w0, w1;
+};
+
+// PIPE: the pipelined K loop (pipelined_slabs above; aligned shapes only), else the plain one
+template <bool RAGGED, bool PIPE>
 __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
+  static_assert(!(RAGGED && PIPE), "the pipelined loop loads without tests");
   constexpr int ROWB = 2 * FK, XPART = FM * ROWB, WPART = FN * ROWB, BUF = 3 * XPART + 3 * WPART;      // bytes: 64, 4 K, 8 K, 36 K
-  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];                                          // 72 KB
+  __shared__ __attribute__((aligned(16))) char smem[(PIPE ? 3 : 2) * BUF];                             // 72 KB; pipelined: 108 KB
   const float *__restrict__ X = a.x;
   const float *__restrict__ W = a.w;
   const int rows = a.rows, out_f = a.out_f, in_f = a.in_f, ntn = a.ntn;
@@ -749,15 +842,37 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
     }
   };
 
-  gload(0);
-  lstore(0);
-  if (nslab > 1) gload(1);
-  __syncthreads();
-  for (int s = 0; s < nslab; ++s) {
-    if (s + 1 < nslab) lstore((s + 1) & 1);           // the other buffer: its last readers passed the barrier of slab s - 1
-    compute(s & 1);
-    if (s + 2 < nslab) gload(s + 2);
+  if constexpr (PIPE) {
+    pipelined_slabs<9, 3, FwdLoads>(
+        nslab, BUF, acc0, acc1,
+        [&](FwdLoads &g, int slab) {
+          g.x = *reinterpret_cast<const f32x4 *>(xp + slab * FK);
+          g.w0 = *reinterpret_cast<const f32x4 *>(wp0 + slab * FK);
+          g.w1 = *reinterpret_cast<const f32x4 *>(wp1 + slab * FK);
+        },
+        [&](const FwdLoads &g, int, int boff) {
+          char *b = smem + boff;
+          split_store(g.x, b, XPART);
+          split_store(g.w0, b + 3 * XPART, WPART);
+          split_store(g.w1, b + 3 * XPART + 64 * ROWB, WPART);
+        },
+        [&](Frags &f, int boff) {
+          const char *xb = smem + boff, *wb = xb + 3 * XPART;
+          f.ah = frag(xb, wm * 32), f.am = frag(xb + XPART, wm * 32), f.al = frag(xb + 2 * XPART, wm * 32);
+          f.b0h = frag(wb, wn * 64), f.b0m = frag(wb + WPART, wn * 64), f.b0l = frag(wb + 2 * WPART, wn * 64);
+          f.b1h = frag(wb, wn * 64 + 32), f.b1m = frag(wb + WPART, wn * 64 + 32), f.b1l = frag(wb + 2 * WPART, wn * 64 + 32);
+        });
+  } else {
+    gload(0);
+    lstore(0);
+    if (nslab > 1) gload(1);
     __syncthreads();
+    for (int s = 0; s < nslab; ++s) {
+      if (s + 1 < nslab) lstore((s + 1) & 1);         // the other buffer: its last readers passed the barrier of slab s - 1
+      compute(s & 1);
+      if (s + 2 < nslab) gload(s + 2);
+      __syncthreads();
+    }
   }
   // ---- the end (the slab buffers are free): K half 0 finishes block 0 of its wave tile, K half 1 block 1 of the same tile (waves w and
   // w ^ 4 hold the two halves of one tile): each hands the accumulator it does not finish to the other, [8 waves x 16 registers][64 lanes]
@@ -783,8 +898,10 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
   }
 }
 
-__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_fwd_kernel_f32x3(FwdArgs a) { linear_fwd_body<false>(a); }
-__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_fwd_kernel_f32x3_ragged(FwdArgs a) { linear_fwd_body<true>(a); }
+// (pipelined: two sets of fragment and of load registers -- two waves per SIMD, as the LDS allows anyway)
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_fwd_kernel_f32x3(FwdArgs a) { linear_fwd_body<false, false>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_fwd_kernel_f32x3_ragged(FwdArgs a) { linear_fwd_body<true, false>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_fwd_kernel_f32x3_pipe(FwdArgs a) { linear_fwd_body<false, true>(a); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The backward of the same pair with respect to its input (pn_linear_bwd): for g, a rows x out, W out x in AS IT LIES,
@@ -806,12 +923,17 @@ struct BwdArgs {
   int rows, out_f, in_f, ntn;
 };
 
-template <bool RAGGED>
+struct BwdLoads {
+  f32x4 g, a, w0, w1;
+};
+
+template <bool RAGGED, bool PIPE>
 __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
+  static_assert(!(RAGGED && PIPE), "the pipelined loop loads without tests");
   constexpr int AROWB = 2 * FK, APART = FM * AROWB;              // gz: [64 rows][32 bf16], 4 KB per part
   constexpr int WROWB = 128, WIMG = FK * WROWB, WPART = 2 * WIMG;      // W: two [32 k][64 bf16] images, 8 KB per part
   constexpr int BUF = 3 * APART + 3 * WPART;                     // 36 KB
-  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];    // 72 KB
+  __shared__ __attribute__((aligned(16))) char smem[(PIPE ? 3 : 2) * BUF];      // 72 KB; pipelined: 108 KB
   const float *__restrict__ G = q.g;
   const float *__restrict__ A = q.a;
   const float *__restrict__ W = q.w;
@@ -891,15 +1013,56 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
     }
   };
 
-  gload(0);
-  lstore(0, 0);
-  if (nslab > 1) gload(1);
-  __syncthreads();
-  for (int s = 0; s < nslab; ++s) {
-    if (s + 1 < nslab) lstore(s + 1, (s + 1) & 1);    // the other buffer: its last readers passed the barrier of slab s - 1
-    compute(s & 1);
-    if (s + 2 < nslab) gload(s + 2);
+  if constexpr (PIPE) {
+    // (the store of gz is a branch of its own in the plain loop; here the loop is instantiated with and without it, so that a step
+    // stays one basic block for the interleave)
+    auto run = [&](auto keep_c) {
+      constexpr bool KEEP = decltype(keep_c)::value;
+      pipelined_slabs<15, 4, BwdLoads>(
+          nslab, BUF, acc0, acc1,
+          [&](BwdLoads &l, int slab) {
+            l.g = *reinterpret_cast<const f32x4 *>(G + aoff + slab * FK);
+            l.a = *reinterpret_cast<const f32x4 *>(A + aoff + slab * FK);
+            l.w0 = *reinterpret_cast<const f32x4 *>(wp + (size_t)(slab * FK) * in_f);
+            l.w1 = *reinterpret_cast<const f32x4 *>(wp + (size_t)(slab * FK + 16) * in_f);
+          },
+          [&](const BwdLoads &l, int slab, int boff) {
+            char *b = smem + boff;
+            // gz as the plain loop forms it, spelled out: 1 - a a in one fma, then ONE rounded product.  Left to contraction, the product
+            // here is fused into the split's first subtraction (fma(g, t, -hi)): other mid and lo terms, other bits in dx
+            f32x4 z;
+            {
+#pragma clang fp contract(off)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) z[e] = l.g[e] * __builtin_fmaf(-l.a[e], l.a[e], 1.f);
+            }
+            if constexpr (KEEP) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
+            split_store(z, b + aso, APART);
+            split_store(l.w0, b + 3 * APART + wso, WPART);
+            split_store(l.w1, b + 3 * APART + wso + 16 * WROWB, WPART);
+          },
+          [&](Frags &f, int boff) {
+            const char *ab = smem + boff, *wb = ab + 3 * APART + wn * WIMG;
+            f.ah = afrag(ab, wm * 32), f.am = afrag(ab + APART, wm * 32), f.al = afrag(ab + 2 * APART, wm * 32);
+            f.b0h = wfrag(wb, 0), f.b0m = wfrag(wb + WPART, 0), f.b0l = wfrag(wb + 2 * WPART, 0);
+            f.b1h = wfrag(wb, 32), f.b1m = wfrag(wb + WPART, 32), f.b1l = wfrag(wb + 2 * WPART, 32);
+          });
+    };
+    if (keep)
+      run(std::true_type{});
+    else
+      run(std::false_type{});
+  } else {
+    gload(0);
+    lstore(0, 0);
+    if (nslab > 1) gload(1);
     __syncthreads();
+    for (int s = 0; s < nslab; ++s) {
+      if (s + 1 < nslab) lstore(s + 1, (s + 1) & 1);  // the other buffer: its last readers passed the barrier of slab s - 1
+      compute(s & 1);
+      if (s + 2 < nslab) gload(s + 2);
+      __syncthreads();
+    }
   }
   // ---- the end, as the forward's: K half 0 finishes block 0 of its wave tile, K half 1 block 1; each hands the other its accumulator
   float(*red)[64] = reinterpret_cast<float(*)[64]>(smem);
@@ -920,8 +1083,9 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   }
 }
 
-__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3(BwdArgs a) { linear_bwd_body<false>(a); }
-__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true>(a); }
 
 int cu_count() {
   static int n = 0;             // (the calling thread's current device; every device of a node is the same part)
@@ -1035,6 +1199,12 @@ int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f
 
 int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
                   void *y) {
+  return pn_linear_fwd_form(stream, dtype, rows, out_f, in_f, x, w, b, act, y, 0);
+}
+
+int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b,
+                       int act, void *y, int flags) {
+  if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_fwd_form: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
   if (!pn_linear_fwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_fwd: unsupported dtype or shape (see pn_linear_fwd_supported)");
   if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH) return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY or PN_ACT_TANH");
   if (x == nullptr || w == nullptr || y == nullptr) return pn::fail("pn_linear_fwd: null operand");
@@ -1046,8 +1216,8 @@ int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
   a.ntn = (int)((out_f + FN - 1) / FN);
   const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)a.ntn;
   const bool ragged = rows % FM != 0 || out_f % FN != 0;
-  return pn::launch("pn_linear_fwd", ragged ? pn_linear_fwd_kernel_f32x3_ragged : pn_linear_fwd_kernel_f32x3, dim3(blocks), dim3(kFwdThreads),
-                    (hipStream_t)stream, a);
+  auto kern = ragged ? pn_linear_fwd_kernel_f32x3_ragged : ((flags & PN_LINEAR_FORM_PLAIN) ? pn_linear_fwd_kernel_f32x3 : pn_linear_fwd_kernel_f32x3_pipe);
+  return pn::launch("pn_linear_fwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, a);
 }
 
 int pn_linear_bwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f) {
@@ -1059,6 +1229,12 @@ int pn_linear_bwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f
 
 int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, void *gz,
                   void *dx) {
+  return pn_linear_bwd_form(stream, dtype, rows, out_f, in_f, g, a, w, gz, dx, 0);
+}
+
+int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w,
+                       void *gz, void *dx, int flags) {
+  if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_bwd_form: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
   if (!pn_linear_bwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_bwd: unsupported dtype or shape (see pn_linear_bwd_supported)");
   if (g == nullptr || a == nullptr || w == nullptr || gz == nullptr || dx == nullptr) return pn::fail("pn_linear_bwd: null operand");
   if (!pn::aligned16(g, a, w, gz, dx)) return pn::fail("pn_linear_bwd: operands must be 16-byte aligned");
@@ -1079,8 +1255,8 @@ int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
   q.ntn = (int)((in_f + FN - 1) / FN);
   const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)q.ntn;
   const bool ragged = rows % FM != 0 || in_f % FN != 0;
-  return pn::launch("pn_linear_bwd", ragged ? pn_linear_bwd_kernel_f32x3_ragged : pn_linear_bwd_kernel_f32x3, dim3(blocks), dim3(kFwdThreads),
-                    (hipStream_t)stream, q);
+  auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : ((flags & PN_LINEAR_FORM_PLAIN) ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
+  return pn::launch("pn_linear_bwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
 }
 
 }  // extern "C"

@@ -16,6 +16,9 @@ the stock modules everywhere; ``1`` is ``auto`` and warns once, with the reason,
 and ``dx = g_z W`` -- as one ``pn_linear_bwd`` launch; ``0`` runs ``tanh_backward`` and ``matmul`` by torch; ``1`` is ``auto`` and
 warns once with the reason a pair's backward runs through torch.  It has no effect where ``-pn_linear_fwd`` leaves the stock modules
 in place: the backward lives in the pair's ``autograd.Function``.
+``-pn_linear_form auto|plain`` (read there too): ``auto``, the default, lets ``pn_linear_fwd`` and ``pn_linear_bwd`` take the pipelined
+K loop on aligned shapes; ``plain`` keeps the plain loop everywhere (``PN_LINEAR_FORM_PLAIN``).  The two give the same bits: the option
+is for timing one against the other inside one tree.
 """
 import os
 import shlex
@@ -88,3 +91,11 @@ def truthy(value, default=True):
     if v == "":
         return True
     return v in ("1", "true", "yes", "on")
+
+
+def linear_form():
+    """-pn_linear_form auto|plain; anything else is refused by name."""
+    v = str(_DB.get("pn_linear_form", "auto")).strip().lower()
+    if v not in ("auto", "plain"):
+        raise ValueError("-pn_linear_form %r: auto or plain" % v)
+    return v

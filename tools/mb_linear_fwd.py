@@ -1,7 +1,9 @@
 """Times pn_linear_fwd (csrc/pn_linear.hip) against the library path it replaces, torch.tanh(F.linear(x, w, b)), on the same
 operands in one process.  Both sides are captured into hipGraphs of N launches and replayed: no Python between two launches, the
 way a graph-mode sweep runs them.     python tools/mb_linear_fwd.py [rows out_f in_f]
-Prints us per launch (the library side: per pair of launches) and the error of both against float64."""
+Both forms of the kernel's K loop (the pipelined one and PN_LINEAR_FORM_PLAIN) are timed in the same process, in interleaved rounds: round r
+times one block of every graph in turn, so that a drift of the clocks falls on all of them alike.
+Prints the median and the fastest block in us per launch (the library side: per pair of launches) and the error against float64."""
 import os
 import sys
 
@@ -10,22 +12,26 @@ import torch
 import torch.nn.functional as F
 
 import pnode_amd  # noqa: F401
+from pnode_amd import _lib
 from pnode_amd._vecops import HipVecOps
 
 
-def timed(graph, n, reps=20):
-    for _ in range(3):
-        graph.replay()
+def timed(graphs, n, reps=20, rounds=9):
+    """{name: graph} -> {name: (median, fastest)} us per launch; one block = reps replays, the graphs take turns inside a round"""
+    for g in graphs.values():
+        for _ in range(3):
+            g.replay()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    best = float("inf")
-    for _ in range(5):
-        e0.record()
-        for _ in range(reps):
-            graph.replay()
-        e1.record()
-        e1.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e3 / (reps * n))
-    return best
+    times = {name: [] for name in graphs}
+    for _ in range(rounds):
+        for name, g in graphs.items():
+            e0.record()
+            for _ in range(reps):
+                g.replay()
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / (reps * n))
+    return {name: (sorted(t)[len(t) // 2], min(t)) for name, t in times.items()}
 
 
 def main():
@@ -40,9 +46,12 @@ def main():
     ops = HipVecOps(dev, torch.float32, rows * in_f)
     assert ops.linear_fwd_supported(rows, out_f, in_f)
 
-    def ours(tanh):
+    def ours(tanh, flags=0):
         for k in range(N):
-            ops.linear_fwd(xs[k % NP], ws[k % NP], bs[k % NP], tanh, ys[k % NP])
+            ops.linear_fwd(xs[k % NP], ws[k % NP], bs[k % NP], tanh, ys[k % NP], flags=flags)
+
+    def plain(tanh):
+        ours(tanh, _lib.PN_LINEAR_FORM_PLAIN)
 
     def lib(tanh):
         for k in range(N):
@@ -51,8 +60,9 @@ def main():
                 torch.tanh(z)
 
     side = torch.cuda.Stream()
-    results = {}
-    for name, fn, arg in (("pn_linear_fwd tanh", ours, True), ("pn_linear_fwd identity", ours, False),
+    graphs = {}
+    for name, fn, arg in (("pn_linear_fwd tanh pipelined", ours, True), ("pn_linear_fwd tanh plain", plain, True),
+                          ("pn_linear_fwd identity pipelined", ours, False), ("pn_linear_fwd identity plain", plain, False),
                           ("torch.tanh(F.linear)", lib, True), ("F.linear", lib, False)):
         with torch.cuda.stream(side):
             fn(arg)
@@ -61,15 +71,18 @@ def main():
             with torch.cuda.graph(g, stream=side):
                 fn(arg)
         torch.cuda.synchronize()
-        results[name] = timed(g, N)
-    for name in results:
-        print("%-24s %4d x %4d x %4d: %6.2f us per layer evaluation" % (name, rows, out_f, in_f, results[name]))
+        graphs[name] = g
+    results = timed(graphs, N)
+    for name, (med, best) in results.items():
+        print("%-32s %4d x %4d x %4d: median %6.2f us (fastest %6.2f) per layer evaluation" % (name, rows, out_f, in_f, med, best))
     x, w, b = xs[0], ws[0], bs[0]
     z64 = F.linear(x.double(), w.double(), b.double())
     scale = x.double().abs() @ w.double().abs().t() + b.double().abs()
     for tanh in (False, True):
         ref = torch.tanh(z64) if tanh else z64
         got = ops.linear_fwd(x, w, b, tanh)
+        print("act=%s  the two forms give the same bits: %s" % (
+            "tanh" if tanh else "identity", torch.equal(got, ops.linear_fwd(x, w, b, tanh, flags=_lib.PN_LINEAR_FORM_PLAIN))))
         libv = torch.tanh(F.linear(x, w, b)) if tanh else F.linear(x, w, b)
         print("act=%s  max error / (sum|x w| + |b|):  pn_linear_fwd %.3e   library %.3e" % (
             "tanh" if tanh else "identity", float(((got.double() - ref).abs() / scale).max()), float(((libv.double() - ref).abs() / scale).max())))
