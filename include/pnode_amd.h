@@ -231,9 +231,10 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
  * applied in fp32 to the biased sum: exactly +-1 once it saturates, NaN for NaN).  The product is the split-bf16 one of pn_linear_wgrad
  * (three exact bf16 terms per operand, the six largest cross products, fp32 accumulation on v_mfma_f32_32x32x16_bf16; an infinite
  * operand gives NaN); one workgroup owns a 64 x 128 tile of y over all of in_f and writes it once: no atomics, no work buffers, the
- * same bits on every launch.  x, w, y 16-byte aligned, y != x.  Replaces, inside the solver's own evaluations of func (the body of
- * evalRHSFunction, pa.py:393-412), the library GEMM and the elementwise kernel of an nn.Linear -> nn.Tanh pair.
- * pn_linear_fwd_supported: fp32, rows >= 256 (any number), out_f % 64 == 0, in_f % 64 == 0; everything else is the caller's to run
+ * same bits on every launch.  x, w, y non-NULL and 16-byte aligned, b 4-byte aligned; y shares no byte with x, w or b (other workgroups
+ * still read them while a tile of y is stored): refused otherwise, nothing launched.  Replaces, inside the solver's own evaluations of
+ * func (the body of evalRHSFunction, pa.py:393-412), the library GEMM and the elementwise kernel of an nn.Linear -> nn.Tanh pair.
+ * pn_linear_fwd_supported: fp32, rows >= 256 (any number), out_f % 64 == 0, in_f % 32 == 0 and >= 64; everything else is the caller's to run
  * through the library. */
 #define PN_ACT_IDENTITY 0
 #define PN_ACT_TANH 1
@@ -242,8 +243,8 @@ int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
                   void *y);
 /* The K loop of pn_linear_fwd and pn_linear_bwd has two forms with the same bits in every output: the PIPELINED one (three LDS buffers,
  * two sets of fragment registers: the MFMAs of a slab run while the next slab's fragments are read and the one after it is split and
- * stored) that aligned shapes -- rows % 64 == 0 and the output's columns % 128 == 0 -- take by themselves, and the PLAIN one, which
- * ragged shapes always take.  pn_linear_fwd_form / pn_linear_bwd_form are pn_linear_fwd / pn_linear_bwd with `flags`: 0, or
+ * stored) that aligned shapes -- rows % 64 == 0, the output's columns % 128 == 0 and K % 64 == 0 -- take by themselves, and the PLAIN one,
+ * which ragged shapes and an odd number of K slabs (K = 96, 160, ...) always take.  pn_linear_fwd_form / pn_linear_bwd_form are pn_linear_fwd / pn_linear_bwd with `flags`: 0, or
  * PN_LINEAR_FORM_PLAIN for the plain loop on an aligned shape too (for comparisons); any other bit is refused. */
 #define PN_LINEAR_FORM_PLAIN 1
 int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b,
@@ -260,7 +261,8 @@ int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
  * gives NaN in the products it takes part in.  All five operands non-NULL and 16-byte aligned; gz and dx share no byte with each other
  * or with an input (other workgroups still read them): refused otherwise, nothing launched.  Replaces, in the reverse sweep's stage VJPs,
  * the tanh_backward kernel and the library GEMM of the pair.
- * pn_linear_bwd_supported: fp32, rows >= 256 (any number), out_f % 64 == 0, in_f % 64 == 0, the size limits of pn_linear_fwd_supported. */
+ * pn_linear_bwd_supported: fp32, rows >= 256 (any number), out_f % 32 == 0 and >= 64, in_f % 64 == 0, the size limits of
+ * pn_linear_fwd_supported. */
 int pn_linear_bwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
 int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, void *gz,
                   void *dx);

@@ -228,7 +228,7 @@ class HipVecOps(object):
 
     def linear_fwd(self, x, w, b, tanh, y=None, flags=None):
         """y = act(x w^T + b), act = tanh or the identity; x (rows, in_f), w (out_f, in_f), b (out_f,) or None: contiguous fp32 on this device.
-        Refused (PnError), never run another way, outside pn_linear_fwd_supported.  flags: pn_linear_fwd_form's (default: linear_flags)."""
+        Refused (PnError), never run another way, outside pn_linear_fwd_supported and where y shares memory with x, w or b.  flags: pn_linear_fwd_form's (default: linear_flags)."""
         rows, in_f = x.shape
         out_f = w.shape[0]
         for v in (x, w, b, y):

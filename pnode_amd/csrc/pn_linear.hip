@@ -663,8 +663,8 @@ __global__ __launch_bounds__(256) void pn_linear_bgrad_finish_kernel(double *__r
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The PIPELINED K loop of pn_linear_fwd / pn_linear_bwd on aligned shapes (the plain loops further down stay: the ragged bodies, and
-// PN_LINEAR_FORM_PLAIN).  The plain loop runs three phases per slab that all eight waves enter together after the barrier -- split and
+// The PIPELINED K loop of pn_linear_fwd / pn_linear_bwd on aligned shapes (the plain loops further down stay: the ragged bodies, an odd
+// number of slabs -- K = 96, 160, ... --, and PN_LINEAR_FORM_PLAIN).  The plain loop runs three phases per slab that all eight waves enter together after the barrier -- split and
 // store of the next slab (VALU), fragment reads (LDS latency, exposed), twelve MFMAs -- and the matrix pipe idles through the first two.
 // Here every wave keeps TWO sets of fragment registers and TWO sets of load registers, and the slabs go through THREE LDS buffers.
 // Step s, between two barriers:
@@ -1099,6 +1099,13 @@ int cu_count() {
   return n;
 }
 
+// the byte ranges [p, p + np) and [r, r + nr) share a byte (a null r: an operand that is not there shares none)
+bool overlap(const void *p, size_t np, const void *r, size_t nr) {
+  if (r == nullptr) return false;
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), r0 = reinterpret_cast<uintptr_t>(r);
+  return p0 < r0 + nr && r0 < p0 + np;
+}
+
 template <typename T>
 int finish_t(hipStream_t st, int64_t out_f, int64_t in_f, void *pw, void *pb, void *mu_w, void *mu_b) {
   const size_t mn = (size_t)out_f * (size_t)in_f;
@@ -1193,7 +1200,8 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
 int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f) {
   if (dtype != PN_F32) return 0;
   const int64_t lim = (int64_t)1 << 30;
-  if (!(rows >= 256 && rows < lim && out_f > 0 && out_f < lim && out_f % 64 == 0 && in_f > 0 && in_f < lim && in_f % 64 == 0)) return 0;
+  // (K = in_f: whole slabs of 32, at least two; an odd number of them takes the plain loop)
+  if (!(rows >= 256 && rows < lim && out_f > 0 && out_f < lim && out_f % 64 == 0 && in_f >= 64 && in_f < lim && in_f % FK == 0)) return 0;
   return ((rows + FM - 1) / FM) * ((out_f + FN - 1) / FN) < lim ? 1 : 0;
 }
 
@@ -1209,21 +1217,27 @@ int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
   if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH) return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY or PN_ACT_TANH");
   if (x == nullptr || w == nullptr || y == nullptr) return pn::fail("pn_linear_fwd: null operand");
   if (!pn::aligned16(x, w, y) || (reinterpret_cast<uintptr_t>(b) & 3)) return pn::fail("pn_linear_fwd: operands must be 16-byte aligned");
-  if (x == y) return pn::fail("pn_linear_fwd: y must not be x (other workgroups still read the rows a workgroup writes)");
+  // an output that shares bytes with anything the launch reads: other workgroups still read x, w and b while a tile of y is stored
+  const size_t ny = (size_t)rows * (size_t)out_f * sizeof(float), nx = (size_t)rows * (size_t)in_f * sizeof(float),
+               nw = (size_t)out_f * (size_t)in_f * sizeof(float), nb = (size_t)out_f * sizeof(float);
+  if (overlap(y, ny, x, nx) || overlap(y, ny, w, nw) || overlap(y, ny, b, nb))
+    return pn::fail("pn_linear_fwd: y must not alias x, w or b (other workgroups still read them)");
   FwdArgs a;
   a.x = (const float *)x, a.w = (const float *)w, a.b = (const float *)b, a.y = (float *)y;
   a.rows = (int)rows, a.out_f = (int)out_f, a.in_f = (int)in_f, a.act = act;
   a.ntn = (int)((out_f + FN - 1) / FN);
   const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)a.ntn;
   const bool ragged = rows % FM != 0 || out_f % FN != 0;
-  auto kern = ragged ? pn_linear_fwd_kernel_f32x3_ragged : ((flags & PN_LINEAR_FORM_PLAIN) ? pn_linear_fwd_kernel_f32x3 : pn_linear_fwd_kernel_f32x3_pipe);
+  const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (in_f / FK) % 2 != 0;       // (the pipelined loop takes an even number of slabs)
+  auto kern = ragged ? pn_linear_fwd_kernel_f32x3_ragged : (plain ? pn_linear_fwd_kernel_f32x3 : pn_linear_fwd_kernel_f32x3_pipe);
   return pn::launch("pn_linear_fwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, a);
 }
 
 int pn_linear_bwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f) {
   if (dtype != PN_F32) return 0;
   const int64_t lim = (int64_t)1 << 30;
-  if (!(rows >= 256 && rows < lim && out_f > 0 && out_f < lim && out_f % 64 == 0 && in_f > 0 && in_f < lim && in_f % 64 == 0)) return 0;
+  // (K = out_f: whole slabs of 32, at least two; an odd number of them takes the plain loop)
+  if (!(rows >= 256 && rows < lim && out_f >= 64 && out_f < lim && out_f % FK == 0 && in_f > 0 && in_f < lim && in_f % 64 == 0)) return 0;
   return ((rows + FM - 1) / FM) * ((in_f + FN - 1) / FN) < lim ? 1 : 0;
 }
 
@@ -1241,10 +1255,6 @@ int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
   // an output that shares bytes with anything else the launch touches: other workgroups still read (or also write) them
   const size_t nz = (size_t)rows * (size_t)out_f * sizeof(float), nw = (size_t)out_f * (size_t)in_f * sizeof(float),
                nx = (size_t)rows * (size_t)in_f * sizeof(float);
-  auto overlap = [](const void *p, size_t np, const void *r, size_t nr) {
-    const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), r0 = reinterpret_cast<uintptr_t>(r);
-    return p0 < r0 + nr && r0 < p0 + np;
-  };
   if (overlap(gz, nz, g, nz) || overlap(gz, nz, a, nz) || overlap(gz, nz, w, nw))
     return pn::fail("pn_linear_bwd: gz must not alias g, a or w (other workgroups still read them)");
   if (overlap(dx, nx, g, nz) || overlap(dx, nx, a, nz) || overlap(dx, nx, w, nw) || overlap(dx, nx, gz, nz))
@@ -1255,7 +1265,8 @@ int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
   q.ntn = (int)((in_f + FN - 1) / FN);
   const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)q.ntn;
   const bool ragged = rows % FM != 0 || in_f % FN != 0;
-  auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : ((flags & PN_LINEAR_FORM_PLAIN) ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
+  const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (out_f / FK) % 2 != 0;      // (the pipelined loop takes an even number of slabs)
+  auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : (plain ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
   return pn::launch("pn_linear_bwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
 }
 

@@ -142,7 +142,7 @@ def _untouched(gz, dx):
     return bool((gz == 7.0).all()) and bool((dx == 9.0).all())
 
 
-@pytest.mark.parametrize("rows,out_f,in_f", [(255, 64, 64), (256, 96, 64), (256, 64, 96)])
+@pytest.mark.parametrize("rows,out_f,in_f", [(255, 64, 64), (256, 80, 64), (256, 32, 64), (256, 64, 96)])
 def test_unsupported_shapes_are_refused_and_nothing_is_launched(rows, out_f, in_f):
     from pnode_amd._lib import PnError
     ops = _ops(rows, out_f)

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _linear_tile_cases import distinct as _distinct
 from conftest import require_gpu
 
 pytestmark = pytest.mark.gpu
@@ -26,15 +27,6 @@ def _ops(n):
     from pnode_amd._vecops import HipVecOps
     assert _lib.PN_LINEAR_FORM_PLAIN == PLAIN
     return HipVecOps(require_gpu(), torch.float32, n)
-
-
-def _distinct(rows, cols, seed):
-    """(1 + (7 r + 3 c + seed) % 31) * 2^((r + c) % 3 - 1), signs alternating: |v| <= 62 in steps of 1/2, five significant bits -- a sum of
-    320 products of two such values is below 2^21 in steps of 1/4: exact in fp32 in any order."""
-    r = torch.arange(rows).view(-1, 1)
-    c = torch.arange(cols).view(1, -1)
-    v = (1 + (7 * r + 3 * c + seed) % 31).float() * torch.pow(2.0, ((r + c) % 3 - 1).float())
-    return v * (1 - 2 * ((r + 2 * c) % 2)).float()
 
 
 def _operands(kind, rows, k, width, seed, dev):

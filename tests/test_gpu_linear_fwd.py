@@ -120,7 +120,7 @@ def test_saturation_nan_and_inf_stay_in_their_rows_and_launches_repeat_bitwise()
         assert bool((torch.isnan(y[300]) | (y[300].abs() == 1.0) | torch.isinf(y[300])).all())
 
 
-@pytest.mark.parametrize("rows,out_f,in_f", [(255, 64, 64), (256, 64, 96), (256, 96, 64)])
+@pytest.mark.parametrize("rows,out_f,in_f", [(255, 64, 64), (256, 64, 80), (256, 64, 32), (256, 96, 64)])
 def test_unsupported_shapes_are_reported_and_never_launch(rows, out_f, in_f):
     from pnode_amd._lib import PnError
     ops = _ops(rows, in_f)
