@@ -269,6 +269,20 @@ int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
 int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w,
                        void *gz, void *dx, int flags);
 
+/* The backward of a BARE Linear layer -- no activation behind it -- with respect to its input (csrc/pn_linear.hip): for g rows x out_f (the
+ * cotangent at the layer's output) and w out_f x in_f as it lies, row-major fp32,
+ *   dx[r][n] = sum_k g[r][k] w[k][n]      rows x in_f, written once
+ * by the kernel body of pn_linear_bwd without its prologue: no a is read, no gz is written (16 MiB less traffic at 4096 x 512), the A
+ * operand is g's bits unchanged.  The bits are fixed by that: for finite g, dx equals the dx of pn_linear_bwd(g, a = 0, w) bit for bit
+ * (g (1 - 0 0) is g exactly, with or without the fma), in every form -- plain, ragged, pipelined -- and on every launch.  A NaN or Inf
+ * in g stays in its row of dx, an Inf in w in the columns it feeds.  g, w, dx non-NULL and 16-byte aligned; dx shares no byte with g or
+ * w: refused otherwise, nothing launched.  Replaces, in the reverse sweep's stage VJPs, the library matmul of a bare nn.Linear of func
+ * (the head of every `... -> Linear` net).  pn_linear_dx_supported is pn_linear_bwd_supported; pn_linear_dx_form takes the flags of
+ * pn_linear_bwd_form (0 or PN_LINEAR_FORM_PLAIN; any other bit is refused, first). */
+int pn_linear_dx_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
+int pn_linear_dx(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *w, void *dx);
+int pn_linear_dx_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *w, void *dx, int flags);
+
 /* result_dev[j] = <x, y_j> for j < nk <= PN_MAX_TERMS, accumulated in double, reduced in a fixed
  * order (bit-reproducible).  ||x||^2 is the case y_0 == x.  Replaces VecMDot / VecNorm inside
  * the KSP(GMRES) and SNES that PETSc's implicit steppers run (TS type BE/CN, pa.py:651-654;

@@ -147,6 +147,9 @@ PROTOTYPES = {
     "pn_linear_bwd_supported": (_i, [_i, _i64, _i64, _i64]),
     "pn_linear_bwd": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pn_linear_bwd_form": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i]),
+    "pn_linear_dx_supported": (_i, [_i, _i64, _i64, _i64]),
+    "pn_linear_dx": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "pn_linear_dx_form": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i]),
     "pn_colsum_accum": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _d, _vp]),
     "pn_colsum_accum_multi": (_i, [_vp, _i, _i, _pi64, _pi64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _pd, _vp]),
     "pn_colsum_work_bytes": (_i64, [_i, _pi64, _pi64]),

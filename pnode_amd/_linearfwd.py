@@ -28,7 +28,17 @@ the pair's node as it sees a hooked layer: the walk goes on along the input edge
 
 At a solver's first fused evaluation outside a capture the pair is computed through torch as well; a difference above 1e-6 of
 ``sum |x w| + |b|`` (the library path's own 1.0e-7, the split product's 5.7e-8 and a few ulp of the two tanh, with room) switches
-fusing off for that solver, ``why`` recorded.  ``-pn_linear_fwd auto|0|1``, ``-pn_linear_bwd auto|0|1``."""
+fusing off for that solver, ``why`` recorded.  ``-pn_linear_fwd auto|0|1``, ``-pn_linear_bwd auto|0|1``.
+
+BARE layers (``-pn_linear_bare 0|1``, default ``0``: nothing below happens).  A child of an eligible container that is exactly
+``nn.Linear``, opens no fused pair and passes the static rules of a pair's Linear (``_static_why``, the same code) is a bare layer: the
+head of every ``... -> Linear`` net, a Linear in front of a ReLU or of a subclass of ``nn.Tanh``.  With ``1`` the runner sends it through
+``_Linear``: forward ``pn_linear_fwd`` with the identity under the call-time rules of ``_fusable``; backward ``dx = g W`` by
+``pn_linear_dx`` (the kernel body of ``pn_linear_bwd`` without the tanh' prologue: no ``a`` read, no ``g_z`` written) under the rules of
+``_bwd_fusable`` minus everything about ``a``, else ``matmul``; ``(g, x)`` then goes to ``LinearParamGrads._grad_hook`` exactly as a
+pair's ``(g_z, x)`` does.  A container whose only eligible members are bare layers is active too.  The self-checks are the pair's in
+the pair's measures (forward against ``F.linear``, ``dx`` against ``matmul``); a miss switches off the bare path, or its backward,
+only -- the pairs are not touched.  The bare layers are kept in ``LinearFwd.bare``, beside ``plans``."""
 import contextlib
 import warnings
 import weakref
@@ -67,12 +77,36 @@ def _user_hooked(m):
     return False
 
 
-def find_pairs(func, params):
-    """[(sequential, {index of the Linear child: (linear, tanh)})] of func, and {class name of a container: reason} for the
-    Linear -> Tanh pairs that cannot be fused (what -pn_linear_fwd 1 warns about)."""
-    plans, refused = [], {}
+def _static_why(seq, kids, lin, act, index, owners):
+    """The static half of the eligibility rules for the Linear `lin` (and the Tanh `act` behind it; None for a bare layer) among the
+    children `kids` of `seq`: None, or the reason as a string."""
+    mods = (lin,) if act is None else (lin, act)
+    if type(seq) is not nn.Sequential or "forward" in seq.__dict__:
+        return "the container's forward is not nn.Sequential's own"
+    if type(lin) is not nn.Linear or (act is not None and type(act) is not nn.Tanh):
+        return "a subclass of nn.Linear or nn.Tanh"
+    if any("forward" in m.__dict__ for m in mods):
+        return "an instance-level forward on the layer"
+    why = None
+    for p in (lin.weight, lin.bias):
+        if p is None:
+            continue
+        if not isinstance(p, nn.Parameter) or not p.requires_grad or id(p) not in index:
+            why = "a weight or bias that is not a trainable parameter of the solver"
+        elif owners.get(id(p), 0) != 1:
+            why = "a weight or bias shared with another module"
+    if why is None and sum(kids.count(m) for m in mods) != len(mods):
+        why = "the layer appears twice in the container"
+    return why
+
+
+def find_layers(func, params):
+    """(plans, refused, bare): [(sequential, {index of the Linear child: (linear, tanh)})] of func; {class name of a container: reason}
+    for the Linear -> Tanh pairs that cannot be fused (what -pn_linear_fwd 1 warns about); and [(sequential, {index of the child:
+    linear})] for the bare layers -- exactly nn.Linear, opening no fused pair, under the same static rules (-pn_linear_bare 1)."""
+    plans, refused, bare = [], {}, []
     if not isinstance(func, nn.Module):
-        return plans, refused
+        return plans, refused, bare
     index = {id(p) for p in params}
     owners = {}
     for m in func.modules():
@@ -90,30 +124,23 @@ def find_pairs(func, params):
             lin, act = kids[i], kids[i + 1]
             if not (isinstance(lin, nn.Linear) and isinstance(act, nn.Tanh)):
                 continue
-            why = None
-            if type(seq) is not nn.Sequential or "forward" in seq.__dict__:
-                why = "the container's forward is not nn.Sequential's own"
-            elif type(lin) is not nn.Linear or type(act) is not nn.Tanh:
-                why = "a subclass of nn.Linear or nn.Tanh"
-            elif "forward" in lin.__dict__ or "forward" in act.__dict__:
-                why = "an instance-level forward on the layer"
-            else:
-                for p in (lin.weight, lin.bias):
-                    if p is None:
-                        continue
-                    if not isinstance(p, nn.Parameter) or not p.requires_grad or id(p) not in index:
-                        why = "a weight or bias that is not a trainable parameter of the solver"
-                    elif owners.get(id(p), 0) != 1:
-                        why = "a weight or bias shared with another module"
-                if why is None and kids.count(lin) + kids.count(act) != 2:
-                    why = "the layer appears twice in the container"
+            why = _static_why(seq, kids, lin, act, index, owners)
             if why is None:
                 pairs[i] = (lin, act)
             else:
                 refused.setdefault(type(seq).__name__, why)
         if pairs:
             plans.append((seq, pairs))
-    return plans, refused
+        alone = {i: m for i, m in enumerate(kids)
+                 if type(m) is nn.Linear and i not in pairs and _static_why(seq, kids, m, None, index, owners) is None}
+        if alone:
+            bare.append((seq, alone))
+    return plans, refused, bare
+
+
+def find_pairs(func, params):
+    """The first two of find_layers."""
+    return find_layers(func, params)[:2]
 
 
 class _Call(object):
@@ -141,19 +168,49 @@ class _LinearTanh(torch.autograd.Function):
         else:
             g_z = torch.ops.aten.tanh_backward(g, a)
             dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
-        lg, ev = call.grads, call.ev
-        taken = False
-        if lg is not None and ev is not None and id(call.module) in lg.slots and not (lg.muted or lg.disabled or ev.muted):
-            # the path of a hooked layer's output hook (pnode_amd/_lineargrad.py): queued for the stage's grouped launch
-            lg._grad_hook(call.module, x.detach(), call.version, ev, g_z)
-            taken = not lg.disabled              # (a backward pass that is not a stage VJP of the solver switches the engine off there)
-        dw = db = None
-        if not taken:
-            g2 = g_z.reshape(-1, w.shape[0])
-            if ctx.needs_input_grad[1]:
-                dw = g2.t().mm(x.reshape(-1, w.shape[1]))
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                db = g2.sum(0)
+        dw, db = _param_grads(ctx, call, g_z, x, w)
+        return dx, dw, db, None
+
+
+def _param_grads(ctx, call, g_z, x, w):
+    """(dW, db) of the Linear of one fused call for autograd, or (None, None) after handing (g_z, x) to the engine."""
+    lg, ev = call.grads, call.ev
+    taken = False
+    if lg is not None and ev is not None and id(call.module) in lg.slots and not (lg.muted or lg.disabled or ev.muted):
+        # the path of a hooked layer's output hook (pnode_amd/_lineargrad.py): queued for the stage's grouped launch
+        lg._grad_hook(call.module, x.detach(), call.version, ev, g_z)
+        taken = not lg.disabled              # (a backward pass that is not a stage VJP of the solver switches the engine off there)
+    dw = db = None
+    if not taken:
+        g2 = g_z.reshape(-1, w.shape[0])
+        if ctx.needs_input_grad[1]:
+            dw = g2.t().mm(x.reshape(-1, w.shape[1]))
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = g2.sum(0)
+    return dw, db
+
+
+class _Linear(torch.autograd.Function):
+    """A bare layer (-pn_linear_bare 1): _LinearTanh without the activation."""
+    @staticmethod
+    def forward(ctx, x, w, b, call):
+        y = call.owner.kernel_bare(x.reshape(-1, w.shape[1]), w, b).view(x.shape[:-1] + (w.shape[0],))
+        ctx.save_for_backward(x, w)
+        ctx.call = call
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        call = ctx.call
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # pn_linear_dx where LinearFwd._bwd_fusable allows it, else the torch operation
+            dx = call.owner._backward_bare(g, w)
+            if dx is None:
+                dx = torch.matmul(g, w)
+        dw, db = _param_grads(ctx, call, g, x, w)
         return dx, dw, db, None
 
 
@@ -178,25 +235,45 @@ class LinearFwd(object):
         self.n_fused_bwd = 0       # pair backwards that ran as one launch
         self._warned_bwd = False
         self._ok_bwd = {}          # (rows, out_f, in_f) -> pn_linear_bwd_supported
+        # the bare layers (-pn_linear_bare 0|1): a map of their own; their checks switch off nothing but themselves
+        self.bare = []             # [(sequential, {child index: linear})]
+        self.bare_mode = "0"
+        self.bare_disabled = False      # the bare forward check failed
+        self.bare_why = None
+        self.bare_checked = False
+        self.n_bare = 0            # bare layer calls that ran pn_linear_fwd with the identity
+        self.bare_bwd_disabled = False  # the bare backward check failed (the bare forward stays)
+        self.bare_bwd_why = None
+        self.bare_bwd_checked = False
+        self.n_bare_bwd = 0        # bare backwards that ran pn_linear_dx
+        self._ok_dx = {}           # (rows, out_f, in_f) -> pn_linear_dx_supported
 
-    def install(self, func, params, mode="auto", bwd_mode="auto"):
-        """Find the eligible pairs of `func`; returns True when there is at least one."""
+    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0"):
+        """Find the eligible pairs of `func` (and, with bare_mode "1", its bare layers); returns True when there is at least one."""
         self.mode = mode
         self.bwd_mode = bwd_mode
-        self.plans, refused = find_pairs(func, params)
+        self.bare_mode = bare_mode
+        self.plans, refused, self.bare = find_layers(func, params)
         if mode == "1" and refused and not self._warned:
             self._warned = True
             for cls, why in refused.items():
                 warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> Tanh pair of %s runs the stock modules: %s" % (cls, why), RuntimeWarning)
-        return bool(self.plans)
+        return bool(self.plans) or self.bare_active
+
+    @property
+    def bare_active(self):
+        return self.bare_mode == "1" and bool(self.bare) and not self.bare_disabled
 
     @property
     def active(self):
-        return bool(self.plans) and not self.disabled
+        return (bool(self.plans) and not self.disabled) or self.bare_active
 
     # the one place the device is touched: tests of the eligibility rules replace it by the torch expression
     def kernel(self, x2, w, b):
         return self._ode()._ops.linear_fwd(x2, w, b, True)
+
+    def kernel_bare(self, x2, w, b):
+        return self._ode()._ops.linear_fwd(x2, w, b, False)
 
     def supported(self, rows, out_f, in_f):
         key = (rows, out_f, in_f)
@@ -230,21 +307,30 @@ class LinearFwd(object):
             return "outside pn_linear_fwd_supported"
         return None
 
-    def _check(self, x, w, b, a):
-        """First fused call of a solver: the pair through torch as well."""
-        self.checked = True
+    def _check(self, x, w, b, a, bare=False):
+        """First fused call of a solver: the pair through torch as well.  bare: a bare layer's first call, against F.linear in the same
+        measure; a miss switches off the bare path only."""
+        done = "bare_checked" if bare else "checked"
+        setattr(self, done, True)
         with torch.no_grad():
             x2 = x.reshape(-1, w.shape[1])
-            ref = torch.tanh(F.linear(x2, w, b))
+            ref = F.linear(x2, w, b)
+            if not bare:
+                ref = torch.tanh(ref)
             scale = x2.abs() @ w.abs().t()
             if b is not None:
                 scale = scale + b.abs()
             ok = torch.isfinite(ref) & (scale > 0)
             if not bool(ok.any()):
-                self.checked = False
+                setattr(self, done, False)
                 return True
             err = float(((a.reshape(ref.shape) - ref).abs() / scale)[ok].max())
         if not err <= CHECK_TOL:
+            if bare:
+                self.bare_disabled = True
+                self.bare_why = "pn_linear_fwd and F.linear differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
+                warnings.warn("pnode_amd: the bare Linear layers run the stock modules for this solver: " + self.bare_why, RuntimeWarning)
+                return False
             self.disabled = True
             self.why = "pn_linear_fwd and torch.tanh(F.linear) differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
             warnings.warn("pnode_amd: the fused Linear -> Tanh forward is switched off for this solver: " + self.why, RuntimeWarning)
@@ -255,36 +341,40 @@ class LinearFwd(object):
     def kernel_bwd(self, g2, a2, w):
         return self._ode()._ops.linear_bwd(g2, a2, w)
 
-    def supported_bwd(self, rows, out_f, in_f):
+    def supported_bwd(self, rows, out_f, in_f, entry="linear_bwd"):
         key = (rows, out_f, in_f)
-        ok = self._ok_bwd.get(key)
+        cache = self._ok_bwd if entry == "linear_bwd" else self._ok_dx
+        ok = cache.get(key)
         if ok is None:
             ops = self._ode()._ops
-            ok = self._ok_bwd[key] = bool(hasattr(ops, "linear_bwd_supported") and ops.linear_bwd_supported(rows, out_f, in_f))
+            ok = cache[key] = bool(hasattr(ops, entry + "_supported") and getattr(ops, entry + "_supported")(rows, out_f, in_f))
         return ok
 
     def _bwd_fusable(self, g, a, w):
-        """None, or the reason (a string) this backward runs the two torch operations."""
+        """None, or the reason (a string) this backward runs the torch operations.  a: the pair's output; None for a bare layer
+        (pn_linear_dx: the same rules minus everything about a)."""
+        bare = a is None
+        entry = "linear_dx" if bare else "linear_bwd"
         ode = self._ode()
-        if ode is None or not hasattr(ode._ops, "linear_bwd"):
-            return "the backend has no linear_bwd"
+        if ode is None or not hasattr(ode._ops, entry):
+            return "the backend has no " + entry
         if self.bwd_mode == "0":
             return "-pn_linear_bwd 0"
-        if self.bwd_disabled:
-            return self.bwd_why
+        if self.bare_bwd_disabled if bare else self.bwd_disabled:
+            return self.bare_bwd_why if bare else self.bwd_why
         if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != w.device or g.device.type != self.device_type \
-                or g.shape != a.shape:
+                or (g.dim() < 1 or g.shape[-1] != w.shape[0] if bare else g.shape != a.shape):
             return "the cotangent is no fp32 tensor of the pair's shape on the weight's device"
-        if not (g.is_contiguous() and a.is_contiguous() and w.is_contiguous()):
+        if not (g.is_contiguous() and (bare or a.is_contiguous()) and w.is_contiguous()):
             return "the cotangent is not contiguous"
-        if g.data_ptr() % 16 or a.data_ptr() % 16 or w.data_ptr() % 16:
+        if g.data_ptr() % 16 or (not bare and a.data_ptr() % 16) or w.data_ptr() % 16:
             return "operands are not 16-byte aligned"
         if _autocast_on(g.device.type):
             return "autocast is on"
         if torch.is_grad_enabled():
             return "the backward pass is itself differentiated (create_graph)"
-        if not self.supported_bwd(g.numel() // w.shape[0], w.shape[0], w.shape[1]):
-            return "outside pn_linear_bwd_supported"
+        if not self.supported_bwd(g.numel() // w.shape[0], w.shape[0], w.shape[1], entry):
+            return "outside pn_%s_supported" % entry
         return None
 
     def _check_bwd(self, g2, a2, w, gz, dx):
@@ -330,6 +420,53 @@ class LinearFwd(object):
         self.n_fused_bwd += 1
         return gz.view(g.shape), dx.view(g.shape[:-1] + (in_f,))
 
+    # ---- the backward of a bare layer (called from _Linear.backward)
+    def kernel_dx(self, g2, w):
+        return self._ode()._ops.linear_dx(g2, w)
+
+    def _check_bare_bwd(self, g2, w, dx):
+        """First pn_linear_dx of a solver: through torch as well, to CHECK_TOL of |g| |w| (the pair's bar in the pair's measure).  Returns
+        None, or the torch result after switching the bare backward -- only it -- off."""
+        self.bare_bwd_checked = True
+        dx_t = torch.matmul(g2, w)
+        scale = g2.abs() @ w.abs()
+        ok = torch.isfinite(dx_t) & (scale > 0)
+        if not bool(ok.any()):
+            self.bare_bwd_checked = False          # nothing to judge by: the next call is checked
+            return None
+        err = float(((dx - dx_t).abs() / scale)[ok].max())
+        if not err <= CHECK_TOL:
+            self.bare_bwd_disabled = True
+            self.bare_bwd_why = "pn_linear_dx and matmul differ: dx by %.2e of |g| |w| (allowed: %.0e)" % (err, CHECK_TOL)
+            warnings.warn("pnode_amd: the backward of the bare Linear layers runs matmul for this solver: " + self.bare_bwd_why, RuntimeWarning)
+            return dx_t
+        return None
+
+    def _backward_bare(self, g, w):
+        """dx of one bare layer by pn_linear_dx, or None: the caller runs matmul."""
+        if self._bwd_fusable(g, None, w) is not None:
+            return None
+        out_f, in_f = w.shape
+        g2 = g.reshape(-1, out_f)
+        with torch.no_grad():
+            dx = self.kernel_dx(g2, w)
+            if not self.bare_bwd_checked and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
+                torch_way = self._check_bare_bwd(g2, w, dx)
+                if torch_way is not None:
+                    return torch_way.view(g.shape[:-1] + (in_f,))
+        self.n_bare_bwd += 1
+        return dx.view(g.shape[:-1] + (in_f,))
+
+    @property
+    def bare_status(self):
+        if self.bare_mode != "1":
+            return "off (-pn_linear_bare 0)"
+        if not self.bare:
+            return "stock modules (no eligible bare layer)"
+        if self.bare_disabled:
+            return "stock modules (%s)" % self.bare_why
+        return "fused (%d layers; %d forward, %d backward calls so far)" % (sum(len(b) for _, b in self.bare), self.n_bare, self.n_bare_bwd)
+
     @property
     def bwd_status(self):
         if self.bwd_mode == "0":
@@ -361,7 +498,26 @@ class LinearFwd(object):
         self.n_fused += 1
         return a
 
-    def _runner(self, seq, pairs, grads):
+    def _bare(self, lin, x, grads):
+        """One bare layer (-pn_linear_bare 1): _pair without the activation."""
+        if self._fusable(lin, x) is not None:
+            return lin(x)
+        w, b = lin.weight, lin.bias
+        ev = grads.recording if grads is not None else None
+        if ev is not None and not grads.note_fused(lin, x):
+            ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
+        call = _Call()
+        call.owner, call.module, call.grads, call.ev, call.version = self, lin, grads, ev, x._version
+        y = _Linear.apply(x, w, b, call)
+        if not self.bare_checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            if not self._check(x.detach(), w.detach(), None if b is None else b.detach(), y.detach(), bare=True):
+                return lin(x)
+        if ev is not None and y.grad_fn is not None:
+            ev.through[y.grad_fn] = x.grad_fn     # Evaluation.clean passes the layer along its input edge only
+        self.n_bare += 1
+        return y
+
+    def _runner(self, seq, pairs, alone, grads):
         def forward(inp):
             kids = list(seq._modules.values())
             i, n = 0, len(kids)
@@ -370,11 +526,25 @@ class LinearFwd(object):
                 if p is not None and i + 1 < n and kids[i] is p[0] and kids[i + 1] is p[1] and not self.disabled:
                     inp = self._pair(p[0], p[1], inp, grads)
                     i += 2
+                elif alone.get(i) is kids[i] and not self.bare_disabled:
+                    inp = self._bare(kids[i], inp, grads)
+                    i += 1
                 else:
                     inp = kids[i](inp)
                     i += 1
             return inp
         return forward
+
+    def _containers(self):
+        """[(sequential, its pairs, its bare layers)]: the pairs while their forward is on, the bare layers with -pn_linear_bare 1."""
+        out = {}
+        if not self.disabled:
+            for seq, pairs in self.plans:
+                out[id(seq)] = (seq, pairs, {})
+        if self.bare_active:
+            for seq, alone in self.bare:
+                out[id(seq)] = (seq, out[id(seq)][1] if id(seq) in out else {}, alone)
+        return list(out.values())
 
     @contextlib.contextmanager
     def window(self, grads=None):
@@ -383,13 +553,19 @@ class LinearFwd(object):
         put = []
         try:
             if self.active and not _global_hooks():
-                for seq, pairs in self.plans:
+                for seq, pairs, alone in self._containers():
                     if "forward" in seq.__dict__ or type(seq) is not nn.Sequential:
                         continue
                     if _user_hooked(seq) or any(_user_hooked(m) for pr in pairs.values() for m in pr):
-                        self._refuse("a forward, pre-forward or backward hook on the pair or its container")
+                        if pairs:
+                            self._refuse("a forward, pre-forward or backward hook on the pair or its container")
+                        if _user_hooked(seq):
+                            continue
+                        pairs = {}                # (a hooked pair keeps the stock modules; the bare layers of the container stay)
+                    alone = {i: m for i, m in alone.items() if not _user_hooked(m)}
+                    if not pairs and not alone:
                         continue
-                    seq.__dict__["forward"] = self._runner(seq, pairs, grads)
+                    seq.__dict__["forward"] = self._runner(seq, pairs, alone, grads)
                     put.append(seq)
             yield
         finally:

@@ -918,34 +918,36 @@ class RKSweep(object):
     def _setup_linear_fwd(self):
         """(Re)install the fused forward of func's Linear -> Tanh pairs (pnode_amd/_linearfwd.py): explicit RK path and ARKIMEX's
         func2, as the engine-side sensitivities; -pn_linear_fwd auto|0|1 (not a PETSc option).  -pn_linear_bwd auto|0|1: the backward
-        of the same pairs as one launch each (pn_linear_bwd); it lives in the pair's Function, so it has no effect without the forward."""
+        of the same pairs as one launch each (pn_linear_bwd); it lives in the pair's Function, so it has no effect without the forward.
+        -pn_linear_bare 0|1 (default 0): func's bare nn.Linear layers through pn_linear_fwd with the identity and pn_linear_dx."""
         mode = str(options.get_all().get("pn_linear_fwd", "auto"))
         mode = "auto" if mode == "auto" else ("1" if options.truthy(mode, False) else "0")
         bwd = str(options.get_all().get("pn_linear_bwd", "auto"))
         bwd = "auto" if bwd == "auto" else ("1" if options.truthy(bwd, False) else "0")
         # -pn_linear_form auto|plain: `plain` keeps the plain K loop of both kernels on aligned shapes too (PN_LINEAR_FORM_PLAIN; the
         # same bits as the pipelined loop they take by themselves) -- for comparisons inside one tree
+        bare = "1" if options.truthy(options.get_all().get("pn_linear_bare", "0"), False) else "0"
         form = options.linear_form()
         if hasattr(self._ops, "linear_flags"):
             self._ops.linear_flags = _lib.PN_LINEAR_FORM_PLAIN if form == "plain" else 0
         from ._linearfwd import LinearFwd
         on = mode != "0" and self._stepper_kind in (None, "imex") and self.device.type == LinearFwd.device_type \
             and self.tensor_dtype == torch.float32 and hasattr(self._ops, "linear_fwd")
-        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form)
+        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form, bare)
         if sig == self._fwd_sig:
             return
         self._fwd_sig = sig
         self._fwd = None
         if on and self._paramsE:
             fwd = LinearFwd(self)
-            if fwd.install(self.funcEX, self._paramsE, mode, bwd):
+            if fwd.install(self.funcEX, self._paramsE, mode, bwd, bare):
                 self._fwd = fwd
 
     @property
     def linear_fwd(self):
         """How func's Linear -> Tanh pairs run in the solver's evaluations: "fused (N pairs)" or "stock modules (why)"."""
         fwd = self._fwd
-        if fwd is None:
+        if fwd is None or not fwd.plans:
             return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)"
         if fwd.disabled:
             return "stock modules (%s)" % fwd.why
@@ -955,9 +957,20 @@ class RKSweep(object):
     def linear_bwd(self):
         """How the backward of those pairs runs: "fused (N calls so far)" or "torch operations (why)"."""
         fwd = self._fwd
-        if fwd is None or fwd.disabled:
+        if fwd is None or fwd.disabled or not fwd.plans:
             return "torch operations (the pairs run the stock modules: see linear_fwd)"
         return fwd.bwd_status
+
+    @property
+    def linear_bare(self):
+        """How func's bare nn.Linear layers run in the solver's evaluations: "off (-pn_linear_bare 0)", "fused (N layers; F forward,
+        R backward calls so far)" or "stock modules (why)"."""
+        fwd = self._fwd
+        if fwd is None:
+            bare = options.truthy(options.get_all().get("pn_linear_bare", "0"), False)
+            return "stock modules (no eligible layer, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" if bare \
+                else "off (-pn_linear_bare 0)"
+        return fwd.bare_status
 
     def _flush_param_accum(self):
         self._flush_bias_accum()

@@ -272,6 +272,29 @@ class HipVecOps(object):
                                           dx.data_ptr(), self.linear_flags if flags is None else flags))
         return gz, dx
 
+    # ---- the backward of a bare Linear layer with respect to its input (pn_linear_dx, csrc/pn_linear.hip)
+    def linear_dx_supported(self, rows, out_f, in_f):
+        return bool(self.lib.pn_linear_dx_supported(self.code, rows, out_f, in_f))
+
+    def linear_dx(self, g, w, dx=None, flags=None):
+        """dx = g w; g (rows, out_f), w (out_f, in_f): contiguous fp32 on this device.  The bits of linear_bwd(g, zeros, w)[1].  Refused
+        (PnError), never run another way, outside pn_linear_dx_supported, for an fp64 state, and where dx shares memory with g or w.
+        flags: pn_linear_dx_form's (default: linear_flags)."""
+        rows, out_f = g.shape
+        in_f = w.shape[1]
+        for v in (g, w, dx):
+            if v is not None and not (v.is_contiguous() and v.dtype == torch.float32 and v.device == g.device and g.is_cuda):
+                raise PnError("pn_linear_dx: contiguous fp32 tensors on one HIP device")
+        if w.shape[0] != out_f:
+            raise PnError("pn_linear_dx: g (rows, out_f), w (out_f, in_f)")
+        if dx is None:
+            dx = torch.empty((rows, in_f), dtype=g.dtype, device=g.device)
+        elif tuple(dx.shape) != (rows, in_f):
+            raise PnError("pn_linear_dx: dx (rows, in_f)")
+        check(self.lib.pn_linear_dx_form(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), w.data_ptr(), dx.data_ptr(),
+                                         self.linear_flags if flags is None else flags))
+        return dx
+
     # ---- dense output (-pn_output_times interpolate; csrc/pn_dense.hip)
     dense_flags = _lib.PN_DENSE_NONTEMPORAL      # output rows are not read again by the sweep: non-temporal stores
 

@@ -927,7 +927,10 @@ struct BwdLoads {
   f32x4 g, a, w0, w1;
 };
 
-template <bool RAGGED, bool PIPE>
+// BARE: the layer has no activation behind it (pn_linear_dx): z = g -- its bits unchanged --, no load of a, nothing stored to gz (q.a and
+// q.gz are null and never touched); the tile map, the W images, the order of the products and the exchange are the tanh body's, so dx has
+// the bits this body gives for a == 0 (g (1 - 0 0) is g exactly, with or without the fma).
+template <bool RAGGED, bool PIPE, bool BARE = false>
 __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   static_assert(!(RAGGED && PIPE), "the pipelined loop loads without tests");
   constexpr int AROWB = 2 * FK, APART = FM * AROWB;              // gz: [64 rows][32 bf16], 4 KB per part
@@ -948,7 +951,7 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   const int nslab = out_f / FK;
   const bool aok = !RAGGED || tm * FM + lrow < rows;
   const bool wok = !RAGGED || tn * FN + sub * 64 + kc * 4 < in_f;
-  const bool keep = tn == 0 && aok;                              // this workgroup writes gz
+  const bool keep = !BARE && tn == 0 && aok;                     // this workgroup writes gz
   const size_t aoff = (size_t)(tm * FM + lrow) * out_f + lc * 4;
   const float *wp = W + (size_t)krow * in_f + tn * FN + sub * 64 + kc * 4;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -959,7 +962,7 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
 
   auto gload = [&](int slab) {
     gv = aok ? *reinterpret_cast<const f32x4 *>(G + aoff + slab * FK) : zero4;
-    av = aok ? *reinterpret_cast<const f32x4 *>(A + aoff + slab * FK) : zero4;
+    if constexpr (!BARE) av = aok ? *reinterpret_cast<const f32x4 *>(A + aoff + slab * FK) : zero4;
     wv0 = wok ? *reinterpret_cast<const f32x4 *>(wp + (size_t)(slab * FK) * in_f) : zero4;
     wv1 = wok ? *reinterpret_cast<const f32x4 *>(wp + (size_t)(slab * FK + 16) * in_f) : zero4;
   };
@@ -974,10 +977,12 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   };
   auto lstore = [&](int slab, int buf) {
     char *b = smem + buf * BUF;
-    f32x4 z;                                                     // here, not at the load: the products would wait for the loads in front of the MFMAs
+    f32x4 z = gv;                                                // here, not at the load: the products would wait for the loads in front of the MFMAs
+    if constexpr (!BARE) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) z[e] = gv[e] * (1.f - av[e] * av[e]);
-    if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
+      for (int e = 0; e < 4; ++e) z[e] = gv[e] * (1.f - av[e] * av[e]);
+      if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
+    }
     split_store(z, b + aso, APART);
     split_store(wv0, b + 3 * APART + wso, WPART);
     split_store(wv1, b + 3 * APART + wso + 16 * WROWB, WPART);
@@ -1018,11 +1023,11 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
     // stays one basic block for the interleave)
     auto run = [&](auto keep_c) {
       constexpr bool KEEP = decltype(keep_c)::value;
-      pipelined_slabs<15, 4, BwdLoads>(
+      pipelined_slabs<15, BARE ? 3 : 4, BwdLoads>(
           nslab, BUF, acc0, acc1,
           [&](BwdLoads &l, int slab) {
             l.g = *reinterpret_cast<const f32x4 *>(G + aoff + slab * FK);
-            l.a = *reinterpret_cast<const f32x4 *>(A + aoff + slab * FK);
+            if constexpr (!BARE) l.a = *reinterpret_cast<const f32x4 *>(A + aoff + slab * FK);
             l.w0 = *reinterpret_cast<const f32x4 *>(wp + (size_t)(slab * FK) * in_f);
             l.w1 = *reinterpret_cast<const f32x4 *>(wp + (size_t)(slab * FK + 16) * in_f);
           },
@@ -1030,8 +1035,8 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
             char *b = smem + boff;
             // gz as the plain loop forms it, spelled out: 1 - a a in one fma, then ONE rounded product.  Left to contraction, the product
             // here is fused into the split's first subtraction (fma(g, t, -hi)): other mid and lo terms, other bits in dx
-            f32x4 z;
-            {
+            f32x4 z = l.g;
+            if constexpr (!BARE) {
 #pragma clang fp contract(off)
 #pragma unroll
               for (int e = 0; e < 4; ++e) z[e] = l.g[e] * __builtin_fmaf(-l.a[e], l.a[e], 1.f);
@@ -1048,7 +1053,9 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
             f.b1h = wfrag(wb, 32), f.b1m = wfrag(wb + WPART, 32), f.b1l = wfrag(wb + 2 * WPART, 32);
           });
     };
-    if (keep)
+    if constexpr (BARE)
+      run(std::false_type{});
+    else if (keep)
       run(std::true_type{});
     else
       run(std::false_type{});
@@ -1086,6 +1093,10 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false>(a); }
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false>(a); }
 __global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true>(a); }
+// the bare ones (pn_linear_dx): a and gz of BwdArgs are null
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_dx_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, true>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_dx_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, true>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_dx_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, true>(a); }
 
 int cu_count() {
   static int n = 0;             // (the calling thread's current device; every device of a node is the same part)
@@ -1268,6 +1279,31 @@ int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
   const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (out_f / FK) % 2 != 0;      // (the pipelined loop takes an even number of slabs)
   auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : (plain ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
   return pn::launch("pn_linear_bwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
+}
+
+int pn_linear_dx_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f) { return pn_linear_bwd_supported(dtype, rows, out_f, in_f); }
+
+int pn_linear_dx(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *w, void *dx) {
+  return pn_linear_dx_form(stream, dtype, rows, out_f, in_f, g, w, dx, 0);
+}
+
+int pn_linear_dx_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *w, void *dx, int flags) {
+  if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_dx_form: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
+  if (!pn_linear_dx_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_dx: unsupported dtype or shape (see pn_linear_dx_supported)");
+  if (g == nullptr || w == nullptr || dx == nullptr) return pn::fail("pn_linear_dx: null operand");
+  if (!pn::aligned16(g, w, dx)) return pn::fail("pn_linear_dx: operands must be 16-byte aligned");
+  const size_t ng = (size_t)rows * (size_t)out_f * sizeof(float), nw = (size_t)out_f * (size_t)in_f * sizeof(float),
+               nx = (size_t)rows * (size_t)in_f * sizeof(float);
+  if (overlap(dx, nx, g, ng) || overlap(dx, nx, w, nw)) return pn::fail("pn_linear_dx: dx must not alias g or w (other workgroups still read them)");
+  BwdArgs q;
+  q.g = (const float *)g, q.a = nullptr, q.w = (const float *)w, q.gz = nullptr, q.dx = (float *)dx;
+  q.rows = (int)rows, q.out_f = (int)out_f, q.in_f = (int)in_f;
+  q.ntn = (int)((in_f + FN - 1) / FN);
+  const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)q.ntn;
+  const bool ragged = rows % FM != 0 || in_f % FN != 0;
+  const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (out_f / FK) % 2 != 0;      // (the pipelined loop takes an even number of slabs)
+  auto kern = ragged ? pn_linear_dx_kernel_f32x3_ragged : (plain ? pn_linear_dx_kernel_f32x3 : pn_linear_dx_kernel_f32x3_pipe);
+  return pn::launch("pn_linear_dx", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
 }
 
 }  // extern "C"

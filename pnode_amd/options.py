@@ -19,6 +19,10 @@ in place: the backward lives in the pair's ``autograd.Function``.
 ``-pn_linear_form auto|plain`` (read there too): ``auto``, the default, lets ``pn_linear_fwd`` and ``pn_linear_bwd`` take the pipelined
 K loop on aligned shapes; ``plain`` keeps the plain loop everywhere (``PN_LINEAR_FORM_PLAIN``).  The two give the same bits: the option
 is for timing one against the other inside one tree.
+``-pn_linear_bare 0|1`` (read there too): ``0``, the default, leaves func's bare ``nn.Linear`` layers -- no ``nn.Tanh`` behind them: the
+head of every ``... -> Linear`` net -- to the stock module; ``1`` runs the eligible ones through ``pn_linear_fwd`` with the identity and
+their backward ``dx = g W`` through ``pn_linear_dx`` (``-pn_linear_bwd 0`` keeps ``matmul``), inside the solver's own evaluations, under
+the rules of the pairs.  ``ode.linear_bare`` reports what runs.  ``-pn_linear_fwd 0`` switches this off with the pairs.
 """
 import os
 import shlex
