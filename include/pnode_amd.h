@@ -227,8 +227,10 @@ int pn_linear_wgrad_group(void *stream, int dtype, int64_t rows, int npairs, con
 int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f, void *pw, void *pb, void *mu_w, void *mu_b);
 
 /* The forward of a Linear layer with its activation in one launch (csrc/pn_linear.hip):  y = act(x w^T + b)  for x rows x in_f, w out_f x
- * in_f, b out_f values or NULL, y rows x out_f, all row-major fp32; act = PN_ACT_IDENTITY or PN_ACT_TANH (tanhf of the device library,
- * applied in fp32 to the biased sum: exactly +-1 once it saturates, NaN for NaN).  The product is the split-bf16 one of pn_linear_wgrad
+ * in_f, b out_f values or NULL, y rows x out_f, all row-major fp32; act = PN_ACT_IDENTITY, PN_ACT_TANH (tanhf of the device library,
+ * applied in fp32 to the biased sum: exactly +-1 once it saturates, NaN for NaN) or PN_ACT_RELU (of the biased sum z: z where z > 0, a
+ * NaN stays that NaN, everything else -- -0 too -- is +0; so y under PN_ACT_RELU is relu of the y under PN_ACT_IDENTITY in the same
+ * form, value for value); any other act is refused, nothing launched.  The product is the split-bf16 one of pn_linear_wgrad
  * (three exact bf16 terms per operand, the six largest cross products, fp32 accumulation on v_mfma_f32_32x32x16_bf16; an infinite
  * operand gives NaN); one workgroup owns a 64 x 128 tile of y over all of in_f and writes it once: no atomics, no work buffers, the
  * same bits on every launch.  x, w, y non-NULL and 16-byte aligned, b 4-byte aligned; y shares no byte with x, w or b (other workgroups
@@ -238,6 +240,7 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
  * through the library. */
 #define PN_ACT_IDENTITY 0
 #define PN_ACT_TANH 1
+#define PN_ACT_RELU 2
 int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
 int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
                   void *y);
@@ -268,6 +271,17 @@ int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
                   void *dx);
 int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w,
                        void *gz, void *dx, int flags);
+/* pn_linear_bwd_form with the pair's activation as an argument: the shape rules (pn_linear_bwd_supported), the null, alignment and aliasing
+ * refusals and the flags are pn_linear_bwd_form's.  act == PN_ACT_TANH launches exactly what pn_linear_bwd_form launches.
+ * act == PN_ACT_RELU is the backward of an nn.Linear -> nn.ReLU pair, a its output:
+ *   gz[r][k] = a[r][k] <= 0 ? +0 : g[r][k]      dx[r][n] = sum_k gz[r][k] w[k][n]
+ * -- aten.threshold_backward(g, a, 0) bit for bit: a NaN in a lets g through, a == +0 or -0 gives +0, and no arithmetic touches g, so
+ * every element of gz is g's bits or +0.  dx has the bits of pn_linear_dx fed that gz, in every form (the prologue sits in front of the
+ * bare body's split, tile map and product order).  Replaces, in the reverse sweep's stage VJPs, the threshold_backward kernel and the
+ * library GEMM of the pair (with -pn_linear_bare 1: threshold_backward and pn_linear_dx, which reads gz back).
+ * PN_ACT_IDENTITY is refused (no prologue, no gz: use pn_linear_dx); so is any other value, and an unknown flag; nothing is launched. */
+int pn_linear_bwd_act(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
+                      void *gz, void *dx, int flags);
 
 /* The backward of a BARE Linear layer -- no activation behind it -- with respect to its input (csrc/pn_linear.hip): for g rows x out_f (the
  * cotangent at the layer's output) and w out_f x in_f as it lies, row-major fp32,

@@ -45,7 +45,7 @@ class WgradPair(ctypes.Structure):
 PN_WGRAD_MAX_PAIRS = 8
 PN_WGRAD_EXACT_FP32 = 1
 PN_WGRAD_TILE_64 = 2
-PN_ACT_IDENTITY, PN_ACT_TANH = 0, 1
+PN_ACT_IDENTITY, PN_ACT_TANH, PN_ACT_RELU = 0, 1, 2
 PN_LINEAR_FORM_PLAIN = 1      # pn_linear_fwd_form / pn_linear_bwd_form flag: the plain K loop on an aligned shape too
 PN_ABI_VERSION = 4
 PN_DENSE_MAX_POW = 4          # columns of a continuous extension's P matrix (pn_tableau_dense)
@@ -147,6 +147,7 @@ PROTOTYPES = {
     "pn_linear_bwd_supported": (_i, [_i, _i64, _i64, _i64]),
     "pn_linear_bwd": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pn_linear_bwd_form": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i]),
+    "pn_linear_bwd_act": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     "pn_linear_dx_supported": (_i, [_i, _i64, _i64, _i64]),
     "pn_linear_dx": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp]),
     "pn_linear_dx_form": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i]),

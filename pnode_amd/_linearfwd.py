@@ -38,7 +38,17 @@ head of every ``... -> Linear`` net, a Linear in front of a ReLU or of a subclas
 ``_bwd_fusable`` minus everything about ``a``, else ``matmul``; ``(g, x)`` then goes to ``LinearParamGrads._grad_hook`` exactly as a
 pair's ``(g_z, x)`` does.  A container whose only eligible members are bare layers is active too.  The self-checks are the pair's in
 the pair's measures (forward against ``F.linear``, ``dx`` against ``matmul``); a miss switches off the bare path, or its backward,
-only -- the pairs are not touched.  The bare layers are kept in ``LinearFwd.bare``, beside ``plans``."""
+only -- the pairs are not touched.  The bare layers are kept in ``LinearFwd.bare``, beside ``plans``.
+
+ReLU pairs (``-pn_linear_relu 0|1``, default ``0``: nothing below happens, a Linear in front of a ReLU stays a stock module or a bare
+layer).  With ``1`` two consecutive children ``nn.Linear``, exactly ``nn.ReLU`` (either ``inplace``: the module is not called) of an
+eligible container are a pair under the static and hook rules of a tanh pair, kept in ``LinearFwd.relu``; such a Linear is no bare layer.
+The pair runs through ``_LinearTanh`` with ``call.relu``: forward ``pn_linear_fwd`` with ``PN_ACT_RELU`` under ``_fusable``; backward
+``g_z = threshold_backward(g, a, 0)`` and ``dx = g_z W`` in one launch (``pn_linear_bwd_act``) under ``_bwd_fusable`` on a backend with
+``linear_relu``, else ``threshold_backward`` and ``matmul``; ``(g_z, x)`` goes to ``LinearParamGrads._grad_hook`` as a tanh pair's.
+Self-checks of their own: the forward against ``torch.relu(F.linear)`` in the pair's measure; ``g_z`` must be ``threshold_backward``'s
+bit for bit (the kernel does no arithmetic on it), ``dx`` in the pair's measure.  A miss switches off the ReLU pairs, or their backward,
+only.  ``n_relu`` / ``n_relu_bwd`` count them; ``n_fused`` / ``n_fused_bwd`` stay the tanh pairs'."""
 import contextlib
 import warnings
 import weakref
@@ -77,14 +87,14 @@ def _user_hooked(m):
     return False
 
 
-def _static_why(seq, kids, lin, act, index, owners):
-    """The static half of the eligibility rules for the Linear `lin` (and the Tanh `act` behind it; None for a bare layer) among the
-    children `kids` of `seq`: None, or the reason as a string."""
+def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
+    """The static half of the eligibility rules for the Linear `lin` (and the activation `act` behind it, exactly a `kind`: nn.Tanh or
+    nn.ReLU; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
     mods = (lin,) if act is None else (lin, act)
     if type(seq) is not nn.Sequential or "forward" in seq.__dict__:
         return "the container's forward is not nn.Sequential's own"
-    if type(lin) is not nn.Linear or (act is not None and type(act) is not nn.Tanh):
-        return "a subclass of nn.Linear or nn.Tanh"
+    if type(lin) is not nn.Linear or (act is not None and type(act) is not kind):
+        return "a subclass of nn.Linear or nn.%s" % kind.__name__
     if any("forward" in m.__dict__ for m in mods):
         return "an instance-level forward on the layer"
     why = None
@@ -100,10 +110,13 @@ def _static_why(seq, kids, lin, act, index, owners):
     return why
 
 
-def find_layers(func, params):
+def find_layers(func, params, relu=False):
     """(plans, refused, bare): [(sequential, {index of the Linear child: (linear, tanh)})] of func; {class name of a container: reason}
     for the Linear -> Tanh pairs that cannot be fused (what -pn_linear_fwd 1 warns about); and [(sequential, {index of the child:
-    linear})] for the bare layers -- exactly nn.Linear, opening no fused pair, under the same static rules (-pn_linear_bare 1)."""
+    linear})] for the bare layers -- exactly nn.Linear, opening no fused pair, under the same static rules (-pn_linear_bare 1).
+    relu (-pn_linear_relu 1): two consecutive children nn.Linear, nn.ReLU are a pair too, under the rules of a tanh pair -- (linear, relu)
+    in `plans`, told from a tanh pair by its second member, and such a Linear is no bare layer; a ReLU pair that cannot be fused is in
+    `refused` under the key (class name of the container, "ReLU").  Without it the three are what they were before there was the option."""
     plans, refused, bare = [], {}, []
     if not isinstance(func, nn.Module):
         return plans, refused, bare
@@ -122,13 +135,19 @@ def find_layers(func, params):
         pairs = {}
         for i in range(len(kids) - 1):
             lin, act = kids[i], kids[i + 1]
-            if not (isinstance(lin, nn.Linear) and isinstance(act, nn.Tanh)):
+            if not isinstance(lin, nn.Linear):
                 continue
-            why = _static_why(seq, kids, lin, act, index, owners)
+            if isinstance(act, nn.Tanh):
+                kind, key = nn.Tanh, type(seq).__name__
+            elif relu and isinstance(act, nn.ReLU):
+                kind, key = nn.ReLU, (type(seq).__name__, "ReLU")
+            else:
+                continue
+            why = _static_why(seq, kids, lin, act, index, owners, kind)
             if why is None:
                 pairs[i] = (lin, act)
             else:
-                refused.setdefault(type(seq).__name__, why)
+                refused.setdefault(key, why)
         if pairs:
             plans.append((seq, pairs))
         alone = {i: m for i, m in enumerate(kids)
@@ -145,13 +164,21 @@ def find_pairs(func, params):
 
 class _Call(object):
     """What one fused call carries into its backward."""
-    __slots__ = ("owner", "module", "grads", "ev", "version")
+    __slots__ = ("owner", "module", "grads", "ev", "version", "relu")
+
+
+def _shaped(y2, shape):
+    """The kernel's (rows, out_f) result in the shape of the layer's output.  A 2-D input gets the tensor itself: a view made inside a
+    Function's forward may not be written in place, and an nn.ReLU(inplace=True) behind a bare layer does just that."""
+    return y2 if y2.shape == shape else y2.view(shape)
 
 
 class _LinearTanh(torch.autograd.Function):
+    """A Linear -> Tanh pair or, with call.relu (-pn_linear_relu 1), a Linear -> ReLU pair: the same structure, the other activation."""
     @staticmethod
     def forward(ctx, x, w, b, call):
-        a = call.owner.kernel(x.reshape(-1, w.shape[1]), w, b).view(x.shape[:-1] + (w.shape[0],))
+        kernel = call.owner.kernel_relu if call.relu else call.owner.kernel
+        a = _shaped(kernel(x.reshape(-1, w.shape[1]), w, b), x.shape[:-1] + (w.shape[0],))
         ctx.save_for_backward(x, w, a)
         ctx.call = call
         ctx.has_bias = b is not None
@@ -161,12 +188,12 @@ class _LinearTanh(torch.autograd.Function):
     def backward(ctx, g):
         x, w, a = ctx.saved_tensors
         call = ctx.call
-        # both in one launch (pn_linear_bwd) where LinearFwd._bwd_fusable allows it, else the two torch operations
-        fused = call.owner._backward(g, a, w) if ctx.needs_input_grad[0] else None
+        # both in one launch (pn_linear_bwd, pn_linear_bwd_act) where LinearFwd._bwd_fusable allows it, else the two torch operations
+        fused = call.owner._backward(g, a, w, call.relu) if ctx.needs_input_grad[0] else None
         if fused is not None:
             g_z, dx = fused
         else:
-            g_z = torch.ops.aten.tanh_backward(g, a)
+            g_z = torch.ops.aten.threshold_backward(g, a, 0) if call.relu else torch.ops.aten.tanh_backward(g, a)
             dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
         dw, db = _param_grads(ctx, call, g_z, x, w)
         return dx, dw, db, None
@@ -194,7 +221,7 @@ class _Linear(torch.autograd.Function):
     """A bare layer (-pn_linear_bare 1): _LinearTanh without the activation."""
     @staticmethod
     def forward(ctx, x, w, b, call):
-        y = call.owner.kernel_bare(x.reshape(-1, w.shape[1]), w, b).view(x.shape[:-1] + (w.shape[0],))
+        y = _shaped(call.owner.kernel_bare(x.reshape(-1, w.shape[1]), w, b), x.shape[:-1] + (w.shape[0],))
         ctx.save_for_backward(x, w)
         ctx.call = call
         ctx.has_bias = b is not None
@@ -247,26 +274,55 @@ class LinearFwd(object):
         self.bare_bwd_checked = False
         self.n_bare_bwd = 0        # bare backwards that ran pn_linear_dx
         self._ok_dx = {}           # (rows, out_f, in_f) -> pn_linear_dx_supported
+        # the Linear -> ReLU pairs (-pn_linear_relu 0|1): a map, flags and counters of their own, as the bare layers'
+        self.relu = []             # [(sequential, {child index: (linear, relu)})]
+        self.relu_mode = "0"
+        self.relu_disabled = False      # the ReLU forward check failed
+        self.relu_why = None
+        self.relu_checked = False
+        self.n_relu = 0            # ReLU pair calls that ran as one launch
+        self.relu_bwd_disabled = False  # the ReLU backward check failed (the ReLU forward stays)
+        self.relu_bwd_why = None
+        self.relu_bwd_checked = False
+        self.n_relu_bwd = 0        # ReLU pair backwards that ran as one launch (pn_linear_bwd_act)
+        self._warned_relu = False
+        self._warned_relu_bwd = False
 
-    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0"):
-        """Find the eligible pairs of `func` (and, with bare_mode "1", its bare layers); returns True when there is at least one."""
+    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0", relu_mode="0"):
+        """Find the eligible pairs of `func` (and, with bare_mode "1", its bare layers; with relu_mode "1", its Linear -> ReLU pairs);
+        returns True when there is at least one."""
         self.mode = mode
         self.bwd_mode = bwd_mode
         self.bare_mode = bare_mode
-        self.plans, refused, self.bare = find_layers(func, params)
-        if mode == "1" and refused and not self._warned:
-            self._warned = True
-            for cls, why in refused.items():
-                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> Tanh pair of %s runs the stock modules: %s" % (cls, why), RuntimeWarning)
-        return bool(self.plans) or self.bare_active
+        self.relu_mode = relu_mode
+        found, refused, self.bare = find_layers(func, params, relu_mode == "1")
+        self.plans, self.relu = [], []
+        for seq, pairs in found:
+            for kind, plans in ((nn.Tanh, self.plans), (nn.ReLU, self.relu)):
+                mine = {i: p for i, p in pairs.items() if type(p[1]) is kind}
+                if mine:
+                    plans.append((seq, mine))
+        if mode == "1" and refused:
+            for key, why in refused.items():
+                cls, name = key if isinstance(key, tuple) else (key, "Tanh")
+                if self._warned_relu if name == "ReLU" else self._warned:
+                    continue
+                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair of %s runs the stock modules: %s" % (name, cls, why), RuntimeWarning)
+            self._warned = self._warned or any(not isinstance(key, tuple) for key in refused)
+            self._warned_relu = self._warned_relu or any(isinstance(key, tuple) for key in refused)
+        return bool(self.plans) or self.bare_active or self.relu_active
 
     @property
     def bare_active(self):
         return self.bare_mode == "1" and bool(self.bare) and not self.bare_disabled
 
     @property
+    def relu_active(self):
+        return self.relu_mode == "1" and bool(self.relu) and not self.relu_disabled
+
+    @property
     def active(self):
-        return (bool(self.plans) and not self.disabled) or self.bare_active
+        return (bool(self.plans) and not self.disabled) or self.bare_active or self.relu_active
 
     # the one place the device is touched: tests of the eligibility rules replace it by the torch expression
     def kernel(self, x2, w, b):
@@ -274,6 +330,9 @@ class LinearFwd(object):
 
     def kernel_bare(self, x2, w, b):
         return self._ode()._ops.linear_fwd(x2, w, b, False)
+
+    def kernel_relu(self, x2, w, b):
+        return self._ode()._ops.linear_fwd(x2, w, b, False, act="relu")
 
     def supported(self, rows, out_f, in_f):
         key = (rows, out_f, in_f)
@@ -283,10 +342,14 @@ class LinearFwd(object):
             ok = self._ok[key] = bool(hasattr(ops, "linear_fwd_supported") and ops.linear_fwd_supported(rows, out_f, in_f))
         return ok
 
-    def _refuse(self, why):
-        if self.mode == "1" and not self._warned:
-            self._warned = True
-            warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> Tanh pair runs the stock modules: %s" % why, RuntimeWarning)
+    def _refuse(self, why, relu=False):
+        if self.mode == "1" and not (self._warned_relu if relu else self._warned):
+            if relu:
+                self._warned_relu = True
+            else:
+                self._warned = True
+            warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair runs the stock modules: %s" % ("ReLU" if relu else "Tanh", why),
+                          RuntimeWarning)
         return None
 
     def _fusable(self, lin, x):
@@ -307,15 +370,18 @@ class LinearFwd(object):
             return "outside pn_linear_fwd_supported"
         return None
 
-    def _check(self, x, w, b, a, bare=False):
+    def _check(self, x, w, b, a, bare=False, relu=False):
         """First fused call of a solver: the pair through torch as well.  bare: a bare layer's first call, against F.linear in the same
-        measure; a miss switches off the bare path only."""
-        done = "bare_checked" if bare else "checked"
+        measure; a miss switches off the bare path only.  relu: a ReLU pair's first call, against torch.relu(F.linear) in the same
+        measure (ReLU is 1-Lipschitz: the bare layer's bar carries over); a miss switches off the ReLU pairs only."""
+        done = "bare_checked" if bare else ("relu_checked" if relu else "checked")
         setattr(self, done, True)
         with torch.no_grad():
             x2 = x.reshape(-1, w.shape[1])
             ref = F.linear(x2, w, b)
-            if not bare:
+            if relu:
+                ref = torch.relu(ref)
+            elif not bare:
                 ref = torch.tanh(ref)
             scale = x2.abs() @ w.abs().t()
             if b is not None:
@@ -330,6 +396,11 @@ class LinearFwd(object):
                 self.bare_disabled = True
                 self.bare_why = "pn_linear_fwd and F.linear differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
                 warnings.warn("pnode_amd: the bare Linear layers run the stock modules for this solver: " + self.bare_why, RuntimeWarning)
+                return False
+            if relu:
+                self.relu_disabled = True
+                self.relu_why = "pn_linear_fwd and torch.relu(F.linear) differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
+                warnings.warn("pnode_amd: the fused Linear -> ReLU forward is switched off for this solver: " + self.relu_why, RuntimeWarning)
                 return False
             self.disabled = True
             self.why = "pn_linear_fwd and torch.tanh(F.linear) differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
@@ -350,17 +421,26 @@ class LinearFwd(object):
             ok = cache[key] = bool(hasattr(ops, entry + "_supported") and getattr(ops, entry + "_supported")(rows, out_f, in_f))
         return ok
 
-    def _bwd_fusable(self, g, a, w):
+    def kernel_bwd_relu(self, g2, a2, w):
+        return self._ode()._ops.linear_bwd(g2, a2, w, act="relu")
+
+    def _bwd_fusable(self, g, a, w, relu=False):
         """None, or the reason (a string) this backward runs the torch operations.  a: the pair's output; None for a bare layer
-        (pn_linear_dx: the same rules minus everything about a)."""
+        (pn_linear_dx: the same rules minus everything about a).  relu: a ReLU pair (pn_linear_bwd_act: the rules of a tanh pair, and
+        a backend with `linear_relu`)."""
         bare = a is None
         entry = "linear_dx" if bare else "linear_bwd"
         ode = self._ode()
         if ode is None or not hasattr(ode._ops, entry):
             return "the backend has no " + entry
+        if relu and not getattr(ode._ops, "linear_relu", False):
+            return "the backend has no linear_relu"
         if self.bwd_mode == "0":
             return "-pn_linear_bwd 0"
-        if self.bare_bwd_disabled if bare else self.bwd_disabled:
+        if relu:
+            if self.relu_bwd_disabled:
+                return self.relu_bwd_why
+        elif self.bare_bwd_disabled if bare else self.bwd_disabled:
             return self.bare_bwd_why if bare else self.bwd_why
         if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != w.device or g.device.type != self.device_type \
                 or (g.dim() < 1 or g.shape[-1] != w.shape[0] if bare else g.shape != a.shape):
@@ -400,24 +480,54 @@ class LinearFwd(object):
             return gz_t, dx_t
         return None
 
-    def _backward(self, g, a, w):
-        """(g_z, dx) of one pair by pn_linear_bwd, or None: the caller runs tanh_backward and matmul."""
-        why = self._bwd_fusable(g, a, w)
+    def _check_relu_bwd(self, g2, a2, w, gz, dx):
+        """First fused backward of a ReLU pair of a solver: both results through torch as well.  gz has no arithmetic in it: it must be
+        threshold_backward's bit for bit; dx to CHECK_TOL of |gz| |w| (the tanh pair's bar in its measure).  Returns None, or the torch
+        results after switching the fused ReLU backward -- only it -- off."""
+        self.relu_bwd_checked = True
+        gz_t = torch.ops.aten.threshold_backward(g2, a2, 0)
+        dx_t = torch.matmul(gz_t, w)
+        scale = gz_t.abs() @ w.abs()
+        ok = torch.isfinite(dx_t) & (scale > 0)
+        bad_z = not torch.equal(gz.view(torch.int32), gz_t.view(torch.int32))
+        if not bad_z and not bool(ok.any()):
+            self.relu_bwd_checked = False          # nothing to judge dx by: the next call is checked
+            return None
+        err = float(((dx - dx_t).abs() / scale)[ok].max()) if bool(ok.any()) else 0.0
+        if bad_z or not err <= CHECK_TOL:
+            self.relu_bwd_disabled = True
+            self.relu_bwd_why = "pn_linear_bwd_act and threshold_backward + matmul differ: " + (
+                "g_z is not threshold_backward's bit for bit" if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
+            warnings.warn("pnode_amd: the fused Linear -> ReLU backward is switched off for this solver: " + self.relu_bwd_why, RuntimeWarning)
+            return gz_t, dx_t
+        return None
+
+    def _backward(self, g, a, w, relu=False):
+        """(g_z, dx) of one pair by pn_linear_bwd (relu: pn_linear_bwd_act), or None: the caller runs tanh_backward (threshold_backward)
+        and matmul."""
+        why = self._bwd_fusable(g, a, w, relu)
         if why is not None:
-            if self.bwd_mode == "1" and not self._warned_bwd:
-                self._warned_bwd = True
-                warnings.warn("pnode_amd: -pn_linear_bwd 1: the backward of a Linear -> Tanh pair runs the torch operations: %s" % why, RuntimeWarning)
+            if self.bwd_mode == "1" and not (self._warned_relu_bwd if relu else self._warned_bwd):
+                if relu:
+                    self._warned_relu_bwd = True
+                else:
+                    self._warned_bwd = True
+                warnings.warn("pnode_amd: -pn_linear_bwd 1: the backward of a Linear -> %s pair runs the torch operations: %s"
+                              % ("ReLU" if relu else "Tanh", why), RuntimeWarning)
             return None
         out_f, in_f = w.shape
         g2, a2 = g.reshape(-1, out_f), a.reshape(-1, out_f)
         with torch.no_grad():
-            gz, dx = self.kernel_bwd(g2, a2, w)
-            if not self.bwd_checked and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
-                torch_way = self._check_bwd(g2, a2, w, gz, dx)
+            gz, dx = self.kernel_bwd_relu(g2, a2, w) if relu else self.kernel_bwd(g2, a2, w)
+            if not (self.relu_bwd_checked if relu else self.bwd_checked) and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
+                torch_way = self._check_relu_bwd(g2, a2, w, gz, dx) if relu else self._check_bwd(g2, a2, w, gz, dx)
                 if torch_way is not None:
                     gz, dx = torch_way
                     return gz.view(g.shape), dx.view(g.shape[:-1] + (in_f,))
-        self.n_fused_bwd += 1
+        if relu:
+            self.n_relu_bwd += 1
+        else:
+            self.n_fused_bwd += 1
         return gz.view(g.shape), dx.view(g.shape[:-1] + (in_f,))
 
     # ---- the backward of a bare layer (called from _Linear.backward)
@@ -468,6 +578,16 @@ class LinearFwd(object):
         return "fused (%d layers; %d forward, %d backward calls so far)" % (sum(len(b) for _, b in self.bare), self.n_bare, self.n_bare_bwd)
 
     @property
+    def relu_status(self):
+        if self.relu_mode != "1":
+            return "off (-pn_linear_relu 0)"
+        if not self.relu:
+            return "stock modules (no eligible Linear -> ReLU pair)"
+        if self.relu_disabled:
+            return "stock modules (%s)" % self.relu_why
+        return "fused (%d pairs; %d forward, %d backward calls so far)" % (sum(len(p) for _, p in self.relu), self.n_relu, self.n_relu_bwd)
+
+    @property
     def bwd_status(self):
         if self.bwd_mode == "0":
             return "torch operations (-pn_linear_bwd 0)"
@@ -479,23 +599,28 @@ class LinearFwd(object):
         return "fused (%d calls so far)" % self.n_fused_bwd
 
     def _pair(self, lin, act, x, grads):
+        """One pair: Linear -> Tanh or, where `act` is an nn.ReLU, Linear -> ReLU (its module is not called: either `inplace` will do)."""
+        relu = type(act) is nn.ReLU
         why = self._fusable(lin, x)
         if why is not None:
-            self._refuse(why)
+            self._refuse(why, relu)
             return act(lin(x))
         w, b = lin.weight, lin.bias
         ev = grads.recording if grads is not None else None
         if ev is not None and not grads.note_fused(lin, x):
             ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
         call = _Call()
-        call.owner, call.module, call.grads, call.ev, call.version = self, lin, grads, ev, x._version
+        call.owner, call.module, call.grads, call.ev, call.version, call.relu = self, lin, grads, ev, x._version, relu
         a = _LinearTanh.apply(x, w, b, call)
-        if not self.checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
-            if not self._check(x.detach(), w.detach(), None if b is None else b.detach(), a.detach()):
+        if not (self.relu_checked if relu else self.checked) and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            if not self._check(x.detach(), w.detach(), None if b is None else b.detach(), a.detach(), relu=relu):
                 return act(lin(x))
         if ev is not None and a.grad_fn is not None:
             ev.through[a.grad_fn] = x.grad_fn     # Evaluation.clean passes the pair along its input edge only
-        self.n_fused += 1
+        if relu:
+            self.n_relu += 1
+        else:
+            self.n_fused += 1
         return a
 
     def _bare(self, lin, x, grads):
@@ -523,7 +648,8 @@ class LinearFwd(object):
             i, n = 0, len(kids)
             while i < n:
                 p = pairs.get(i)
-                if p is not None and i + 1 < n and kids[i] is p[0] and kids[i + 1] is p[1] and not self.disabled:
+                if p is not None and i + 1 < n and kids[i] is p[0] and kids[i + 1] is p[1] \
+                        and not (self.relu_disabled if type(p[1]) is nn.ReLU else self.disabled):
                     inp = self._pair(p[0], p[1], inp, grads)
                     i += 2
                 elif alone.get(i) is kids[i] and not self.bare_disabled:
@@ -536,11 +662,17 @@ class LinearFwd(object):
         return forward
 
     def _containers(self):
-        """[(sequential, its pairs, its bare layers)]: the pairs while their forward is on, the bare layers with -pn_linear_bare 1."""
+        """[(sequential, its pairs, its bare layers)]: the pairs while their forward is on (the ReLU pairs with -pn_linear_relu 1), the
+        bare layers with -pn_linear_bare 1."""
         out = {}
         if not self.disabled:
             for seq, pairs in self.plans:
                 out[id(seq)] = (seq, pairs, {})
+        if self.relu_active:
+            for seq, pairs in self.relu:
+                both = dict(out[id(seq)][1]) if id(seq) in out else {}      # (a copy: the container's tanh pairs stay their own map)
+                both.update(pairs)
+                out[id(seq)] = (seq, both, {})
         if self.bare_active:
             for seq, alone in self.bare:
                 out[id(seq)] = (seq, out[id(seq)][1] if id(seq) in out else {}, alone)
@@ -557,8 +689,8 @@ class LinearFwd(object):
                     if "forward" in seq.__dict__ or type(seq) is not nn.Sequential:
                         continue
                     if _user_hooked(seq) or any(_user_hooked(m) for pr in pairs.values() for m in pr):
-                        if pairs:
-                            self._refuse("a forward, pre-forward or backward hook on the pair or its container")
+                        for relu in sorted({type(pr[1]) is nn.ReLU for pr in pairs.values()}):
+                            self._refuse("a forward, pre-forward or backward hook on the pair or its container", relu)
                         if _user_hooked(seq):
                             continue
                         pairs = {}                # (a hooked pair keeps the stock modules; the bare layers of the container stay)

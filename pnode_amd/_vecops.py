@@ -226,9 +226,17 @@ class HipVecOps(object):
 
     linear_flags = 0           # PN_LINEAR_FORM_PLAIN with -pn_linear_form plain: the K loop of linear_fwd / linear_bwd (the same bits)
 
-    def linear_fwd(self, x, w, b, tanh, y=None, flags=None):
+    linear_relu = True         # linear_fwd and linear_bwd take act="relu" (PN_ACT_RELU; -pn_linear_relu 1)
+    _ACTS = {"identity": _lib.PN_ACT_IDENTITY, "tanh": _lib.PN_ACT_TANH, "relu": _lib.PN_ACT_RELU}
+
+    def linear_fwd(self, x, w, b, tanh, y=None, flags=None, act=None):
         """y = act(x w^T + b), act = tanh or the identity; x (rows, in_f), w (out_f, in_f), b (out_f,) or None: contiguous fp32 on this device.
-        Refused (PnError), never run another way, outside pn_linear_fwd_supported and where y shares memory with x, w or b.  flags: pn_linear_fwd_form's (default: linear_flags)."""
+        Refused (PnError), never run another way, outside pn_linear_fwd_supported and where y shares memory with x, w or b.  flags: pn_linear_fwd_form's (default: linear_flags).
+        act: None -- `tanh` says which of the two --, or "identity", "tanh", "relu" by name (`tanh` is then not looked at); "relu" gives
+        relu of what the identity gives, value for value."""
+        if act is not None and act not in self._ACTS:
+            raise PnError("pn_linear_fwd: act %r: identity, tanh or relu" % (act,))
+        code = self._ACTS[act] if act is not None else (_lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY)
         rows, in_f = x.shape
         out_f = w.shape[0]
         for v in (x, w, b, y):
@@ -241,7 +249,7 @@ class HipVecOps(object):
         elif tuple(y.shape) != (rows, out_f):
             raise PnError("pn_linear_fwd: y (rows, out_f)")
         check(self.lib.pn_linear_fwd_form(self.stream(), _lib.dtype_code(x.dtype), rows, out_f, in_f, x.data_ptr(), w.data_ptr(),
-                                          None if b is None else b.data_ptr(), _lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY, y.data_ptr(),
+                                          None if b is None else b.data_ptr(), code, y.data_ptr(),
                                           self.linear_flags if flags is None else flags))
         return y
 
@@ -249,10 +257,13 @@ class HipVecOps(object):
     def linear_bwd_supported(self, rows, out_f, in_f):
         return bool(self.lib.pn_linear_bwd_supported(self.code, rows, out_f, in_f))
 
-    def linear_bwd(self, g, a, w, gz=None, dx=None, flags=None):
+    def linear_bwd(self, g, a, w, gz=None, dx=None, flags=None, act="tanh"):
         """(gz, dx) = (g (1 - a^2), gz w); g, a (rows, out_f), w (out_f, in_f): contiguous fp32 on this device.  Refused (PnError), never
         run another way, outside pn_linear_bwd_supported, for an fp64 state, and where gz or dx shares memory with an input.
-        flags: pn_linear_bwd_form's (default: linear_flags)."""
+        flags: pn_linear_bwd_form's (default: linear_flags).  act="relu" (pn_linear_bwd_act): gz = threshold_backward(g, a, 0) bit for bit,
+        dx the bits of linear_dx(gz, w)."""
+        if act not in ("tanh", "relu"):
+            raise PnError("pn_linear_bwd: act %r: tanh or relu (no activation: linear_dx)" % (act,))
         rows, out_f = g.shape
         in_f = w.shape[1]
         for v in (g, a, w, gz, dx):
@@ -268,8 +279,13 @@ class HipVecOps(object):
             dx = torch.empty((rows, in_f), dtype=g.dtype, device=g.device)
         elif tuple(dx.shape) != (rows, in_f):
             raise PnError("pn_linear_bwd: dx (rows, in_f)")
-        check(self.lib.pn_linear_bwd_form(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), gz.data_ptr(),
-                                          dx.data_ptr(), self.linear_flags if flags is None else flags))
+        flags = self.linear_flags if flags is None else flags
+        if act == "relu":
+            check(self.lib.pn_linear_bwd_act(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), _lib.PN_ACT_RELU,
+                                             gz.data_ptr(), dx.data_ptr(), flags))
+        else:
+            check(self.lib.pn_linear_bwd_form(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), gz.data_ptr(),
+                                              dx.data_ptr(), flags))
         return gz, dx
 
     # ---- the backward of a bare Linear layer with respect to its input (pn_linear_dx, csrc/pn_linear.hip)

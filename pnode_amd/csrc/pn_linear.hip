@@ -887,12 +887,15 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
   const int row0 = tm * FM + wm * 32 + 4 * (lane >> 5);          // (C/D map of the 32 x 32 MFMAs: register e is row (e & 3) + 8 (e >> 2) + 4 (lane >> 5))
   float *yp = a.y + (size_t)row0 * out_f + col;
   const bool tanh_act = a.act == PN_ACT_TANH;
+  const bool relu_act = a.act == PN_ACT_RELU;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const float other = red[(w ^ 4) * 16 + e][lane];
     const float first = kh == 0 ? acc0[e] : other, second = kh == 0 ? other : acc1[e];
     float z = (first + second) + bias;
     if (tanh_act) z = tanhf(z);
+    // relu of the identity's value: a positive z as it is, a NaN stays a NaN, everything else (-0 too) is +0 (not fmaxf: it drops a NaN)
+    if (relu_act) z = z > 0.f ? z : (z == z ? 0.f : z);
     const int r = (e & 3) + 8 * (e >> 2);
     if (colok && (!RAGGED || row0 + r < rows)) yp[(size_t)r * out_f] = z;
   }
@@ -930,9 +933,15 @@ struct BwdLoads {
 // BARE: the layer has no activation behind it (pn_linear_dx): z = g -- its bits unchanged --, no load of a, nothing stored to gz (q.a and
 // q.gz are null and never touched); the tile map, the W images, the order of the products and the exchange are the tanh body's, so dx has
 // the bits this body gives for a == 0 (g (1 - 0 0) is g exactly, with or without the fma).
-template <bool RAGGED, bool PIPE, bool BARE = false>
+// ACT: the activation behind the layer, a's: PN_ACT_TANH (above), PN_ACT_IDENTITY (BARE) or PN_ACT_RELU (pn_linear_bwd_act):
+//   gz[r][k] = a[r][k] <= 0 ? +0 : g[r][k]
+// -- aten.threshold_backward(g, a, 0): a NaN in a lets g through, a == +-0 gives +0.  No arithmetic touches g: every element of gz is
+// g's bits or +0, so gz is threshold_backward's bit for bit and dx is what the bare body gives when fed that gz, in every form.
+template <bool RAGGED, bool PIPE, int ACT = PN_ACT_TANH>
 __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   static_assert(!(RAGGED && PIPE), "the pipelined loop loads without tests");
+  static_assert(ACT == PN_ACT_TANH || ACT == PN_ACT_IDENTITY || ACT == PN_ACT_RELU, "tanh, none or ReLU");
+  constexpr bool BARE = ACT == PN_ACT_IDENTITY, RELU = ACT == PN_ACT_RELU;
   constexpr int AROWB = 2 * FK, APART = FM * AROWB;              // gz: [64 rows][32 bf16], 4 KB per part
   constexpr int WROWB = 128, WIMG = FK * WROWB, WPART = 2 * WIMG;      // W: two [32 k][64 bf16] images, 8 KB per part
   constexpr int BUF = 3 * APART + 3 * WPART;                     // 36 KB
@@ -978,7 +987,11 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   auto lstore = [&](int slab, int buf) {
     char *b = smem + buf * BUF;
     f32x4 z = gv;                                                // here, not at the load: the products would wait for the loads in front of the MFMAs
-    if constexpr (!BARE) {
+    if constexpr (RELU) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) z[e] = av[e] <= 0.f ? 0.f : gv[e];
+      if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
+    } else if constexpr (!BARE) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[e] = gv[e] * (1.f - av[e] * av[e]);
       if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
@@ -1036,7 +1049,10 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
             // gz as the plain loop forms it, spelled out: 1 - a a in one fma, then ONE rounded product.  Left to contraction, the product
             // here is fused into the split's first subtraction (fma(g, t, -hi)): other mid and lo terms, other bits in dx
             f32x4 z = l.g;
-            if constexpr (!BARE) {
+            if constexpr (RELU) {                // (nothing to contract: a compare and a select)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) z[e] = l.a[e] <= 0.f ? 0.f : l.g[e];
+            } else if constexpr (!BARE) {
 #pragma clang fp contract(off)
 #pragma unroll
               for (int e = 0; e < 4; ++e) z[e] = l.g[e] * __builtin_fmaf(-l.a[e], l.a[e], 1.f);
@@ -1094,9 +1110,13 @@ __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3(Bwd
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false>(a); }
 __global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true>(a); }
 // the bare ones (pn_linear_dx): a and gz of BwdArgs are null
-__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_dx_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, true>(a); }
-__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_dx_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, true>(a); }
-__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_dx_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, true>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_dx_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_IDENTITY>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_dx_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_IDENTITY>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_dx_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_IDENTITY>(a); }
+// the ReLU pairs' (pn_linear_bwd_act with PN_ACT_RELU): the launch bounds of their tanh siblings
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_relu_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_RELU>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_relu_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_RELU>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_relu_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_RELU>(a); }
 
 int cu_count() {
   static int n = 0;             // (the calling thread's current device; every device of a node is the same part)
@@ -1127,6 +1147,35 @@ int finish_t(hipStream_t st, int64_t out_f, int64_t in_f, void *pw, void *pb, vo
     rc = pn::launch(name, pn_linear_bgrad_finish_kernel<T>, dim3((unsigned)((out_f + 255) / 256)), dim3(256), st, (double *)pb, (int)out_f,
                     (int)(kSplit * (in_f / BN)), (T *)mu_b);
   return rc;
+}
+
+// what pn_linear_bwd_form and pn_linear_bwd_act share behind their own checks of `flags` (and of `act`): the shape rules, the null,
+// alignment and aliasing refusals, the choice of the form; act is PN_ACT_TANH or PN_ACT_RELU
+int bwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
+             void *gz, void *dx, int flags) {
+  if (!pn_linear_bwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_bwd: unsupported dtype or shape (see pn_linear_bwd_supported)");
+  if (g == nullptr || a == nullptr || w == nullptr || gz == nullptr || dx == nullptr) return pn::fail("pn_linear_bwd: null operand");
+  if (!pn::aligned16(g, a, w, gz, dx)) return pn::fail("pn_linear_bwd: operands must be 16-byte aligned");
+  // an output that shares bytes with anything else the launch touches: other workgroups still read (or also write) them
+  const size_t nz = (size_t)rows * (size_t)out_f * sizeof(float), nw = (size_t)out_f * (size_t)in_f * sizeof(float),
+               nx = (size_t)rows * (size_t)in_f * sizeof(float);
+  if (overlap(gz, nz, g, nz) || overlap(gz, nz, a, nz) || overlap(gz, nz, w, nw))
+    return pn::fail("pn_linear_bwd: gz must not alias g, a or w (other workgroups still read them)");
+  if (overlap(dx, nx, g, nz) || overlap(dx, nx, a, nz) || overlap(dx, nx, w, nw) || overlap(dx, nx, gz, nz))
+    return pn::fail("pn_linear_bwd: dx must not alias g, a, w or gz");
+  BwdArgs q;
+  q.g = (const float *)g, q.a = (const float *)a, q.w = (const float *)w, q.gz = (float *)gz, q.dx = (float *)dx;
+  q.rows = (int)rows, q.out_f = (int)out_f, q.in_f = (int)in_f;
+  q.ntn = (int)((in_f + FN - 1) / FN);
+  const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)q.ntn;
+  const bool ragged = rows % FM != 0 || in_f % FN != 0;
+  const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (out_f / FK) % 2 != 0;      // (the pipelined loop takes an even number of slabs)
+  if (act == PN_ACT_RELU) {
+    auto kern = ragged ? pn_linear_bwd_relu_kernel_f32x3_ragged : (plain ? pn_linear_bwd_relu_kernel_f32x3 : pn_linear_bwd_relu_kernel_f32x3_pipe);
+    return pn::launch("pn_linear_bwd_act", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
+  }
+  auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : (plain ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
+  return pn::launch("pn_linear_bwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
 }
 
 }  // namespace
@@ -1225,7 +1274,8 @@ int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
                        int act, void *y, int flags) {
   if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_fwd_form: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
   if (!pn_linear_fwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_fwd: unsupported dtype or shape (see pn_linear_fwd_supported)");
-  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH) return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY or PN_ACT_TANH");
+  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH && act != PN_ACT_RELU)
+    return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY, PN_ACT_TANH or PN_ACT_RELU");
   if (x == nullptr || w == nullptr || y == nullptr) return pn::fail("pn_linear_fwd: null operand");
   if (!pn::aligned16(x, w, y) || (reinterpret_cast<uintptr_t>(b) & 3)) return pn::fail("pn_linear_fwd: operands must be 16-byte aligned");
   // an output that shares bytes with anything the launch reads: other workgroups still read x, w and b while a tile of y is stored
@@ -1260,25 +1310,15 @@ int pn_linear_bwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
 int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w,
                        void *gz, void *dx, int flags) {
   if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_bwd_form: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
-  if (!pn_linear_bwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_bwd: unsupported dtype or shape (see pn_linear_bwd_supported)");
-  if (g == nullptr || a == nullptr || w == nullptr || gz == nullptr || dx == nullptr) return pn::fail("pn_linear_bwd: null operand");
-  if (!pn::aligned16(g, a, w, gz, dx)) return pn::fail("pn_linear_bwd: operands must be 16-byte aligned");
-  // an output that shares bytes with anything else the launch touches: other workgroups still read (or also write) them
-  const size_t nz = (size_t)rows * (size_t)out_f * sizeof(float), nw = (size_t)out_f * (size_t)in_f * sizeof(float),
-               nx = (size_t)rows * (size_t)in_f * sizeof(float);
-  if (overlap(gz, nz, g, nz) || overlap(gz, nz, a, nz) || overlap(gz, nz, w, nw))
-    return pn::fail("pn_linear_bwd: gz must not alias g, a or w (other workgroups still read them)");
-  if (overlap(dx, nx, g, nz) || overlap(dx, nx, a, nz) || overlap(dx, nx, w, nw) || overlap(dx, nx, gz, nz))
-    return pn::fail("pn_linear_bwd: dx must not alias g, a, w or gz");
-  BwdArgs q;
-  q.g = (const float *)g, q.a = (const float *)a, q.w = (const float *)w, q.gz = (float *)gz, q.dx = (float *)dx;
-  q.rows = (int)rows, q.out_f = (int)out_f, q.in_f = (int)in_f;
-  q.ntn = (int)((in_f + FN - 1) / FN);
-  const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)q.ntn;
-  const bool ragged = rows % FM != 0 || in_f % FN != 0;
-  const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (out_f / FK) % 2 != 0;      // (the pipelined loop takes an even number of slabs)
-  auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : (plain ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
-  return pn::launch("pn_linear_bwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
+  return bwd_pair(stream, dtype, rows, out_f, in_f, g, a, w, PN_ACT_TANH, gz, dx, flags);
+}
+
+int pn_linear_bwd_act(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
+                      void *gz, void *dx, int flags) {
+  if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_bwd_act: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
+  if (act == PN_ACT_IDENTITY) return pn::fail("pn_linear_bwd_act: PN_ACT_IDENTITY has no prologue and no gz: use pn_linear_dx");
+  if (act != PN_ACT_TANH && act != PN_ACT_RELU) return pn::fail("pn_linear_bwd_act: act is PN_ACT_TANH or PN_ACT_RELU (PN_ACT_IDENTITY: use pn_linear_dx)");
+  return bwd_pair(stream, dtype, rows, out_f, in_f, g, a, w, act, gz, dx, flags);
 }
 
 int pn_linear_dx_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f) { return pn_linear_bwd_supported(dtype, rows, out_f, in_f); }

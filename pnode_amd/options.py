@@ -23,6 +23,11 @@ is for timing one against the other inside one tree.
 head of every ``... -> Linear`` net -- to the stock module; ``1`` runs the eligible ones through ``pn_linear_fwd`` with the identity and
 their backward ``dx = g W`` through ``pn_linear_dx`` (``-pn_linear_bwd 0`` keeps ``matmul``), inside the solver's own evaluations, under
 the rules of the pairs.  ``ode.linear_bare`` reports what runs.  ``-pn_linear_fwd 0`` switches this off with the pairs.
+``-pn_linear_relu 0|1`` (read there too; anything else is refused): ``0``, the default, leaves a Linear in front of an ``nn.ReLU`` what it
+is -- a stock module, or a bare layer under ``-pn_linear_bare 1``; ``1`` runs the eligible ``nn.Linear -> nn.ReLU`` pairs as one
+``pn_linear_fwd`` launch with ``PN_ACT_RELU`` and their backward -- ``g_z = threshold_backward(g, a, 0)``, ``dx = g_z W`` -- as one
+``pn_linear_bwd_act`` launch (``-pn_linear_bwd 0`` keeps ``threshold_backward`` and ``matmul``), under the rules of the Tanh pairs.
+``ode.linear_relu`` reports what runs.  ``-pn_linear_fwd 0`` switches this off too.
 """
 import os
 import shlex
