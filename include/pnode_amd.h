@@ -230,7 +230,10 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
  * in_f, b out_f values or NULL, y rows x out_f, all row-major fp32; act = PN_ACT_IDENTITY, PN_ACT_TANH (tanhf of the device library,
  * applied in fp32 to the biased sum: exactly +-1 once it saturates, NaN for NaN) or PN_ACT_RELU (of the biased sum z: z where z > 0, a
  * NaN stays that NaN, everything else -- -0 too -- is +0; so y under PN_ACT_RELU is relu of the y under PN_ACT_IDENTITY in the same
- * form, value for value); any other act is refused, nothing launched.  The product is the split-bf16 one of pn_linear_wgrad
+ * form, value for value) or PN_ACT_SIGMOID (y = 1 / (1 + expf(-z)) of the biased sum z in fp32: expf of the device library, one rounded
+ * add, one correctly rounded division -- within 2.5 * 2^-24 of sigma of the y under PN_ACT_IDENTITY in the same form; never above 1,
+ * exactly 1 from z >= 40 on, exactly +0 from z <= -110 on, in (0, 1] for |z| <= 80, NaN for NaN; not torch.sigmoid's bits); any other
+ * act -- 3 too, which names nothing -- is refused, nothing launched.  The product is the split-bf16 one of pn_linear_wgrad
  * (three exact bf16 terms per operand, the six largest cross products, fp32 accumulation on v_mfma_f32_32x32x16_bf16; an infinite
  * operand gives NaN); one workgroup owns a 64 x 128 tile of y over all of in_f and writes it once: no atomics, no work buffers, the
  * same bits on every launch.  x, w, y non-NULL and 16-byte aligned, b 4-byte aligned; y shares no byte with x, w or b (other workgroups
@@ -241,6 +244,7 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
 #define PN_ACT_IDENTITY 0
 #define PN_ACT_TANH 1
 #define PN_ACT_RELU 2
+#define PN_ACT_SIGMOID 4 /* (3 names nothing and is refused) */
 int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
 int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
                   void *y);
@@ -279,6 +283,13 @@ int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
  * every element of gz is g's bits or +0.  dx has the bits of pn_linear_dx fed that gz, in every form (the prologue sits in front of the
  * bare body's split, tile map and product order).  Replaces, in the reverse sweep's stage VJPs, the threshold_backward kernel and the
  * library GEMM of the pair (with -pn_linear_bare 1: threshold_backward and pn_linear_dx, which reads gz back).
+ * act == PN_ACT_SIGMOID is the backward of an nn.Linear -> nn.Sigmoid pair, a its output:
+ *   gz[r][k] = g[r][k] s,  s = fmaf(-a[r][k], a[r][k], a[r][k])      dx[r][n] = sum_k gz[r][k] w[k][n]
+ * -- a (1 - a) in one fma, then ONE rounded product (never contracted into what follows), spelled the same in every form: two roundings,
+ * within 2.5 * 2^-24 of |g a (1 - a)|, the same bits of gz in every form; not aten.sigmoid_backward bit for bit (three roundings there).
+ * a == 0 or a == 1 with finite g gives gz == 0; a NaN in a or g stays in its own element of gz and its own row of dx; g = +-inf where s
+ * is 0 gives NaN, as in aten.sigmoid_backward.  dx has the bits of pn_linear_dx fed that gz, in every form.  Replaces the
+ * sigmoid_backward kernel and the library GEMM of the pair.
  * PN_ACT_IDENTITY is refused (no prologue, no gz: use pn_linear_dx); so is any other value, and an unknown flag; nothing is launched. */
 int pn_linear_bwd_act(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
                       void *gz, void *dx, int flags);

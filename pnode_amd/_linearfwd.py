@@ -48,7 +48,18 @@ The pair runs through ``_LinearTanh`` with ``call.relu``: forward ``pn_linear_fw
 ``linear_relu``, else ``threshold_backward`` and ``matmul``; ``(g_z, x)`` goes to ``LinearParamGrads._grad_hook`` as a tanh pair's.
 Self-checks of their own: the forward against ``torch.relu(F.linear)`` in the pair's measure; ``g_z`` must be ``threshold_backward``'s
 bit for bit (the kernel does no arithmetic on it), ``dx`` in the pair's measure.  A miss switches off the ReLU pairs, or their backward,
-only.  ``n_relu`` / ``n_relu_bwd`` count them; ``n_fused`` / ``n_fused_bwd`` stay the tanh pairs'."""
+only.  ``n_relu`` / ``n_relu_bwd`` count them; ``n_fused`` / ``n_fused_bwd`` stay the tanh pairs'.
+
+Sigmoid pairs (``-pn_linear_sigmoid 0|1``, default ``0``: nothing below happens).  With ``1`` two consecutive children ``nn.Linear``,
+exactly ``nn.Sigmoid`` of an eligible container are a pair under the same rules; such a Linear is no bare layer.  Their maps, flags and
+counters are one record, ``LinearFwd.sig`` (a ``_PairState``), not a third copy of every field; ``n_sigmoid`` / ``n_sigmoid_bwd`` read
+it.  The pair runs through ``_LinearTanh`` with ``call.sigmoid``: forward ``pn_linear_fwd`` with ``PN_ACT_SIGMOID``; backward
+``g_z = g a (1 - a)`` and ``dx = g_z W`` in one launch (``pn_linear_bwd_act``) on a backend with ``linear_sigmoid``, else
+``sigmoid_backward`` and ``matmul``.  The arithmetic is not exact, so the self-checks are bounds: the forward against
+``torch.sigmoid(F.linear)`` to ``1e-6 (sum |x w| + |b|) + 4 * 2^-24`` -- the absolute term because a zero pre-activation maps to 0.5 with
+a rounding of its own on either side (the kernel at most 2.5, the library about 1 ulp of 2^-24), where tanh and ReLU give an exact 0;
+``g_z`` to ``1.5 * 2^-24 |g|`` of ``sigmoid_backward``'s (two roundings here, three there, relative to ``g a (1 - a) <= |g| / 4``); ``dx``
+in the pairs' measure.  A miss switches off the Sigmoid pairs, or their backward, only."""
 import contextlib
 import warnings
 import weakref
@@ -89,7 +100,7 @@ def _user_hooked(m):
 
 def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
     """The static half of the eligibility rules for the Linear `lin` (and the activation `act` behind it, exactly a `kind`: nn.Tanh or
-    nn.ReLU; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
+    nn.ReLU or nn.Sigmoid; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
     mods = (lin,) if act is None else (lin, act)
     if type(seq) is not nn.Sequential or "forward" in seq.__dict__:
         return "the container's forward is not nn.Sequential's own"
@@ -110,13 +121,14 @@ def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
     return why
 
 
-def find_layers(func, params, relu=False):
+def find_layers(func, params, relu=False, sigmoid=False):
     """(plans, refused, bare): [(sequential, {index of the Linear child: (linear, tanh)})] of func; {class name of a container: reason}
     for the Linear -> Tanh pairs that cannot be fused (what -pn_linear_fwd 1 warns about); and [(sequential, {index of the child:
     linear})] for the bare layers -- exactly nn.Linear, opening no fused pair, under the same static rules (-pn_linear_bare 1).
     relu (-pn_linear_relu 1): two consecutive children nn.Linear, nn.ReLU are a pair too, under the rules of a tanh pair -- (linear, relu)
     in `plans`, told from a tanh pair by its second member, and such a Linear is no bare layer; a ReLU pair that cannot be fused is in
-    `refused` under the key (class name of the container, "ReLU").  Without it the three are what they were before there was the option."""
+    `refused` under the key (class name of the container, "ReLU").  Without it the three are what they were before there was the option.
+    sigmoid (-pn_linear_sigmoid 1): the same for nn.Linear, nn.Sigmoid; the key in `refused` is (class name, "Sigmoid")."""
     plans, refused, bare = [], {}, []
     if not isinstance(func, nn.Module):
         return plans, refused, bare
@@ -141,6 +153,8 @@ def find_layers(func, params, relu=False):
                 kind, key = nn.Tanh, type(seq).__name__
             elif relu and isinstance(act, nn.ReLU):
                 kind, key = nn.ReLU, (type(seq).__name__, "ReLU")
+            elif sigmoid and isinstance(act, nn.Sigmoid):
+                kind, key = nn.Sigmoid, (type(seq).__name__, "Sigmoid")
             else:
                 continue
             why = _static_why(seq, kids, lin, act, index, owners, kind)
@@ -164,7 +178,44 @@ def find_pairs(func, params):
 
 class _Call(object):
     """What one fused call carries into its backward."""
-    __slots__ = ("owner", "module", "grads", "ev", "version", "relu")
+    __slots__ = ("owner", "module", "grads", "ev", "version", "relu", "sigmoid")
+
+
+class _PairState(object):
+    """The state of one further kind of pair beside the tanh and ReLU pairs, whose fields are LinearFwd's own: the map, the option, the
+    self-checks' flags and reasons, the counters.  `name` is the activation's class name, `torch_fwd` / `torch_bwd` the expressions the
+    pair replaces (in the wording of the warnings)."""
+    def __init__(self, name, option, torch_fwd, torch_bwd):
+        self.name, self.option, self.torch_fwd, self.torch_bwd = name, option, torch_fwd, torch_bwd
+        self.plans = []            # [(sequential, {child index: (linear, activation)})]
+        self.mode = "0"
+        self.disabled = False      # the forward check failed
+        self.why = None
+        self.checked = False
+        self.n = 0                 # pair calls that ran as one launch
+        self.bwd_disabled = False  # the backward check failed (the forward stays)
+        self.bwd_why = None
+        self.bwd_checked = False
+        self.n_bwd = 0             # pair backwards that ran as one launch (pn_linear_bwd_act)
+        self.warned = False
+        self.warned_bwd = False
+        self.refused = None        # the reason of the last call-time refusal (LinearFwd._fusable): that call ran the stock modules
+
+    @property
+    def active(self):
+        return self.mode == "1" and bool(self.plans) and not self.disabled
+
+    @property
+    def status(self):
+        if self.mode != "1":
+            return "off (%s 0)" % self.option
+        if not self.plans:
+            return "stock modules (no eligible Linear -> %s pair)" % self.name
+        if self.disabled:
+            return "stock modules (%s)" % self.why
+        return "fused (%d pairs; %d forward, %d backward calls so far%s)" % (
+            sum(len(p) for _, p in self.plans), self.n, self.n_bwd,
+            "" if self.refused is None else "; the stock modules where a call is refused, last: " + self.refused)
 
 
 def _shaped(y2, shape):
@@ -174,10 +225,11 @@ def _shaped(y2, shape):
 
 
 class _LinearTanh(torch.autograd.Function):
-    """A Linear -> Tanh pair or, with call.relu (-pn_linear_relu 1), a Linear -> ReLU pair: the same structure, the other activation."""
+    """A Linear -> Tanh pair or, with call.relu (-pn_linear_relu 1), a Linear -> ReLU pair, or, with call.sigmoid (-pn_linear_sigmoid 1), a
+    Linear -> Sigmoid pair: the same structure, the other activation."""
     @staticmethod
     def forward(ctx, x, w, b, call):
-        kernel = call.owner.kernel_relu if call.relu else call.owner.kernel
+        kernel = call.owner.kernel_sigmoid if call.sigmoid else (call.owner.kernel_relu if call.relu else call.owner.kernel)
         a = _shaped(kernel(x.reshape(-1, w.shape[1]), w, b), x.shape[:-1] + (w.shape[0],))
         ctx.save_for_backward(x, w, a)
         ctx.call = call
@@ -189,11 +241,19 @@ class _LinearTanh(torch.autograd.Function):
         x, w, a = ctx.saved_tensors
         call = ctx.call
         # both in one launch (pn_linear_bwd, pn_linear_bwd_act) where LinearFwd._bwd_fusable allows it, else the two torch operations
-        fused = call.owner._backward(g, a, w, call.relu) if ctx.needs_input_grad[0] else None
+        if not ctx.needs_input_grad[0]:
+            fused = None
+        elif call.sigmoid:
+            fused = call.owner._backward(g, a, w, sigmoid=True)
+        else:
+            fused = call.owner._backward(g, a, w, call.relu)
         if fused is not None:
             g_z, dx = fused
         else:
-            g_z = torch.ops.aten.threshold_backward(g, a, 0) if call.relu else torch.ops.aten.tanh_backward(g, a)
+            if call.sigmoid:
+                g_z = torch.ops.aten.sigmoid_backward(g, a)
+            else:
+                g_z = torch.ops.aten.threshold_backward(g, a, 0) if call.relu else torch.ops.aten.tanh_backward(g, a)
             dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
         dw, db = _param_grads(ctx, call, g_z, x, w)
         return dx, dw, db, None
@@ -287,30 +347,35 @@ class LinearFwd(object):
         self.n_relu_bwd = 0        # ReLU pair backwards that ran as one launch (pn_linear_bwd_act)
         self._warned_relu = False
         self._warned_relu_bwd = False
+        # the Linear -> Sigmoid pairs (-pn_linear_sigmoid 0|1): the same in one record
+        self.sig = _PairState("Sigmoid", "-pn_linear_sigmoid", "torch.sigmoid(F.linear)", "sigmoid_backward + matmul")
 
-    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0", relu_mode="0"):
-        """Find the eligible pairs of `func` (and, with bare_mode "1", its bare layers; with relu_mode "1", its Linear -> ReLU pairs);
-        returns True when there is at least one."""
+    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0", relu_mode="0", sigmoid_mode="0"):
+        """Find the eligible pairs of `func` (and, with bare_mode "1", its bare layers; with relu_mode "1", its Linear -> ReLU pairs; with
+        sigmoid_mode "1", its Linear -> Sigmoid pairs); returns True when there is at least one."""
         self.mode = mode
         self.bwd_mode = bwd_mode
         self.bare_mode = bare_mode
         self.relu_mode = relu_mode
-        found, refused, self.bare = find_layers(func, params, relu_mode == "1")
-        self.plans, self.relu = [], []
+        self.sig.mode = sigmoid_mode
+        self.sig.refused = None
+        found, refused, self.bare = find_layers(func, params, relu_mode == "1", sigmoid=sigmoid_mode == "1")
+        self.plans, self.relu, self.sig.plans = [], [], []
         for seq, pairs in found:
-            for kind, plans in ((nn.Tanh, self.plans), (nn.ReLU, self.relu)):
+            for kind, plans in ((nn.Tanh, self.plans), (nn.ReLU, self.relu), (nn.Sigmoid, self.sig.plans)):
                 mine = {i: p for i, p in pairs.items() if type(p[1]) is kind}
                 if mine:
                     plans.append((seq, mine))
         if mode == "1" and refused:
             for key, why in refused.items():
                 cls, name = key if isinstance(key, tuple) else (key, "Tanh")
-                if self._warned_relu if name == "ReLU" else self._warned:
+                if self.sig.warned if name == "Sigmoid" else (self._warned_relu if name == "ReLU" else self._warned):
                     continue
                 warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair of %s runs the stock modules: %s" % (name, cls, why), RuntimeWarning)
             self._warned = self._warned or any(not isinstance(key, tuple) for key in refused)
-            self._warned_relu = self._warned_relu or any(isinstance(key, tuple) for key in refused)
-        return bool(self.plans) or self.bare_active or self.relu_active
+            self._warned_relu = self._warned_relu or any(isinstance(key, tuple) and key[1] == "ReLU" for key in refused)
+            self.sig.warned = self.sig.warned or any(isinstance(key, tuple) and key[1] == "Sigmoid" for key in refused)
+        return bool(self.plans) or self.bare_active or self.relu_active or self.sig.active
 
     @property
     def bare_active(self):
@@ -322,7 +387,28 @@ class LinearFwd(object):
 
     @property
     def active(self):
-        return (bool(self.plans) and not self.disabled) or self.bare_active or self.relu_active
+        return (bool(self.plans) and not self.disabled) or self.bare_active or self.relu_active or self.sig.active
+
+    # what the Sigmoid pairs' record holds, under the names the tanh and ReLU pairs' fields have
+    @property
+    def sigmoid(self):
+        return self.sig.plans
+
+    @property
+    def sigmoid_active(self):
+        return self.sig.active
+
+    @property
+    def sigmoid_status(self):
+        return self.sig.status
+
+    @property
+    def n_sigmoid(self):
+        return self.sig.n
+
+    @property
+    def n_sigmoid_bwd(self):
+        return self.sig.n_bwd
 
     # the one place the device is touched: tests of the eligibility rules replace it by the torch expression
     def kernel(self, x2, w, b):
@@ -334,6 +420,9 @@ class LinearFwd(object):
     def kernel_relu(self, x2, w, b):
         return self._ode()._ops.linear_fwd(x2, w, b, False, act="relu")
 
+    def kernel_sigmoid(self, x2, w, b):
+        return self._ode()._ops.linear_fwd(x2, w, b, False, act="sigmoid")
+
     def supported(self, rows, out_f, in_f):
         key = (rows, out_f, in_f)
         ok = self._ok.get(key)
@@ -342,14 +431,16 @@ class LinearFwd(object):
             ok = self._ok[key] = bool(hasattr(ops, "linear_fwd_supported") and ops.linear_fwd_supported(rows, out_f, in_f))
         return ok
 
-    def _refuse(self, why, relu=False):
-        if self.mode == "1" and not (self._warned_relu if relu else self._warned):
-            if relu:
+    def _refuse(self, why, relu=False, sigmoid=False):
+        if self.mode == "1" and not (self.sig.warned if sigmoid else (self._warned_relu if relu else self._warned)):
+            if sigmoid:
+                self.sig.warned = True
+            elif relu:
                 self._warned_relu = True
             else:
                 self._warned = True
-            warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair runs the stock modules: %s" % ("ReLU" if relu else "Tanh", why),
-                          RuntimeWarning)
+            warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair runs the stock modules: %s"
+                          % ("Sigmoid" if sigmoid else ("ReLU" if relu else "Tanh"), why), RuntimeWarning)
         return None
 
     def _fusable(self, lin, x):
@@ -369,6 +460,32 @@ class LinearFwd(object):
         if not self.supported(x.numel() // w.shape[1], w.shape[0], w.shape[1]):
             return "outside pn_linear_fwd_supported"
         return None
+
+    def _check_sigmoid(self, x, w, b, a):
+        """First fused call of a Sigmoid pair of a solver: against torch.sigmoid(F.linear), |y - ref| <= CHECK_TOL (sum |x w| + |b|) +
+        4 * 2^-24.  The absolute term: sigma maps a zero pre-activation to 0.5 with a rounding of its own on either side (the kernel at
+        most 2.5 ulp of 2^-24, the library about 1), where tanh and ReLU give an exact 0 -- a small sum |x w| + |b| is no miss.  A miss
+        switches off the Sigmoid pairs only."""
+        st = self.sig
+        st.checked = True
+        with torch.no_grad():
+            x2 = x.reshape(-1, w.shape[1])
+            ref = torch.sigmoid(F.linear(x2, w, b))
+            scale = x2.abs() @ w.abs().t()
+            if b is not None:
+                scale = scale + b.abs()
+            ok = torch.isfinite(ref) & torch.isfinite(scale)
+            if not bool(ok.any()):
+                st.checked = False
+                return True
+            bar = CHECK_TOL * scale + 4.0 * 2.0 ** -24
+            over = ((a.reshape(ref.shape) - ref).abs() / bar)[ok].max()
+        if not float(over) <= 1.0:
+            st.disabled = True
+            st.why = "pn_linear_fwd and %s differ by %.2f times the bar %.0e (sum |x w| + |b|) + 4 * 2^-24" % (st.torch_fwd, float(over), CHECK_TOL)
+            warnings.warn("pnode_amd: the fused Linear -> %s forward is switched off for this solver: %s" % (st.name, st.why), RuntimeWarning)
+            return False
+        return True
 
     def _check(self, x, w, b, a, bare=False, relu=False):
         """First fused call of a solver: the pair through torch as well.  bare: a bare layer's first call, against F.linear in the same
@@ -424,10 +541,13 @@ class LinearFwd(object):
     def kernel_bwd_relu(self, g2, a2, w):
         return self._ode()._ops.linear_bwd(g2, a2, w, act="relu")
 
-    def _bwd_fusable(self, g, a, w, relu=False):
+    def kernel_bwd_sigmoid(self, g2, a2, w):
+        return self._ode()._ops.linear_bwd(g2, a2, w, act="sigmoid")
+
+    def _bwd_fusable(self, g, a, w, relu=False, sigmoid=False):
         """None, or the reason (a string) this backward runs the torch operations.  a: the pair's output; None for a bare layer
         (pn_linear_dx: the same rules minus everything about a).  relu: a ReLU pair (pn_linear_bwd_act: the rules of a tanh pair, and
-        a backend with `linear_relu`)."""
+        a backend with `linear_relu`).  sigmoid: a Sigmoid pair (the same, and a backend with `linear_sigmoid`)."""
         bare = a is None
         entry = "linear_dx" if bare else "linear_bwd"
         ode = self._ode()
@@ -435,9 +555,14 @@ class LinearFwd(object):
             return "the backend has no " + entry
         if relu and not getattr(ode._ops, "linear_relu", False):
             return "the backend has no linear_relu"
+        if sigmoid and not getattr(ode._ops, "linear_sigmoid", False):
+            return "the backend has no linear_sigmoid"
         if self.bwd_mode == "0":
             return "-pn_linear_bwd 0"
-        if relu:
+        if sigmoid:
+            if self.sig.bwd_disabled:
+                return self.sig.bwd_why
+        elif relu:
             if self.relu_bwd_disabled:
                 return self.relu_bwd_why
         elif self.bare_bwd_disabled if bare else self.bwd_disabled:
@@ -502,29 +627,66 @@ class LinearFwd(object):
             return gz_t, dx_t
         return None
 
-    def _backward(self, g, a, w, relu=False):
-        """(g_z, dx) of one pair by pn_linear_bwd (relu: pn_linear_bwd_act), or None: the caller runs tanh_backward (threshold_backward)
-        and matmul."""
-        why = self._bwd_fusable(g, a, w, relu)
+    def _check_sigmoid_bwd(self, g2, a2, w, gz, dx):
+        """First fused backward of a Sigmoid pair of a solver: both results through torch as well.  gz to 1.5 * 2^-24 |g| of
+        sigmoid_backward's, elementwise (two roundings here, three there, each relative to |g a (1 - a)| <= |g| / 4); dx to CHECK_TOL of
+        |gz| |w| (the pairs' measure).  Returns None, or the torch results after switching the fused Sigmoid backward -- only it -- off."""
+        st = self.sig
+        st.bwd_checked = True
+        gz_t = torch.ops.aten.sigmoid_backward(g2, a2)
+        dx_t = torch.matmul(gz_t, w)
+        scale = gz_t.abs() @ w.abs()
+        fin = torch.isfinite(gz_t)
+        ok = torch.isfinite(dx_t) & (scale > 0)
+        if not bool(fin.any()) or not bool(ok.any()):
+            st.bwd_checked = False                 # nothing to judge by: the next call is checked
+            return None
+        bad_z = bool((~((gz - gz_t).abs() <= 1.5 * 2.0 ** -24 * g2.abs()) & fin).any())
+        err = float(((dx - dx_t).abs() / scale)[ok].max())
+        if bad_z or not err <= CHECK_TOL:
+            st.bwd_disabled = True
+            st.bwd_why = "pn_linear_bwd_act and %s differ: " % st.torch_bwd + (
+                "g_z by more than 1.5 * 2^-24 |g|" if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
+            warnings.warn("pnode_amd: the fused Linear -> %s backward is switched off for this solver: %s" % (st.name, st.bwd_why), RuntimeWarning)
+            return gz_t, dx_t
+        return None
+
+    def _backward(self, g, a, w, relu=False, sigmoid=False):
+        """(g_z, dx) of one pair by pn_linear_bwd (relu, sigmoid: pn_linear_bwd_act), or None: the caller runs tanh_backward
+        (threshold_backward, sigmoid_backward) and matmul."""
+        st = self.sig
+        why = self._bwd_fusable(g, a, w, relu, sigmoid)
         if why is not None:
-            if self.bwd_mode == "1" and not (self._warned_relu_bwd if relu else self._warned_bwd):
-                if relu:
+            if self.bwd_mode == "1" and not (st.warned_bwd if sigmoid else (self._warned_relu_bwd if relu else self._warned_bwd)):
+                if sigmoid:
+                    st.warned_bwd = True
+                elif relu:
                     self._warned_relu_bwd = True
                 else:
                     self._warned_bwd = True
                 warnings.warn("pnode_amd: -pn_linear_bwd 1: the backward of a Linear -> %s pair runs the torch operations: %s"
-                              % ("ReLU" if relu else "Tanh", why), RuntimeWarning)
+                              % ("Sigmoid" if sigmoid else ("ReLU" if relu else "Tanh"), why), RuntimeWarning)
             return None
         out_f, in_f = w.shape
         g2, a2 = g.reshape(-1, out_f), a.reshape(-1, out_f)
         with torch.no_grad():
-            gz, dx = self.kernel_bwd_relu(g2, a2, w) if relu else self.kernel_bwd(g2, a2, w)
-            if not (self.relu_bwd_checked if relu else self.bwd_checked) and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
-                torch_way = self._check_relu_bwd(g2, a2, w, gz, dx) if relu else self._check_bwd(g2, a2, w, gz, dx)
+            if sigmoid:
+                gz, dx = self.kernel_bwd_sigmoid(g2, a2, w)
+                checked, check = st.bwd_checked, self._check_sigmoid_bwd
+            elif relu:
+                gz, dx = self.kernel_bwd_relu(g2, a2, w)
+                checked, check = self.relu_bwd_checked, self._check_relu_bwd
+            else:
+                gz, dx = self.kernel_bwd(g2, a2, w)
+                checked, check = self.bwd_checked, self._check_bwd
+            if not checked and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
+                torch_way = check(g2, a2, w, gz, dx)
                 if torch_way is not None:
                     gz, dx = torch_way
                     return gz.view(g.shape), dx.view(g.shape[:-1] + (in_f,))
-        if relu:
+        if sigmoid:
+            st.n_bwd += 1
+        elif relu:
             self.n_relu_bwd += 1
         else:
             self.n_fused_bwd += 1
@@ -599,25 +761,32 @@ class LinearFwd(object):
         return "fused (%d calls so far)" % self.n_fused_bwd
 
     def _pair(self, lin, act, x, grads):
-        """One pair: Linear -> Tanh or, where `act` is an nn.ReLU, Linear -> ReLU (its module is not called: either `inplace` will do)."""
-        relu = type(act) is nn.ReLU
+        """One pair: Linear -> Tanh or, where `act` is an nn.ReLU, Linear -> ReLU (its module is not called: either `inplace` will do), or,
+        where it is an nn.Sigmoid, Linear -> Sigmoid."""
+        relu, sigmoid = type(act) is nn.ReLU, type(act) is nn.Sigmoid
         why = self._fusable(lin, x)
         if why is not None:
-            self._refuse(why, relu)
+            if sigmoid:
+                self.sig.refused = why
+            self._refuse(why, relu, sigmoid)
             return act(lin(x))
         w, b = lin.weight, lin.bias
         ev = grads.recording if grads is not None else None
         if ev is not None and not grads.note_fused(lin, x):
             ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
         call = _Call()
-        call.owner, call.module, call.grads, call.ev, call.version, call.relu = self, lin, grads, ev, x._version, relu
+        call.owner, call.module, call.grads, call.ev, call.version, call.relu, call.sigmoid = self, lin, grads, ev, x._version, relu, sigmoid
         a = _LinearTanh.apply(x, w, b, call)
-        if not (self.relu_checked if relu else self.checked) and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
-            if not self._check(x.detach(), w.detach(), None if b is None else b.detach(), a.detach(), relu=relu):
+        checked = self.sig.checked if sigmoid else (self.relu_checked if relu else self.checked)
+        if not checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            args = (x.detach(), w.detach(), None if b is None else b.detach(), a.detach())
+            if not (self._check_sigmoid(*args) if sigmoid else self._check(*args, relu=relu)):
                 return act(lin(x))
         if ev is not None and a.grad_fn is not None:
             ev.through[a.grad_fn] = x.grad_fn     # Evaluation.clean passes the pair along its input edge only
-        if relu:
+        if sigmoid:
+            self.sig.n += 1
+        elif relu:
             self.n_relu += 1
         else:
             self.n_fused += 1
@@ -642,6 +811,12 @@ class LinearFwd(object):
         self.n_bare += 1
         return y
 
+    def _off(self, act):
+        """The forward check of the pairs of `act`'s kind failed."""
+        if type(act) is nn.Sigmoid:
+            return self.sig.disabled
+        return self.relu_disabled if type(act) is nn.ReLU else self.disabled
+
     def _runner(self, seq, pairs, alone, grads):
         def forward(inp):
             kids = list(seq._modules.values())
@@ -649,7 +824,7 @@ class LinearFwd(object):
             while i < n:
                 p = pairs.get(i)
                 if p is not None and i + 1 < n and kids[i] is p[0] and kids[i + 1] is p[1] \
-                        and not (self.relu_disabled if type(p[1]) is nn.ReLU else self.disabled):
+                        and not self._off(p[1]):
                     inp = self._pair(p[0], p[1], inp, grads)
                     i += 2
                 elif alone.get(i) is kids[i] and not self.bare_disabled:
@@ -662,14 +837,14 @@ class LinearFwd(object):
         return forward
 
     def _containers(self):
-        """[(sequential, its pairs, its bare layers)]: the pairs while their forward is on (the ReLU pairs with -pn_linear_relu 1), the
-        bare layers with -pn_linear_bare 1."""
+        """[(sequential, its pairs, its bare layers)]: the pairs while their forward is on (the ReLU pairs with -pn_linear_relu 1, the
+        Sigmoid pairs with -pn_linear_sigmoid 1), the bare layers with -pn_linear_bare 1."""
         out = {}
         if not self.disabled:
             for seq, pairs in self.plans:
                 out[id(seq)] = (seq, pairs, {})
-        if self.relu_active:
-            for seq, pairs in self.relu:
+        for plans in ((self.relu,) if self.relu_active else ()) + ((self.sig.plans,) if self.sig.active else ()):
+            for seq, pairs in plans:
                 both = dict(out[id(seq)][1]) if id(seq) in out else {}      # (a copy: the container's tanh pairs stay their own map)
                 both.update(pairs)
                 out[id(seq)] = (seq, both, {})
@@ -689,8 +864,8 @@ class LinearFwd(object):
                     if "forward" in seq.__dict__ or type(seq) is not nn.Sequential:
                         continue
                     if _user_hooked(seq) or any(_user_hooked(m) for pr in pairs.values() for m in pr):
-                        for relu in sorted({type(pr[1]) is nn.ReLU for pr in pairs.values()}):
-                            self._refuse("a forward, pre-forward or backward hook on the pair or its container", relu)
+                        for relu, sigmoid in sorted({(type(pr[1]) is nn.ReLU, type(pr[1]) is nn.Sigmoid) for pr in pairs.values()}):
+                            self._refuse("a forward, pre-forward or backward hook on the pair or its container", relu, sigmoid)
                         if _user_hooked(seq):
                             continue
                         pairs = {}                # (a hooked pair keeps the stock modules; the bare layers of the container stay)

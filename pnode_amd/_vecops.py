@@ -227,15 +227,16 @@ class HipVecOps(object):
     linear_flags = 0           # PN_LINEAR_FORM_PLAIN with -pn_linear_form plain: the K loop of linear_fwd / linear_bwd (the same bits)
 
     linear_relu = True         # linear_fwd and linear_bwd take act="relu" (PN_ACT_RELU; -pn_linear_relu 1)
-    _ACTS = {"identity": _lib.PN_ACT_IDENTITY, "tanh": _lib.PN_ACT_TANH, "relu": _lib.PN_ACT_RELU}
+    linear_sigmoid = True      # ... and act="sigmoid" (PN_ACT_SIGMOID; -pn_linear_sigmoid 1)
+    _ACTS = {"identity": _lib.PN_ACT_IDENTITY, "tanh": _lib.PN_ACT_TANH, "relu": _lib.PN_ACT_RELU, "sigmoid": _lib.PN_ACT_SIGMOID}
 
     def linear_fwd(self, x, w, b, tanh, y=None, flags=None, act=None):
         """y = act(x w^T + b), act = tanh or the identity; x (rows, in_f), w (out_f, in_f), b (out_f,) or None: contiguous fp32 on this device.
         Refused (PnError), never run another way, outside pn_linear_fwd_supported and where y shares memory with x, w or b.  flags: pn_linear_fwd_form's (default: linear_flags).
-        act: None -- `tanh` says which of the two --, or "identity", "tanh", "relu" by name (`tanh` is then not looked at); "relu" gives
-        relu of what the identity gives, value for value."""
+        act: None -- `tanh` says which of the two --, or "identity", "tanh", "relu", "sigmoid" by name (`tanh` is then not looked at);
+        "relu" gives relu of what the identity gives, value for value; "sigmoid" 1 / (1 + expf(-z)) of it, within 2.5 * 2^-24 of sigma."""
         if act is not None and act not in self._ACTS:
-            raise PnError("pn_linear_fwd: act %r: identity, tanh or relu" % (act,))
+            raise PnError("pn_linear_fwd: act %r: identity, tanh or relu or sigmoid" % (act,))
         code = self._ACTS[act] if act is not None else (_lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY)
         rows, in_f = x.shape
         out_f = w.shape[0]
@@ -261,9 +262,10 @@ class HipVecOps(object):
         """(gz, dx) = (g (1 - a^2), gz w); g, a (rows, out_f), w (out_f, in_f): contiguous fp32 on this device.  Refused (PnError), never
         run another way, outside pn_linear_bwd_supported, for an fp64 state, and where gz or dx shares memory with an input.
         flags: pn_linear_bwd_form's (default: linear_flags).  act="relu" (pn_linear_bwd_act): gz = threshold_backward(g, a, 0) bit for bit,
-        dx the bits of linear_dx(gz, w)."""
-        if act not in ("tanh", "relu"):
-            raise PnError("pn_linear_bwd: act %r: tanh or relu (no activation: linear_dx)" % (act,))
+        dx the bits of linear_dx(gz, w).  act="sigmoid" (pn_linear_bwd_act): gz = g fmaf(-a, a, a), two roundings, the same bits in every
+        form; dx the bits of linear_dx(gz, w)."""
+        if act not in ("tanh", "relu", "sigmoid"):
+            raise PnError("pn_linear_bwd: act %r: tanh or relu or sigmoid (no activation: linear_dx)" % (act,))
         rows, out_f = g.shape
         in_f = w.shape[1]
         for v in (g, a, w, gz, dx):
@@ -280,8 +282,8 @@ class HipVecOps(object):
         elif tuple(dx.shape) != (rows, in_f):
             raise PnError("pn_linear_bwd: dx (rows, in_f)")
         flags = self.linear_flags if flags is None else flags
-        if act == "relu":
-            check(self.lib.pn_linear_bwd_act(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), _lib.PN_ACT_RELU,
+        if act != "tanh":
+            check(self.lib.pn_linear_bwd_act(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), self._ACTS[act],
                                              gz.data_ptr(), dx.data_ptr(), flags))
         else:
             check(self.lib.pn_linear_bwd_form(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), gz.data_ptr(),

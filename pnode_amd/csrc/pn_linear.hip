@@ -888,17 +888,33 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
   float *yp = a.y + (size_t)row0 * out_f + col;
   const bool tanh_act = a.act == PN_ACT_TANH;
   const bool relu_act = a.act == PN_ACT_RELU;
+  // the Sigmoid epilogue is a loop of its own behind ONE uniform branch: inside the loop of the other three, its sixteen expf and
+  // divisions cost the tanh pairs 0.2 us per launch (the headline, option absent: -0.68 % over five interleaved runs)
+  auto finish = [&](auto sigmoid_c) {
+    constexpr bool SIGMOID = decltype(sigmoid_c)::value;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const float other = red[(w ^ 4) * 16 + e][lane];
-    const float first = kh == 0 ? acc0[e] : other, second = kh == 0 ? other : acc1[e];
-    float z = (first + second) + bias;
-    if (tanh_act) z = tanhf(z);
-    // relu of the identity's value: a positive z as it is, a NaN stays a NaN, everything else (-0 too) is +0 (not fmaxf: it drops a NaN)
-    if (relu_act) z = z > 0.f ? z : (z == z ? 0.f : z);
-    const int r = (e & 3) + 8 * (e >> 2);
-    if (colok && (!RAGGED || row0 + r < rows)) yp[(size_t)r * out_f] = z;
-  }
+    for (int e = 0; e < 16; ++e) {
+      const float other = red[(w ^ 4) * 16 + e][lane];
+      const float first = kh == 0 ? acc0[e] : other, second = kh == 0 ? other : acc1[e];
+      float z = (first + second) + bias;
+      if constexpr (SIGMOID) {
+        // the logistic function of the identity's value: expf within 1 ulp, one rounded add, one correctly rounded division (2.5 ulp of
+        // 2^-24 in all, never above 1).  expf(-z) overflows to +inf from z <= -88.8 on: 1 / inf is +0; it is below 2^-25 from z >= 17.4
+        // on: 1 / 1 is 1; a NaN goes through all three
+        z = 1.f / (1.f + expf(-z));
+      } else {
+        if (tanh_act) z = tanhf(z);
+        // relu of the identity's value: a positive z as it is, a NaN stays a NaN, everything else (-0 too) is +0 (not fmaxf: it drops a NaN)
+        if (relu_act) z = z > 0.f ? z : (z == z ? 0.f : z);
+      }
+      const int r = (e & 3) + 8 * (e >> 2);
+      if (colok && (!RAGGED || row0 + r < rows)) yp[(size_t)r * out_f] = z;
+    }
+  };
+  if (a.act == PN_ACT_SIGMOID)
+    finish(std::true_type{});
+  else
+    finish(std::false_type{});
 }
 
 // (pipelined: two sets of fragment and of load registers -- two waves per SIMD, as the LDS allows anyway)
@@ -937,11 +953,27 @@ struct BwdLoads {
 //   gz[r][k] = a[r][k] <= 0 ? +0 : g[r][k]
 // -- aten.threshold_backward(g, a, 0): a NaN in a lets g through, a == +-0 gives +0.  No arithmetic touches g: every element of gz is
 // g's bits or +0, so gz is threshold_backward's bit for bit and dx is what the bare body gives when fed that gz, in every form.
+// PN_ACT_SIGMOID (pn_linear_bwd_act), a the pair's output sigma(z):
+//   gz[r][k] = g[r][k] (a[r][k] - a[r][k]^2)
+// by sigmoid_gz below, the one spelling of all three forms: the same bits of gz in each, and dx is what the bare body gives when fed it.
+// a in {0, 1} with finite g: gz == 0; a NaN in a or g stays in its element; g = +-inf where a (1 - a) is 0: NaN (aten.sigmoid_backward's).
+
+// s = a - a a in ONE fma (a (1 - a) with one rounding, exactly 0 at a == 0 and a == 1), then ONE rounded product: two roundings in gz.
+// Contraction is off so that the product stays a product wherever this is inlined: in the pipelined loop it would otherwise be fused
+// into the split's first subtraction (fma(g, s, -hi)) -- other mid and lo terms, other bits in dx than the plain loop's.
+__device__ __forceinline__ f32x4 sigmoid_gz(const f32x4 g, const f32x4 a) {
+#pragma clang fp contract(off)
+  f32x4 z;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) z[e] = g[e] * __builtin_fmaf(-a[e], a[e], a[e]);
+  return z;
+}
+
 template <bool RAGGED, bool PIPE, int ACT = PN_ACT_TANH>
 __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   static_assert(!(RAGGED && PIPE), "the pipelined loop loads without tests");
-  static_assert(ACT == PN_ACT_TANH || ACT == PN_ACT_IDENTITY || ACT == PN_ACT_RELU, "tanh, none or ReLU");
-  constexpr bool BARE = ACT == PN_ACT_IDENTITY, RELU = ACT == PN_ACT_RELU;
+  static_assert(ACT == PN_ACT_TANH || ACT == PN_ACT_IDENTITY || ACT == PN_ACT_RELU || ACT == PN_ACT_SIGMOID, "tanh, none, ReLU or sigmoid");
+  constexpr bool BARE = ACT == PN_ACT_IDENTITY, RELU = ACT == PN_ACT_RELU, SIGMOID = ACT == PN_ACT_SIGMOID;
   constexpr int AROWB = 2 * FK, APART = FM * AROWB;              // gz: [64 rows][32 bf16], 4 KB per part
   constexpr int WROWB = 128, WIMG = FK * WROWB, WPART = 2 * WIMG;      // W: two [32 k][64 bf16] images, 8 KB per part
   constexpr int BUF = 3 * APART + 3 * WPART;                     // 36 KB
@@ -990,6 +1022,9 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
     if constexpr (RELU) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[e] = av[e] <= 0.f ? 0.f : gv[e];
+      if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
+    } else if constexpr (SIGMOID) {
+      z = sigmoid_gz(gv, av);
       if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
     } else if constexpr (!BARE) {
 #pragma unroll
@@ -1052,6 +1087,8 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
             if constexpr (RELU) {                // (nothing to contract: a compare and a select)
 #pragma unroll
               for (int e = 0; e < 4; ++e) z[e] = l.a[e] <= 0.f ? 0.f : l.g[e];
+            } else if constexpr (SIGMOID) {
+              z = sigmoid_gz(l.g, l.a);
             } else if constexpr (!BARE) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -1117,6 +1154,10 @@ __global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_dx_kernel_f32x3_pipe
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_relu_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_RELU>(a); }
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_relu_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_RELU>(a); }
 __global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_relu_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_RELU>(a); }
+// the Sigmoid pairs' (pn_linear_bwd_act with PN_ACT_SIGMOID): the same
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_sigmoid_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_SIGMOID>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_sigmoid_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_SIGMOID>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_sigmoid_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_SIGMOID>(a); }
 
 int cu_count() {
   static int n = 0;             // (the calling thread's current device; every device of a node is the same part)
@@ -1150,7 +1191,7 @@ int finish_t(hipStream_t st, int64_t out_f, int64_t in_f, void *pw, void *pb, vo
 }
 
 // what pn_linear_bwd_form and pn_linear_bwd_act share behind their own checks of `flags` (and of `act`): the shape rules, the null,
-// alignment and aliasing refusals, the choice of the form; act is PN_ACT_TANH or PN_ACT_RELU
+// alignment and aliasing refusals, the choice of the form; act is PN_ACT_TANH, PN_ACT_RELU or PN_ACT_SIGMOID
 int bwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
              void *gz, void *dx, int flags) {
   if (!pn_linear_bwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_bwd: unsupported dtype or shape (see pn_linear_bwd_supported)");
@@ -1172,6 +1213,11 @@ int bwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f,
   const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (out_f / FK) % 2 != 0;      // (the pipelined loop takes an even number of slabs)
   if (act == PN_ACT_RELU) {
     auto kern = ragged ? pn_linear_bwd_relu_kernel_f32x3_ragged : (plain ? pn_linear_bwd_relu_kernel_f32x3 : pn_linear_bwd_relu_kernel_f32x3_pipe);
+    return pn::launch("pn_linear_bwd_act", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
+  }
+  if (act == PN_ACT_SIGMOID) {
+    auto kern = ragged ? pn_linear_bwd_sigmoid_kernel_f32x3_ragged
+                       : (plain ? pn_linear_bwd_sigmoid_kernel_f32x3 : pn_linear_bwd_sigmoid_kernel_f32x3_pipe);
     return pn::launch("pn_linear_bwd_act", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
   }
   auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : (plain ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
@@ -1274,8 +1320,8 @@ int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
                        int act, void *y, int flags) {
   if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_fwd_form: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
   if (!pn_linear_fwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_fwd: unsupported dtype or shape (see pn_linear_fwd_supported)");
-  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH && act != PN_ACT_RELU)
-    return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY, PN_ACT_TANH or PN_ACT_RELU");
+  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID)
+    return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY, PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID");
   if (x == nullptr || w == nullptr || y == nullptr) return pn::fail("pn_linear_fwd: null operand");
   if (!pn::aligned16(x, w, y) || (reinterpret_cast<uintptr_t>(b) & 3)) return pn::fail("pn_linear_fwd: operands must be 16-byte aligned");
   // an output that shares bytes with anything the launch reads: other workgroups still read x, w and b while a tile of y is stored
@@ -1317,7 +1363,8 @@ int pn_linear_bwd_act(void *stream, int dtype, int64_t rows, int64_t out_f, int6
                       void *gz, void *dx, int flags) {
   if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_bwd_act: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
   if (act == PN_ACT_IDENTITY) return pn::fail("pn_linear_bwd_act: PN_ACT_IDENTITY has no prologue and no gz: use pn_linear_dx");
-  if (act != PN_ACT_TANH && act != PN_ACT_RELU) return pn::fail("pn_linear_bwd_act: act is PN_ACT_TANH or PN_ACT_RELU (PN_ACT_IDENTITY: use pn_linear_dx)");
+  if (act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID)
+    return pn::fail("pn_linear_bwd_act: act is PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID (PN_ACT_IDENTITY: use pn_linear_dx)");
   return bwd_pair(stream, dtype, rows, out_f, in_f, g, a, w, act, gz, dx, flags);
 }
 

@@ -28,6 +28,11 @@ is -- a stock module, or a bare layer under ``-pn_linear_bare 1``; ``1`` runs th
 ``pn_linear_fwd`` launch with ``PN_ACT_RELU`` and their backward -- ``g_z = threshold_backward(g, a, 0)``, ``dx = g_z W`` -- as one
 ``pn_linear_bwd_act`` launch (``-pn_linear_bwd 0`` keeps ``threshold_backward`` and ``matmul``), under the rules of the Tanh pairs.
 ``ode.linear_relu`` reports what runs.  ``-pn_linear_fwd 0`` switches this off too.
+``-pn_linear_sigmoid 0|1`` (read there too; anything else is refused): the same for the ``nn.Linear -> nn.Sigmoid`` pairs (exactly those
+types): ``0``, the default, leaves such a Linear a stock module, or a bare layer under ``-pn_linear_bare 1``; ``1`` runs the pair as one
+``pn_linear_fwd`` launch with ``PN_ACT_SIGMOID`` (``1 / (1 + expf(-z))``, within 2.5 * 2^-24 of sigma: not ``torch.sigmoid``'s bits) and
+its backward -- ``g_z = g a (1 - a)``, ``dx = g_z W`` -- as one ``pn_linear_bwd_act`` launch (``-pn_linear_bwd 0`` keeps
+``sigmoid_backward`` and ``matmul``).  ``ode.linear_sigmoid`` reports what runs.  ``-pn_linear_fwd 0`` switches this off too.
 """
 import os
 import shlex
