@@ -232,8 +232,12 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
  * NaN stays that NaN, everything else -- -0 too -- is +0; so y under PN_ACT_RELU is relu of the y under PN_ACT_IDENTITY in the same
  * form, value for value) or PN_ACT_SIGMOID (y = 1 / (1 + expf(-z)) of the biased sum z in fp32: expf of the device library, one rounded
  * add, one correctly rounded division -- within 2.5 * 2^-24 of sigma of the y under PN_ACT_IDENTITY in the same form; never above 1,
- * exactly 1 from z >= 40 on, exactly +0 from z <= -110 on, in (0, 1] for |z| <= 80, NaN for NaN; not torch.sigmoid's bits); any other
- * act -- 3 too, which names nothing -- is refused, nothing launched.  The product is the split-bf16 one of pn_linear_wgrad
+ * exactly 1 from z >= 40 on, exactly +0 from z <= -110 on, in (0, 1] for |z| <= 80, NaN for NaN; not torch.sigmoid's bits) or
+ * PN_ACT_GELU (exact GELU, approximate='none': y = 0.5f * z * (1.f + erff(z * 0.70710678f)) of the biased sum z in fp32, never contracted,
+ * spelled once: the same bits of y in every form.  erff is the device library's, whose bound this file does not know: the error is
+ * MEASURED, see pn_linear_fwd_pre below; y is exactly z from z >= 6 on and exactly -0 from z <= -6 on, NaN for NaN; not F.gelu's bits.
+ * y alone is for evaluations nobody differentiates: GELU's derivative needs z, which pn_linear_fwd_pre writes beside y); any other
+ * act -- 3, 5 and 7 too, which name nothing -- is refused, nothing launched.  The product is the split-bf16 one of pn_linear_wgrad
  * (three exact bf16 terms per operand, the six largest cross products, fp32 accumulation on v_mfma_f32_32x32x16_bf16; an infinite
  * operand gives NaN); one workgroup owns a 64 x 128 tile of y over all of in_f and writes it once: no atomics, no work buffers, the
  * same bits on every launch.  x, w, y non-NULL and 16-byte aligned, b 4-byte aligned; y shares no byte with x, w or b (other workgroups
@@ -245,6 +249,7 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
 #define PN_ACT_TANH 1
 #define PN_ACT_RELU 2
 #define PN_ACT_SIGMOID 4 /* (3 names nothing and is refused) */
+#define PN_ACT_GELU 8    /* (5 and 7 name nothing and are refused) */
 int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
 int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
                   void *y);
@@ -256,6 +261,21 @@ int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
 #define PN_LINEAR_FORM_PLAIN 1
 int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b,
                        int act, void *y, int flags);
+/* pn_linear_fwd_form with a SECOND output, the pre-activation:  z = x w^T + b  (rows x out_f, fp32) beside  y = act(z), for the pairs
+ * whose derivative is a function of z and not of y (GELU: not monotonic, z cannot be had back from y).  The epilogue stores z at y's tile
+ * positions under y's guards: one more 4-byte store per element, no scratch, no LDS beyond pn_linear_fwd's, no atomics.  z has the bits of
+ * the y that PN_ACT_IDENTITY gives in the same form, and y the bits pn_linear_fwd_form gives for the same act, for every act (under
+ * PN_ACT_IDENTITY z == y).  PN_ACT_GELU has no closed bound (the device library states none for erff); MEASURED on MI355X against float64
+ * GELU of z, |z| < 6 (tools/mb_linear_gelu.py, tests/test_gpu_linear_gelu.py): |y - gelu(z)| at most 7.4 * 2^-24, at most 2.1 * 2^-24
+ * max(1, |z|) -- the figures of fp32 F.gelu on the same z, digit for digit; absolute, because 1 + erff cancels for negative z: there
+ * the error is small and the RELATIVE error is not bounded; y == z exactly for z >= 6, y == -0 for z <= -6 (erff is exactly +-1 from |z| of about 5.6 on), a NaN in a row
+ * of x gives NaN in that row of y and of z and touches no other row.  z must be non-NULL (y alone: pn_linear_fwd_form), 16-byte aligned,
+ * and share no byte with y, x, w or b; everything pn_linear_fwd_form refuses is refused here: nothing is launched, y and z are untouched.
+ * Replaces, in the solver's evaluations of func that autograd will differentiate (the stage VJPs of the reverse sweep: the body of
+ * RHSJacShell.multTranspose, petsc_adjoint.py:318-339), the library GEMM and the gelu kernel of an nn.Linear -> nn.GELU pair, whose
+ * saved tensor is that z. */
+int pn_linear_fwd_pre(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
+                      void *y, void *z, int flags);
 
 /* The backward of such a pair with respect to its input in one launch (csrc/pn_linear.hip): for g (the cotangent at the pair's output)
  * and a (the pair's output, tanh of the biased sum) rows x out_f, w out_f x in_f AS IT LIES (no transposed copy is read or kept: an
@@ -290,6 +310,15 @@ int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
  * a == 0 or a == 1 with finite g gives gz == 0; a NaN in a or g stays in its own element of gz and its own row of dx; g = +-inf where s
  * is 0 gives NaN, as in aten.sigmoid_backward.  dx has the bits of pn_linear_dx fed that gz, in every form.  Replaces the
  * sigmoid_backward kernel and the library GEMM of the pair.
+ * act == PN_ACT_GELU is the backward of an nn.Linear -> nn.GELU pair (approximate='none'); a is then the pair's PRE-activation z (what
+ * pn_linear_fwd_pre wrote), not its output:
+ *   gz[r][k] = g[r][k] d,  d = cdf + z pdf,  cdf = 0.5f * (1.f + erff(z * 0.70710678f)),  pdf = expf(-0.5f * z * z) * 0.3989423f
+ * -- aten.gelu_backward's formula, never contracted, spelled once: the same bits of gz in every form.  Measured on MI355X against
+ * float64 (tools/mb_linear_gelu.py): |gz - g d(z)| / |g| at most 3.2 * 2^-24 (aten.gelu_backward on the same operands: 3.1) -- absolute in
+ * d, which crosses zero near z = -0.7518.  d is exactly 1
+ * from z >= 6 on (gz == g); from z <= -6 down cdf is 0 and d = z pdf, below 4e-8 in size, an exact -0 once expf underflows; a NaN in a or g stays in its own element of gz and its own row of dx; g = +-inf
+ * where d is 0 gives NaN, as in aten.gelu_backward.  dx has the bits of pn_linear_dx fed that gz, in every form.  Replaces the
+ * gelu_backward kernel and the library GEMM of the pair.
  * PN_ACT_IDENTITY is refused (no prologue, no gz: use pn_linear_dx); so is any other value, and an unknown flag; nothing is launched. */
 int pn_linear_bwd_act(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
                       void *gz, void *dx, int flags);

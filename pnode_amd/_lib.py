@@ -47,6 +47,7 @@ PN_WGRAD_EXACT_FP32 = 1
 PN_WGRAD_TILE_64 = 2
 PN_ACT_IDENTITY, PN_ACT_TANH, PN_ACT_RELU = 0, 1, 2
 PN_ACT_SIGMOID = 4            # (3 names nothing: refused)
+PN_ACT_GELU = 8               # (5 and 7 name nothing: refused)
 PN_LINEAR_FORM_PLAIN = 1      # pn_linear_fwd_form / pn_linear_bwd_form flag: the plain K loop on an aligned shape too
 PN_ABI_VERSION = 4
 PN_DENSE_MAX_POW = 4          # columns of a continuous extension's P matrix (pn_tableau_dense)
@@ -145,6 +146,7 @@ PROTOTYPES = {
     "pn_linear_fwd_supported": (_i, [_i, _i64, _i64, _i64]),
     "pn_linear_fwd": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp]),
     "pn_linear_fwd_form": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp, _i]),
+    "pn_linear_fwd_pre": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i]),
     "pn_linear_bwd_supported": (_i, [_i, _i64, _i64, _i64]),
     "pn_linear_bwd": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pn_linear_bwd_form": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i]),

@@ -59,7 +59,23 @@ it.  The pair runs through ``_LinearTanh`` with ``call.sigmoid``: forward ``pn_l
 ``torch.sigmoid(F.linear)`` to ``1e-6 (sum |x w| + |b|) + 4 * 2^-24`` -- the absolute term because a zero pre-activation maps to 0.5 with
 a rounding of its own on either side (the kernel at most 2.5, the library about 1 ulp of 2^-24), where tanh and ReLU give an exact 0;
 ``g_z`` to ``1.5 * 2^-24 |g|`` of ``sigmoid_backward``'s (two roundings here, three there, relative to ``g a (1 - a) <= |g| / 4``); ``dx``
-in the pairs' measure.  A miss switches off the Sigmoid pairs, or their backward, only."""
+in the pairs' measure.  A miss switches off the Sigmoid pairs, or their backward, only.
+
+GELU pairs (``-pn_linear_gelu 0|1``, default ``0``: nothing below happens): the SAVED PRE-ACTIVATION form.  The derivative of every
+activation above is a function of the pair's output ``a``, so their Function saves ``(x, w, a)``.  GELU is not monotonic: its derivative
+needs ``z = x W^T + b``, which cannot be had back from ``a``.  With ``1`` two consecutive children ``nn.Linear``, exactly ``nn.GELU`` with
+``approximate == 'none'`` of an eligible container are a pair under the same rules (``approximate='tanh'`` is none: its reason is in
+``refused`` under ``(class name, "GELU")`` and in the status); one record, ``LinearFwd.gelu``.  The pair runs through ``_LinearGelu``.
+An evaluation that will be differentiated (grad mode on and the input or a parameter requires a gradient) launches ``pn_linear_fwd_pre``:
+``y`` and ``z`` from one epilogue; ``(x, w, z)`` is saved and ``y`` is not -- the memory of the stock pair.  Any other evaluation (the
+forward sweep without retained tapes) launches ``pn_linear_fwd`` with ``PN_ACT_GELU`` and allocates no ``z``.  ``LinearFwd.gelu.n``
+counts both, ``n_pre`` the first kind, ``n_y`` the second.  Backward: ``g_z = g (cdf + z pdf)`` and ``dx = g_z W`` in one launch
+(``pn_linear_bwd_act`` with ``PN_ACT_GELU``, reading ``z``) on a backend with ``linear_gelu``, else ``gelu_backward`` and ``matmul``.
+Self-checks as the Sigmoid pairs': the forward against ``F.gelu(F.linear)`` to ``1e-6 (sum |x w| + |b|) + 4 * 2^-24`` (GELU crosses zero
+at ``z = 0``: rows of scale 0 must have a bar above 0), ``z`` against ``F.linear`` in the bare layer's measure; ``g_z`` to ``32 * 2^-24 |g|``
+of ``gelu_backward``'s -- absolute in the derivative, which crosses zero near ``z = -0.7518``: two evaluations of ``erff``, each within
+the 16 ulp that OpenCL allows ``erf``, halved in ``cdf`` --; ``dx`` in the pairs' measure.  A miss switches off the GELU pairs, or their
+backward, only."""
 import contextlib
 import warnings
 import weakref
@@ -100,7 +116,7 @@ def _user_hooked(m):
 
 def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
     """The static half of the eligibility rules for the Linear `lin` (and the activation `act` behind it, exactly a `kind`: nn.Tanh or
-    nn.ReLU or nn.Sigmoid; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
+    nn.ReLU or nn.Sigmoid or nn.GELU; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
     mods = (lin,) if act is None else (lin, act)
     if type(seq) is not nn.Sequential or "forward" in seq.__dict__:
         return "the container's forward is not nn.Sequential's own"
@@ -121,14 +137,16 @@ def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
     return why
 
 
-def find_layers(func, params, relu=False, sigmoid=False):
+def find_layers(func, params, relu=False, sigmoid=False, gelu=False):
     """(plans, refused, bare): [(sequential, {index of the Linear child: (linear, tanh)})] of func; {class name of a container: reason}
     for the Linear -> Tanh pairs that cannot be fused (what -pn_linear_fwd 1 warns about); and [(sequential, {index of the child:
     linear})] for the bare layers -- exactly nn.Linear, opening no fused pair, under the same static rules (-pn_linear_bare 1).
     relu (-pn_linear_relu 1): two consecutive children nn.Linear, nn.ReLU are a pair too, under the rules of a tanh pair -- (linear, relu)
     in `plans`, told from a tanh pair by its second member, and such a Linear is no bare layer; a ReLU pair that cannot be fused is in
     `refused` under the key (class name of the container, "ReLU").  Without it the three are what they were before there was the option.
-    sigmoid (-pn_linear_sigmoid 1): the same for nn.Linear, nn.Sigmoid; the key in `refused` is (class name, "Sigmoid")."""
+    sigmoid (-pn_linear_sigmoid 1): the same for nn.Linear, nn.Sigmoid; the key in `refused` is (class name, "Sigmoid").
+    gelu (-pn_linear_gelu 1): the same for nn.Linear, nn.GELU with approximate == 'none'; the key in `refused` is (class name, "GELU"),
+    also for an nn.GELU(approximate='tanh'), whose Linear is then a stock module or a bare layer."""
     plans, refused, bare = [], {}, []
     if not isinstance(func, nn.Module):
         return plans, refused, bare
@@ -155,9 +173,13 @@ def find_layers(func, params, relu=False, sigmoid=False):
                 kind, key = nn.ReLU, (type(seq).__name__, "ReLU")
             elif sigmoid and isinstance(act, nn.Sigmoid):
                 kind, key = nn.Sigmoid, (type(seq).__name__, "Sigmoid")
+            elif gelu and isinstance(act, nn.GELU):
+                kind, key = nn.GELU, (type(seq).__name__, "GELU")
             else:
                 continue
             why = _static_why(seq, kids, lin, act, index, owners, kind)
+            if why is None and kind is nn.GELU and getattr(act, "approximate", "none") != "none":
+                why = "nn.GELU(approximate=%r): only the exact GELU (approximate='none') is owned" % (act.approximate,)
             if why is None:
                 pairs[i] = (lin, act)
             else:
@@ -178,7 +200,7 @@ def find_pairs(func, params):
 
 class _Call(object):
     """What one fused call carries into its backward."""
-    __slots__ = ("owner", "module", "grads", "ev", "version", "relu", "sigmoid")
+    __slots__ = ("owner", "module", "grads", "ev", "version", "relu", "sigmoid", "pre")
 
 
 class _PairState(object):
@@ -193,6 +215,8 @@ class _PairState(object):
         self.why = None
         self.checked = False
         self.n = 0                 # pair calls that ran as one launch
+        self.n_pre = 0             # ... those of them that also wrote the pre-activation (pn_linear_fwd_pre; the GELU pairs)
+        self.static_why = None     # why a pair of this kind is none (find_layers' `refused`), for the status
         self.bwd_disabled = False  # the backward check failed (the forward stays)
         self.bwd_why = None
         self.bwd_checked = False
@@ -206,11 +230,16 @@ class _PairState(object):
         return self.mode == "1" and bool(self.plans) and not self.disabled
 
     @property
+    def n_y(self):
+        """Pair calls that ran the y-only form: nobody differentiates them."""
+        return self.n - self.n_pre
+
+    @property
     def status(self):
         if self.mode != "1":
             return "off (%s 0)" % self.option
         if not self.plans:
-            return "stock modules (no eligible Linear -> %s pair)" % self.name
+            return "stock modules (no eligible Linear -> %s pair%s)" % (self.name, "" if self.static_why is None else ": " + self.static_why)
         if self.disabled:
             return "stock modules (%s)" % self.why
         return "fused (%d pairs; %d forward, %d backward calls so far%s)" % (
@@ -254,6 +283,33 @@ class _LinearTanh(torch.autograd.Function):
                 g_z = torch.ops.aten.sigmoid_backward(g, a)
             else:
                 g_z = torch.ops.aten.threshold_backward(g, a, 0) if call.relu else torch.ops.aten.tanh_backward(g, a)
+            dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
+        dw, db = _param_grads(ctx, call, g_z, x, w)
+        return dx, dw, db, None
+
+
+class _LinearGelu(torch.autograd.Function):
+    """A Linear -> GELU pair (-pn_linear_gelu 1): the sibling of _LinearTanh that saves the PRE-activation.  call.pre: somebody will
+    differentiate this evaluation -- y and z from one launch, (x, w, z) saved, y not; else y alone and nothing saved."""
+    @staticmethod
+    def forward(ctx, x, w, b, call):
+        y2, z2 = call.owner.kernel_gelu(x.reshape(-1, w.shape[1]), w, b, call.pre)
+        shape = x.shape[:-1] + (w.shape[0],)
+        if call.pre:
+            ctx.save_for_backward(x, w, _shaped(z2, shape))
+        ctx.call = call
+        ctx.has_bias = b is not None
+        return _shaped(y2, shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, z = ctx.saved_tensors
+        call = ctx.call
+        fused = call.owner._backward(g, z, w, gelu=True) if ctx.needs_input_grad[0] else None
+        if fused is not None:
+            g_z, dx = fused
+        else:
+            g_z = torch.ops.aten.gelu_backward(g, z, approximate="none")
             dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
         dw, db = _param_grads(ctx, call, g_z, x, w)
         return dx, dw, db, None
@@ -349,33 +405,43 @@ class LinearFwd(object):
         self._warned_relu_bwd = False
         # the Linear -> Sigmoid pairs (-pn_linear_sigmoid 0|1): the same in one record
         self.sig = _PairState("Sigmoid", "-pn_linear_sigmoid", "torch.sigmoid(F.linear)", "sigmoid_backward + matmul")
+        # the Linear -> GELU pairs (-pn_linear_gelu 0|1): one more record; the pairs that save their pre-activation
+        self.gelu = _PairState("GELU", "-pn_linear_gelu", "F.gelu(F.linear)", "gelu_backward + matmul")
 
-    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0", relu_mode="0", sigmoid_mode="0"):
+    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0", relu_mode="0", sigmoid_mode="0", gelu_mode="0"):
         """Find the eligible pairs of `func` (and, with bare_mode "1", its bare layers; with relu_mode "1", its Linear -> ReLU pairs; with
-        sigmoid_mode "1", its Linear -> Sigmoid pairs); returns True when there is at least one."""
+        sigmoid_mode "1", its Linear -> Sigmoid pairs; with gelu_mode "1", its Linear -> GELU pairs); returns True when there is at least
+        one."""
         self.mode = mode
         self.bwd_mode = bwd_mode
         self.bare_mode = bare_mode
         self.relu_mode = relu_mode
         self.sig.mode = sigmoid_mode
         self.sig.refused = None
-        found, refused, self.bare = find_layers(func, params, relu_mode == "1", sigmoid=sigmoid_mode == "1")
-        self.plans, self.relu, self.sig.plans = [], [], []
+        self.gelu.mode = gelu_mode
+        self.gelu.refused = None
+        found, refused, self.bare = find_layers(func, params, relu_mode == "1", sigmoid=sigmoid_mode == "1", gelu=gelu_mode == "1")
+        self.gelu.static_why = next((why for key, why in refused.items() if isinstance(key, tuple) and key[1] == "GELU"), None)
+        self.plans, self.relu, self.sig.plans, self.gelu.plans = [], [], [], []
         for seq, pairs in found:
-            for kind, plans in ((nn.Tanh, self.plans), (nn.ReLU, self.relu), (nn.Sigmoid, self.sig.plans)):
+            for kind, plans in ((nn.Tanh, self.plans), (nn.ReLU, self.relu), (nn.Sigmoid, self.sig.plans), (nn.GELU, self.gelu.plans)):
                 mine = {i: p for i, p in pairs.items() if type(p[1]) is kind}
                 if mine:
                     plans.append((seq, mine))
         if mode == "1" and refused:
             for key, why in refused.items():
                 cls, name = key if isinstance(key, tuple) else (key, "Tanh")
-                if self.sig.warned if name == "Sigmoid" else (self._warned_relu if name == "ReLU" else self._warned):
+                if name == "GELU":
+                    if self.gelu.warned:
+                        continue
+                elif self.sig.warned if name == "Sigmoid" else (self._warned_relu if name == "ReLU" else self._warned):
                     continue
                 warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair of %s runs the stock modules: %s" % (name, cls, why), RuntimeWarning)
             self._warned = self._warned or any(not isinstance(key, tuple) for key in refused)
             self._warned_relu = self._warned_relu or any(isinstance(key, tuple) and key[1] == "ReLU" for key in refused)
             self.sig.warned = self.sig.warned or any(isinstance(key, tuple) and key[1] == "Sigmoid" for key in refused)
-        return bool(self.plans) or self.bare_active or self.relu_active or self.sig.active
+            self.gelu.warned = self.gelu.warned or any(isinstance(key, tuple) and key[1] == "GELU" for key in refused)
+        return bool(self.plans) or self.bare_active or self.relu_active or self.sig.active or self.gelu.active
 
     @property
     def bare_active(self):
@@ -387,7 +453,7 @@ class LinearFwd(object):
 
     @property
     def active(self):
-        return (bool(self.plans) and not self.disabled) or self.bare_active or self.relu_active or self.sig.active
+        return (bool(self.plans) and not self.disabled) or self.bare_active or self.relu_active or self.sig.active or self.gelu.active
 
     # what the Sigmoid pairs' record holds, under the names the tanh and ReLU pairs' fields have
     @property
@@ -410,6 +476,23 @@ class LinearFwd(object):
     def n_sigmoid_bwd(self):
         return self.sig.n_bwd
 
+    # ... and the GELU pairs' (`gelu` is the record itself)
+    @property
+    def gelu_active(self):
+        return self.gelu.active
+
+    @property
+    def gelu_status(self):
+        return self.gelu.status
+
+    @property
+    def n_gelu(self):
+        return self.gelu.n
+
+    @property
+    def n_gelu_bwd(self):
+        return self.gelu.n_bwd
+
     # the one place the device is touched: tests of the eligibility rules replace it by the torch expression
     def kernel(self, x2, w, b):
         return self._ode()._ops.linear_fwd(x2, w, b, True)
@@ -423,6 +506,14 @@ class LinearFwd(object):
     def kernel_sigmoid(self, x2, w, b):
         return self._ode()._ops.linear_fwd(x2, w, b, False, act="sigmoid")
 
+    def kernel_gelu(self, x2, w, b, pre):
+        """(y, z): z the pre-activation from the same launch (pn_linear_fwd_pre) when `pre`, else None and no tensor allocated for it."""
+        ops = self._ode()._ops
+        if not pre:
+            return ops.linear_act_fwd(x2, w, b, "gelu"), None
+        z = torch.empty((x2.shape[0], w.shape[0]), dtype=x2.dtype, device=x2.device)
+        return ops.linear_act_fwd(x2, w, b, "gelu", z=z), z
+
     def supported(self, rows, out_f, in_f):
         key = (rows, out_f, in_f)
         ok = self._ok.get(key)
@@ -431,7 +522,12 @@ class LinearFwd(object):
             ok = self._ok[key] = bool(hasattr(ops, "linear_fwd_supported") and ops.linear_fwd_supported(rows, out_f, in_f))
         return ok
 
-    def _refuse(self, why, relu=False, sigmoid=False):
+    def _refuse(self, why, relu=False, sigmoid=False, gelu=False):
+        if gelu:
+            if self.mode == "1" and not self.gelu.warned:
+                self.gelu.warned = True
+                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> GELU pair runs the stock modules: %s" % why, RuntimeWarning)
+            return None
         if self.mode == "1" and not (self.sig.warned if sigmoid else (self._warned_relu if relu else self._warned)):
             if sigmoid:
                 self.sig.warned = True
@@ -483,6 +579,37 @@ class LinearFwd(object):
         if not float(over) <= 1.0:
             st.disabled = True
             st.why = "pn_linear_fwd and %s differ by %.2f times the bar %.0e (sum |x w| + |b|) + 4 * 2^-24" % (st.torch_fwd, float(over), CHECK_TOL)
+            warnings.warn("pnode_amd: the fused Linear -> %s forward is switched off for this solver: %s" % (st.name, st.why), RuntimeWarning)
+            return False
+        return True
+
+    def _check_gelu(self, x, w, b, a, z=None):
+        """First fused call of a GELU pair of a solver: against F.gelu(F.linear), |y - ref| <= CHECK_TOL (sum |x w| + |b|) + 4 * 2^-24.
+        The absolute term: GELU crosses zero at z = 0 -- a row with x = 0 and b = 0 has the scale 0 and the bar must stay above it; next
+        to it the two erff (the kernel's and the library's) differ by their own ulps of a value up to 1, not of y.  z, where the call
+        wrote it: against F.linear in the bare layer's measure.  A miss switches off the GELU pairs only."""
+        st = self.gelu
+        st.checked = True
+        with torch.no_grad():
+            x2 = x.reshape(-1, w.shape[1])
+            lin = F.linear(x2, w, b)
+            ref = F.gelu(lin)
+            scale = x2.abs() @ w.abs().t()
+            if b is not None:
+                scale = scale + b.abs()
+            ok = torch.isfinite(ref) & torch.isfinite(scale)
+            if not bool(ok.any()):
+                st.checked = False
+                return True
+            bar = CHECK_TOL * scale + 4.0 * 2.0 ** -24
+            over = ((a.reshape(ref.shape) - ref).abs() / bar)[ok].max()
+            what = "pn_linear_fwd and %s" % st.torch_fwd
+            if z is not None and float(over) <= 1.0:
+                over = ((z.reshape(ref.shape) - lin).abs() / bar)[ok].max()
+                what = "the pre-activation of pn_linear_fwd_pre and F.linear"
+        if not float(over) <= 1.0:
+            st.disabled = True
+            st.why = "%s differ by %.2f times the bar %.0e (sum |x w| + |b|) + 4 * 2^-24" % (what, float(over), CHECK_TOL)
             warnings.warn("pnode_amd: the fused Linear -> %s forward is switched off for this solver: %s" % (st.name, st.why), RuntimeWarning)
             return False
         return True
@@ -544,10 +671,14 @@ class LinearFwd(object):
     def kernel_bwd_sigmoid(self, g2, a2, w):
         return self._ode()._ops.linear_bwd(g2, a2, w, act="sigmoid")
 
-    def _bwd_fusable(self, g, a, w, relu=False, sigmoid=False):
+    def kernel_bwd_gelu(self, g2, z2, w):
+        return self._ode()._ops.linear_bwd(g2, z2, w, act="gelu")
+
+    def _bwd_fusable(self, g, a, w, relu=False, sigmoid=False, gelu=False):
         """None, or the reason (a string) this backward runs the torch operations.  a: the pair's output; None for a bare layer
         (pn_linear_dx: the same rules minus everything about a).  relu: a ReLU pair (pn_linear_bwd_act: the rules of a tanh pair, and
-        a backend with `linear_relu`).  sigmoid: a Sigmoid pair (the same, and a backend with `linear_sigmoid`)."""
+        a backend with `linear_relu`).  sigmoid: a Sigmoid pair (the same, and a backend with `linear_sigmoid`).  gelu: a GELU pair (the same, and a
+        backend with `linear_gelu`; `a` is then the pair's pre-activation)."""
         bare = a is None
         entry = "linear_dx" if bare else "linear_bwd"
         ode = self._ode()
@@ -557,9 +688,14 @@ class LinearFwd(object):
             return "the backend has no linear_relu"
         if sigmoid and not getattr(ode._ops, "linear_sigmoid", False):
             return "the backend has no linear_sigmoid"
+        if gelu and not getattr(ode._ops, "linear_gelu", False):
+            return "the backend has no linear_gelu"
         if self.bwd_mode == "0":
             return "-pn_linear_bwd 0"
-        if sigmoid:
+        if gelu:
+            if self.gelu.bwd_disabled:
+                return self.gelu.bwd_why
+        elif sigmoid:
             if self.sig.bwd_disabled:
                 return self.sig.bwd_why
         elif relu:
@@ -651,11 +787,38 @@ class LinearFwd(object):
             return gz_t, dx_t
         return None
 
-    def _backward(self, g, a, w, relu=False, sigmoid=False):
-        """(g_z, dx) of one pair by pn_linear_bwd (relu, sigmoid: pn_linear_bwd_act), or None: the caller runs tanh_backward
-        (threshold_backward, sigmoid_backward) and matmul."""
-        st = self.sig
-        why = self._bwd_fusable(g, a, w, relu, sigmoid)
+    def _check_gelu_bwd(self, g2, z2, w, gz, dx):
+        """First fused backward of a GELU pair of a solver: both results through torch as well.  gz to 32 * 2^-24 |g| of gelu_backward's,
+        elementwise and ABSOLUTE in the derivative d = cdf + z pdf, which crosses zero near z = -0.7518 (a bar relative to |g d| would be 0
+        there): each side evaluates erff once, within the 16 ulp OpenCL allows erf, of a value up to 1, halved in cdf -- 8 * 2^-24 a
+        side; z pdf <= 0.25 adds less than one more; twice that for the two sides.  dx to CHECK_TOL of |gz| |w| (the pairs' measure).
+        Returns None, or the torch results after switching the fused GELU backward -- only it -- off."""
+        st = self.gelu
+        st.bwd_checked = True
+        gz_t = torch.ops.aten.gelu_backward(g2, z2, approximate="none")
+        dx_t = torch.matmul(gz_t, w)
+        scale = gz_t.abs() @ w.abs()
+        fin = torch.isfinite(gz_t)
+        ok = torch.isfinite(dx_t) & (scale > 0)
+        if not bool(fin.any()) or not bool(ok.any()):
+            st.bwd_checked = False                 # nothing to judge by: the next call is checked
+            return None
+        bad_z = bool((~((gz - gz_t).abs() <= 32.0 * 2.0 ** -24 * g2.abs()) & fin).any())
+        err = float(((dx - dx_t).abs() / scale)[ok].max())
+        if bad_z or not err <= CHECK_TOL:
+            st.bwd_disabled = True
+            st.bwd_why = "pn_linear_bwd_act and %s differ: " % st.torch_bwd + (
+                "g_z by more than 32 * 2^-24 |g|" if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
+            warnings.warn("pnode_amd: the fused Linear -> %s backward is switched off for this solver: %s" % (st.name, st.bwd_why), RuntimeWarning)
+            return gz_t, dx_t
+        return None
+
+    def _backward(self, g, a, w, relu=False, sigmoid=False, gelu=False):
+        """(g_z, dx) of one pair by pn_linear_bwd (relu, sigmoid, gelu: pn_linear_bwd_act; gelu: `a` is the pre-activation), or None: the
+        caller runs tanh_backward (threshold_backward, sigmoid_backward, gelu_backward) and matmul."""
+        st = self.gelu if gelu else self.sig
+        sigmoid = sigmoid or gelu                  # (below: the pairs whose state is a record, `st`)
+        why = self._bwd_fusable(g, a, w, relu, sigmoid and not gelu, gelu)
         if why is not None:
             if self.bwd_mode == "1" and not (st.warned_bwd if sigmoid else (self._warned_relu_bwd if relu else self._warned_bwd)):
                 if sigmoid:
@@ -665,12 +828,15 @@ class LinearFwd(object):
                 else:
                     self._warned_bwd = True
                 warnings.warn("pnode_amd: -pn_linear_bwd 1: the backward of a Linear -> %s pair runs the torch operations: %s"
-                              % ("Sigmoid" if sigmoid else ("ReLU" if relu else "Tanh"), why), RuntimeWarning)
+                              % (st.name if sigmoid else ("ReLU" if relu else "Tanh"), why), RuntimeWarning)
             return None
         out_f, in_f = w.shape
         g2, a2 = g.reshape(-1, out_f), a.reshape(-1, out_f)
         with torch.no_grad():
-            if sigmoid:
+            if gelu:
+                gz, dx = self.kernel_bwd_gelu(g2, a2, w)
+                checked, check = st.bwd_checked, self._check_gelu_bwd
+            elif sigmoid:
                 gz, dx = self.kernel_bwd_sigmoid(g2, a2, w)
                 checked, check = st.bwd_checked, self._check_sigmoid_bwd
             elif relu:
@@ -763,12 +929,14 @@ class LinearFwd(object):
     def _pair(self, lin, act, x, grads):
         """One pair: Linear -> Tanh or, where `act` is an nn.ReLU, Linear -> ReLU (its module is not called: either `inplace` will do), or,
         where it is an nn.Sigmoid, Linear -> Sigmoid."""
-        relu, sigmoid = type(act) is nn.ReLU, type(act) is nn.Sigmoid
+        relu, sigmoid, gelu = type(act) is nn.ReLU, type(act) is nn.Sigmoid, type(act) is nn.GELU
         why = self._fusable(lin, x)
         if why is not None:
             if sigmoid:
                 self.sig.refused = why
-            self._refuse(why, relu, sigmoid)
+            if gelu:
+                self.gelu.refused = why
+            self._refuse(why, relu, sigmoid, gelu)
             return act(lin(x))
         w, b = lin.weight, lin.bias
         ev = grads.recording if grads is not None else None
@@ -776,15 +944,28 @@ class LinearFwd(object):
             ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
         call = _Call()
         call.owner, call.module, call.grads, call.ev, call.version, call.relu, call.sigmoid = self, lin, grads, ev, x._version, relu, sigmoid
-        a = _LinearTanh.apply(x, w, b, call)
-        checked = self.sig.checked if sigmoid else (self.relu_checked if relu else self.checked)
+        if gelu:
+            # the saved-pre-activation form only where somebody will differentiate the call: else y alone, and no z is allocated
+            call.pre = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad))
+            a = _LinearGelu.apply(x, w, b, call)
+        else:
+            a = _LinearTanh.apply(x, w, b, call)
+        checked = self.gelu.checked if gelu else (self.sig.checked if sigmoid else (self.relu_checked if relu else self.checked))
         if not checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
             args = (x.detach(), w.detach(), None if b is None else b.detach(), a.detach())
-            if not (self._check_sigmoid(*args) if sigmoid else self._check(*args, relu=relu)):
+            if gelu:
+                z = a.grad_fn.saved_tensors[2] if call.pre and a.grad_fn is not None else None
+                good = self._check_gelu(*args, z=z)
+            else:
+                good = self._check_sigmoid(*args) if sigmoid else self._check(*args, relu=relu)
+            if not good:
                 return act(lin(x))
         if ev is not None and a.grad_fn is not None:
             ev.through[a.grad_fn] = x.grad_fn     # Evaluation.clean passes the pair along its input edge only
-        if sigmoid:
+        if gelu:
+            self.gelu.n += 1
+            self.gelu.n_pre += 1 if call.pre else 0
+        elif sigmoid:
             self.sig.n += 1
         elif relu:
             self.n_relu += 1
@@ -815,6 +996,8 @@ class LinearFwd(object):
         """The forward check of the pairs of `act`'s kind failed."""
         if type(act) is nn.Sigmoid:
             return self.sig.disabled
+        if type(act) is nn.GELU:
+            return self.gelu.disabled
         return self.relu_disabled if type(act) is nn.ReLU else self.disabled
 
     def _runner(self, seq, pairs, alone, grads):
@@ -838,12 +1021,13 @@ class LinearFwd(object):
 
     def _containers(self):
         """[(sequential, its pairs, its bare layers)]: the pairs while their forward is on (the ReLU pairs with -pn_linear_relu 1, the
-        Sigmoid pairs with -pn_linear_sigmoid 1), the bare layers with -pn_linear_bare 1."""
+        Sigmoid pairs with -pn_linear_sigmoid 1, the GELU pairs with -pn_linear_gelu 1), the bare layers with -pn_linear_bare 1."""
         out = {}
         if not self.disabled:
             for seq, pairs in self.plans:
                 out[id(seq)] = (seq, pairs, {})
-        for plans in ((self.relu,) if self.relu_active else ()) + ((self.sig.plans,) if self.sig.active else ()):
+        for plans in ((self.relu,) if self.relu_active else ()) + ((self.sig.plans,) if self.sig.active else ()) \
+                + ((self.gelu.plans,) if self.gelu.active else ()):
             for seq, pairs in plans:
                 both = dict(out[id(seq)][1]) if id(seq) in out else {}      # (a copy: the container's tanh pairs stay their own map)
                 both.update(pairs)
@@ -864,8 +1048,9 @@ class LinearFwd(object):
                     if "forward" in seq.__dict__ or type(seq) is not nn.Sequential:
                         continue
                     if _user_hooked(seq) or any(_user_hooked(m) for pr in pairs.values() for m in pr):
-                        for relu, sigmoid in sorted({(type(pr[1]) is nn.ReLU, type(pr[1]) is nn.Sigmoid) for pr in pairs.values()}):
-                            self._refuse("a forward, pre-forward or backward hook on the pair or its container", relu, sigmoid)
+                        for relu, sigmoid, gelu in sorted({(type(pr[1]) is nn.ReLU, type(pr[1]) is nn.Sigmoid, type(pr[1]) is nn.GELU)
+                                                           for pr in pairs.values()}):
+                            self._refuse("a forward, pre-forward or backward hook on the pair or its container", relu, sigmoid, gelu)
                         if _user_hooked(seq):
                             continue
                         pairs = {}                # (a hooked pair keeps the stock modules; the bare layers of the container stay)

@@ -921,7 +921,8 @@ class RKSweep(object):
         of the same pairs as one launch each (pn_linear_bwd); it lives in the pair's Function, so it has no effect without the forward.
         -pn_linear_bare 0|1 (default 0): func's bare nn.Linear layers through pn_linear_fwd with the identity and pn_linear_dx.
         -pn_linear_relu 0|1 (default 0; anything else is refused): func's Linear -> ReLU pairs as the Tanh ones.
-        -pn_linear_sigmoid 0|1 (default 0; anything else is refused): func's Linear -> Sigmoid pairs as the Tanh ones."""
+        -pn_linear_sigmoid 0|1 (default 0; anything else is refused): func's Linear -> Sigmoid pairs as the Tanh ones.
+        -pn_linear_gelu 0|1 (default 0; anything else is refused): func's Linear -> GELU pairs, which save their pre-activation."""
         mode = str(options.get_all().get("pn_linear_fwd", "auto"))
         mode = "auto" if mode == "auto" else ("1" if options.truthy(mode, False) else "0")
         bwd = str(options.get_all().get("pn_linear_bwd", "auto"))
@@ -937,20 +938,24 @@ class RKSweep(object):
         sigmoid = str(options.get_all().get("pn_linear_sigmoid", "0"))
         if sigmoid not in ("0", "1"):
             raise PnError("-pn_linear_sigmoid must be 0 or 1 (got '%s')" % sigmoid)
+        # -pn_linear_gelu 0|1 (default 0): func's nn.Linear -> nn.GELU pairs through pn_linear_fwd_pre / pn_linear_fwd with PN_ACT_GELU and pn_linear_bwd_act
+        gelu = str(options.get_all().get("pn_linear_gelu", "0"))
+        if gelu not in ("0", "1"):
+            raise PnError("-pn_linear_gelu must be 0 or 1 (got '%s')" % gelu)
         form = options.linear_form()
         if hasattr(self._ops, "linear_flags"):
             self._ops.linear_flags = _lib.PN_LINEAR_FORM_PLAIN if form == "plain" else 0
         from ._linearfwd import LinearFwd
         on = mode != "0" and self._stepper_kind in (None, "imex") and self.device.type == LinearFwd.device_type \
             and self.tensor_dtype == torch.float32 and hasattr(self._ops, "linear_fwd")
-        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form, bare, relu, sigmoid)
+        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form, bare, relu, sigmoid, gelu)
         if sig == self._fwd_sig:
             return
         self._fwd_sig = sig
         self._fwd = None
         if on and self._paramsE:
             fwd = LinearFwd(self)
-            if fwd.install(self.funcEX, self._paramsE, mode, bwd, bare, relu, sigmoid):
+            if fwd.install(self.funcEX, self._paramsE, mode, bwd, bare, relu, sigmoid, gelu):
                 self._fwd = fwd
 
     @property
@@ -1001,6 +1006,16 @@ class RKSweep(object):
             return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" \
                 if str(options.get_all().get("pn_linear_sigmoid", "0")) == "1" else "off (-pn_linear_sigmoid 0)"
         return fwd.sigmoid_status
+
+    @property
+    def linear_gelu(self):
+        """How func's nn.Linear -> nn.GELU pairs run in the solver's evaluations: "off (-pn_linear_gelu 0)", "fused (N pairs; F forward, R
+        backward calls so far)" or "stock modules (why)"."""
+        fwd = self._fwd
+        if fwd is None:
+            return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" \
+                if str(options.get_all().get("pn_linear_gelu", "0")) == "1" else "off (-pn_linear_gelu 0)"
+        return fwd.gelu_status
 
     def _flush_param_accum(self):
         self._flush_bias_accum()

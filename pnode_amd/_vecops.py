@@ -228,19 +228,35 @@ class HipVecOps(object):
 
     linear_relu = True         # linear_fwd and linear_bwd take act="relu" (PN_ACT_RELU; -pn_linear_relu 1)
     linear_sigmoid = True      # ... and act="sigmoid" (PN_ACT_SIGMOID; -pn_linear_sigmoid 1)
+    # linear_act_fwd and linear_bwd take act="gelu" (PN_ACT_GELU; -pn_linear_gelu 1), linear_act_fwd a second output z (pn_linear_fwd_pre).
+    # linear_fwd keeps refusing the name: its callers save the pair's OUTPUT, and GELU's backward needs the pre-activation
+    linear_gelu = True
     _ACTS = {"identity": _lib.PN_ACT_IDENTITY, "tanh": _lib.PN_ACT_TANH, "relu": _lib.PN_ACT_RELU, "sigmoid": _lib.PN_ACT_SIGMOID}
+    _ACTS_PRE = dict(_ACTS, gelu=_lib.PN_ACT_GELU)
 
     def linear_fwd(self, x, w, b, tanh, y=None, flags=None, act=None):
         """y = act(x w^T + b), act = tanh or the identity; x (rows, in_f), w (out_f, in_f), b (out_f,) or None: contiguous fp32 on this device.
         Refused (PnError), never run another way, outside pn_linear_fwd_supported and where y shares memory with x, w or b.  flags: pn_linear_fwd_form's (default: linear_flags).
         act: None -- `tanh` says which of the two --, or "identity", "tanh", "relu", "sigmoid" by name (`tanh` is then not looked at);
-        "relu" gives relu of what the identity gives, value for value; "sigmoid" 1 / (1 + expf(-z)) of it, within 2.5 * 2^-24 of sigma."""
+        "relu" gives relu of what the identity gives, value for value; "sigmoid" 1 / (1 + expf(-z)) of it, within 2.5 * 2^-24 of sigma.
+        ("gelu" is linear_act_fwd's.)"""
         if act is not None and act not in self._ACTS:
-            raise PnError("pn_linear_fwd: act %r: identity, tanh or relu or sigmoid" % (act,))
-        code = self._ACTS[act] if act is not None else (_lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY)
+            raise PnError("pn_linear_fwd: act %r: identity, tanh or relu or sigmoid (gelu, and the pre-activation beside y: linear_act_fwd)" % (act,))
+        return self._linear_fwd(self._ACTS[act] if act is not None else (_lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY), x, w, b, y, None, flags)
+
+    def linear_act_fwd(self, x, w, b, act, y=None, z=None, flags=None):
+        """linear_fwd with the activation by name only, "gelu" among the names (PN_ACT_GELU: the exact GELU of what the identity gives,
+        0.5 z (1 + erff(z / sqrt 2))), and a second output.  z: None -- y alone, pn_linear_fwd_form --, or a (rows, out_f) tensor that
+        receives the pre-activation x w^T + b beside y (pn_linear_fwd_pre; any act): the bits of what "identity" gives, and y the bits
+        it has without z.  Returns y."""
+        if act not in self._ACTS_PRE:
+            raise PnError("pn_linear_fwd_pre: act %r: identity, tanh or relu or sigmoid or gelu" % (act,))
+        return self._linear_fwd(self._ACTS_PRE[act], x, w, b, y, z, flags)
+
+    def _linear_fwd(self, code, x, w, b, y, z, flags):
         rows, in_f = x.shape
         out_f = w.shape[0]
-        for v in (x, w, b, y):
+        for v in (x, w, b, y, z):
             if v is not None and not (v.is_contiguous() and v.dtype == torch.float32 and v.device == x.device and x.is_cuda):
                 raise PnError("pn_linear_fwd: contiguous fp32 tensors on one HIP device")
         if w.shape[1] != in_f or (b is not None and b.numel() != out_f):
@@ -249,6 +265,13 @@ class HipVecOps(object):
             y = torch.empty((rows, out_f), dtype=x.dtype, device=x.device)
         elif tuple(y.shape) != (rows, out_f):
             raise PnError("pn_linear_fwd: y (rows, out_f)")
+        if z is not None:
+            if tuple(z.shape) != (rows, out_f):
+                raise PnError("pn_linear_fwd: z (rows, out_f)")
+            check(self.lib.pn_linear_fwd_pre(self.stream(), _lib.dtype_code(x.dtype), rows, out_f, in_f, x.data_ptr(), w.data_ptr(),
+                                             None if b is None else b.data_ptr(), code, y.data_ptr(), z.data_ptr(),
+                                             self.linear_flags if flags is None else flags))
+            return y
         check(self.lib.pn_linear_fwd_form(self.stream(), _lib.dtype_code(x.dtype), rows, out_f, in_f, x.data_ptr(), w.data_ptr(),
                                           None if b is None else b.data_ptr(), code, y.data_ptr(),
                                           self.linear_flags if flags is None else flags))
@@ -263,9 +286,10 @@ class HipVecOps(object):
         run another way, outside pn_linear_bwd_supported, for an fp64 state, and where gz or dx shares memory with an input.
         flags: pn_linear_bwd_form's (default: linear_flags).  act="relu" (pn_linear_bwd_act): gz = threshold_backward(g, a, 0) bit for bit,
         dx the bits of linear_dx(gz, w).  act="sigmoid" (pn_linear_bwd_act): gz = g fmaf(-a, a, a), two roundings, the same bits in every
-        form; dx the bits of linear_dx(gz, w)."""
-        if act not in ("tanh", "relu", "sigmoid"):
-            raise PnError("pn_linear_bwd: act %r: tanh or relu or sigmoid (no activation: linear_dx)" % (act,))
+        form; dx the bits of linear_dx(gz, w).  act="gelu" (pn_linear_bwd_act): `a` is the pair's PRE-activation z; gz = g (cdf + z pdf),
+        aten.gelu_backward's formula, the same bits in every form; dx the bits of linear_dx(gz, w)."""
+        if act not in ("tanh", "relu", "sigmoid", "gelu"):
+            raise PnError("pn_linear_bwd: act %r: tanh or relu or sigmoid or gelu (no activation: linear_dx)" % (act,))
         rows, out_f = g.shape
         in_f = w.shape[1]
         for v in (g, a, w, gz, dx):
@@ -283,7 +307,7 @@ class HipVecOps(object):
             raise PnError("pn_linear_bwd: dx (rows, in_f)")
         flags = self.linear_flags if flags is None else flags
         if act != "tanh":
-            check(self.lib.pn_linear_bwd_act(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), self._ACTS[act],
+            check(self.lib.pn_linear_bwd_act(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), self._ACTS_PRE[act],
                                              gz.data_ptr(), dx.data_ptr(), flags))
         else:
             check(self.lib.pn_linear_bwd_form(self.stream(), self.code, rows, out_f, in_f, g.data_ptr(), a.data_ptr(), w.data_ptr(), gz.data_ptr(),

@@ -771,8 +771,18 @@ constexpr int FM = 64, FN = 128, FK = 32, kFwdThreads = 512;
 struct FwdArgs {
   const float *x, *w, *b;
   float *y;
+  float *z;                      // the pre-activation beside y (pn_linear_fwd_pre), or null
   int rows, out_f, in_f, act, ntn;
 };
+
+// Exact GELU of the biased sum, y = z Phi(z): the one spelling of all three forms.  Contraction is off, so the three products and the add
+// stay what they are wherever this is inlined: the same bits of y in every form.  erff is the device library's: exactly +-1 from |z| of
+// about 5.6 on, so y is z itself (0.5 z * 2) above and -0 below (0.5 z * 0, z negative); 1 + erff cancels for negative z -- the error is
+// small in absolute terms, large relative to y there; a NaN goes through.
+__device__ __forceinline__ float gelu_y(const float z) {
+#pragma clang fp contract(off)
+  return 0.5f * z * (1.f + erff(z * 0.70710678f));
+}
 
 struct FwdLoads {                // one slab's global loads of a thread
   f32x4 x, w0, w1;
@@ -890,14 +900,27 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
   const bool relu_act = a.act == PN_ACT_RELU;
   // the Sigmoid epilogue is a loop of its own behind ONE uniform branch: inside the loop of the other three, its sixteen expf and
   // divisions cost the tanh pairs 0.2 us per launch (the headline, option absent: -0.68 % over five interleaved runs)
-  auto finish = [&](auto sigmoid_c) {
-    constexpr bool SIGMOID = decltype(sigmoid_c)::value;
+  // The GELU epilogue (gelu_y) is a loop of its own in the same way, and so is every epilogue that also stores the pre-activation
+  // (a.z, pn_linear_fwd_pre): the loops of a launch without z are what they were before there was one -- one more uniform branch in
+  // front of them.  With z: the biased sum goes to z at y's tile positions under y's guards, one more 4-byte store per element; the
+  // GELU pairs -- the ones that save z -- have that loop to themselves, every other act shares one that tests act per element.
+  auto finish = [&](auto sigmoid_c, auto gelu_c, auto pre_c) {
+    constexpr bool SIGMOID = decltype(sigmoid_c)::value, GELU = decltype(gelu_c)::value, PRE = decltype(pre_c)::value;
+    const bool sigmoid_act = a.act == PN_ACT_SIGMOID;               // (looked at by the shared loop with z only)
+    float *zp = PRE ? a.z + (size_t)row0 * out_f + col : nullptr;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const float other = red[(w ^ 4) * 16 + e][lane];
       const float first = kh == 0 ? acc0[e] : other, second = kh == 0 ? other : acc1[e];
       float z = (first + second) + bias;
-      if constexpr (SIGMOID) {
+      const float pre = z;
+      if constexpr (GELU) {
+        z = gelu_y(z);
+      } else if constexpr (PRE) {
+        if (sigmoid_act) z = 1.f / (1.f + expf(-z));                // (the Sigmoid loop's expression)
+        if (tanh_act) z = tanhf(z);
+        if (relu_act) z = z > 0.f ? z : (z == z ? 0.f : z);
+      } else if constexpr (SIGMOID) {
         // the logistic function of the identity's value: expf within 1 ulp, one rounded add, one correctly rounded division (2.5 ulp of
         // 2^-24 in all, never above 1).  expf(-z) overflows to +inf from z <= -88.8 on: 1 / inf is +0; it is below 2^-25 from z >= 17.4
         // on: 1 / 1 is 1; a NaN goes through all three
@@ -908,13 +931,25 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
         if (relu_act) z = z > 0.f ? z : (z == z ? 0.f : z);
       }
       const int r = (e & 3) + 8 * (e >> 2);
-      if (colok && (!RAGGED || row0 + r < rows)) yp[(size_t)r * out_f] = z;
+      if (colok && (!RAGGED || row0 + r < rows)) {
+        yp[(size_t)r * out_f] = z;
+        if constexpr (PRE) zp[(size_t)r * out_f] = pre;
+      }
     }
   };
-  if (a.act == PN_ACT_SIGMOID)
-    finish(std::true_type{});
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (a.z != nullptr) {
+    if (a.act == PN_ACT_GELU)
+      finish(no, yes, yes);
+    else
+      finish(no, no, yes);
+  } else if (a.act == PN_ACT_GELU)
+    finish(no, yes, no);
+  else if (a.act == PN_ACT_SIGMOID)
+    finish(yes, no, no);
   else
-    finish(std::false_type{});
+    finish(no, no, no);
 }
 
 // (pipelined: two sets of fragment and of load registers -- two waves per SIMD, as the LDS allows anyway)
@@ -969,11 +1004,31 @@ __device__ __forceinline__ f32x4 sigmoid_gz(const f32x4 g, const f32x4 a) {
   return z;
 }
 
+// PN_ACT_GELU (pn_linear_bwd_act): the operand called a holds the pair's PRE-activation z (GELU is not monotonic: z cannot be had from
+// the output), and
+//   gz[r][k] = g[r][k] d,   d = cdf + z pdf,   cdf = 0.5 (1 + erff(z 0.70710678)),   pdf = expf(-0.5 z z) 0.3989423
+// -- aten.gelu_backward's formula (approximate='none') by gelu_gz below, the one spelling of all three forms, contraction off: the same
+// bits of gz in each, and dx is what the bare body gives when fed it.  d is 1 from z = 6 on (gz == g); from -6 down cdf is 0 and d = z pdf,
+// below 4e-8 in size and an exact -0 once expf underflows (z below -14.4); a NaN in z or g stays in its element; g = +-inf where d is 0: NaN.
+__device__ __forceinline__ f32x4 gelu_gz(const f32x4 g, const f32x4 zin) {
+#pragma clang fp contract(off)
+  f32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float z = zin[e];
+    const float cdf = 0.5f * (1.f + erff(z * 0.70710678f));
+    const float pdf = expf(-0.5f * z * z) * 0.3989423f;
+    r[e] = g[e] * (cdf + z * pdf);
+  }
+  return r;
+}
+
 template <bool RAGGED, bool PIPE, int ACT = PN_ACT_TANH>
 __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   static_assert(!(RAGGED && PIPE), "the pipelined loop loads without tests");
-  static_assert(ACT == PN_ACT_TANH || ACT == PN_ACT_IDENTITY || ACT == PN_ACT_RELU || ACT == PN_ACT_SIGMOID, "tanh, none, ReLU or sigmoid");
-  constexpr bool BARE = ACT == PN_ACT_IDENTITY, RELU = ACT == PN_ACT_RELU, SIGMOID = ACT == PN_ACT_SIGMOID;
+  static_assert(ACT == PN_ACT_TANH || ACT == PN_ACT_IDENTITY || ACT == PN_ACT_RELU || ACT == PN_ACT_SIGMOID || ACT == PN_ACT_GELU,
+                "tanh, none, ReLU, sigmoid or GELU");
+  constexpr bool BARE = ACT == PN_ACT_IDENTITY, RELU = ACT == PN_ACT_RELU, SIGMOID = ACT == PN_ACT_SIGMOID, GELU = ACT == PN_ACT_GELU;
   constexpr int AROWB = 2 * FK, APART = FM * AROWB;              // gz: [64 rows][32 bf16], 4 KB per part
   constexpr int WROWB = 128, WIMG = FK * WROWB, WPART = 2 * WIMG;      // W: two [32 k][64 bf16] images, 8 KB per part
   constexpr int BUF = 3 * APART + 3 * WPART;                     // 36 KB
@@ -1025,6 +1080,9 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
       if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
     } else if constexpr (SIGMOID) {
       z = sigmoid_gz(gv, av);
+      if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
+    } else if constexpr (GELU) {
+      z = gelu_gz(gv, av);
       if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
     } else if constexpr (!BARE) {
 #pragma unroll
@@ -1089,6 +1147,8 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
               for (int e = 0; e < 4; ++e) z[e] = l.a[e] <= 0.f ? 0.f : l.g[e];
             } else if constexpr (SIGMOID) {
               z = sigmoid_gz(l.g, l.a);
+            } else if constexpr (GELU) {
+              z = gelu_gz(l.g, l.a);
             } else if constexpr (!BARE) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -1158,6 +1218,10 @@ __global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_relu_kernel_f32x
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_sigmoid_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_SIGMOID>(a); }
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_sigmoid_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_SIGMOID>(a); }
 __global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_sigmoid_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_SIGMOID>(a); }
+// the GELU pairs' (pn_linear_bwd_act with PN_ACT_GELU; a of BwdArgs is the pre-activation): the same
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_gelu_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_GELU>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_gelu_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_GELU>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_gelu_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_GELU>(a); }
 
 int cu_count() {
   static int n = 0;             // (the calling thread's current device; every device of a node is the same part)
@@ -1191,7 +1255,7 @@ int finish_t(hipStream_t st, int64_t out_f, int64_t in_f, void *pw, void *pb, vo
 }
 
 // what pn_linear_bwd_form and pn_linear_bwd_act share behind their own checks of `flags` (and of `act`): the shape rules, the null,
-// alignment and aliasing refusals, the choice of the form; act is PN_ACT_TANH, PN_ACT_RELU or PN_ACT_SIGMOID
+// alignment and aliasing refusals, the choice of the form; act is PN_ACT_TANH, PN_ACT_RELU, PN_ACT_SIGMOID or PN_ACT_GELU
 int bwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
              void *gz, void *dx, int flags) {
   if (!pn_linear_bwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_bwd: unsupported dtype or shape (see pn_linear_bwd_supported)");
@@ -1220,8 +1284,41 @@ int bwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f,
                        : (plain ? pn_linear_bwd_sigmoid_kernel_f32x3 : pn_linear_bwd_sigmoid_kernel_f32x3_pipe);
     return pn::launch("pn_linear_bwd_act", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
   }
+  if (act == PN_ACT_GELU) {
+    auto kern = ragged ? pn_linear_bwd_gelu_kernel_f32x3_ragged : (plain ? pn_linear_bwd_gelu_kernel_f32x3 : pn_linear_bwd_gelu_kernel_f32x3_pipe);
+    return pn::launch("pn_linear_bwd_act", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
+  }
   auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : (plain ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
   return pn::launch("pn_linear_bwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
+}
+
+// what pn_linear_fwd_form and pn_linear_fwd_pre share behind their own checks of `flags` (and of a null z): z is the second output or null
+int fwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
+             void *y, void *z, int flags) {
+  if (!pn_linear_fwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_fwd: unsupported dtype or shape (see pn_linear_fwd_supported)");
+  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID && act != PN_ACT_GELU)
+    return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY, PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID or PN_ACT_GELU");
+  if (x == nullptr || w == nullptr || y == nullptr) return pn::fail("pn_linear_fwd: null operand");
+  if (!pn::aligned16(x, w, y) || (reinterpret_cast<uintptr_t>(b) & 3)) return pn::fail("pn_linear_fwd: operands must be 16-byte aligned");
+  // an output that shares bytes with anything the launch reads: other workgroups still read x, w and b while a tile of y is stored
+  const size_t ny = (size_t)rows * (size_t)out_f * sizeof(float), nx = (size_t)rows * (size_t)in_f * sizeof(float),
+               nw = (size_t)out_f * (size_t)in_f * sizeof(float), nb = (size_t)out_f * sizeof(float);
+  if (overlap(y, ny, x, nx) || overlap(y, ny, w, nw) || overlap(y, ny, b, nb))
+    return pn::fail("pn_linear_fwd: y must not alias x, w or b (other workgroups still read them)");
+  if (z != nullptr) {              // (pn_linear_fwd_pre) the second output: y's size, y's rules, and no byte of y
+    if (!pn::aligned16(z)) return pn::fail("pn_linear_fwd_pre: z must be 16-byte aligned");
+    if (overlap(z, ny, y, ny) || overlap(z, ny, x, nx) || overlap(z, ny, w, nw) || overlap(z, ny, b, nb))
+      return pn::fail("pn_linear_fwd_pre: z must not alias y, x, w or b");
+  }
+  FwdArgs a;
+  a.x = (const float *)x, a.w = (const float *)w, a.b = (const float *)b, a.y = (float *)y, a.z = (float *)z;
+  a.rows = (int)rows, a.out_f = (int)out_f, a.in_f = (int)in_f, a.act = act;
+  a.ntn = (int)((out_f + FN - 1) / FN);
+  const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)a.ntn;
+  const bool ragged = rows % FM != 0 || out_f % FN != 0;
+  const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (in_f / FK) % 2 != 0;       // (the pipelined loop takes an even number of slabs)
+  auto kern = ragged ? pn_linear_fwd_kernel_f32x3_ragged : (plain ? pn_linear_fwd_kernel_f32x3 : pn_linear_fwd_kernel_f32x3_pipe);
+  return pn::launch("pn_linear_fwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, a);
 }
 
 }  // namespace
@@ -1319,27 +1416,15 @@ int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t 
 int pn_linear_fwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b,
                        int act, void *y, int flags) {
   if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_fwd_form: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
-  if (!pn_linear_fwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_fwd: unsupported dtype or shape (see pn_linear_fwd_supported)");
-  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID)
-    return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY, PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID");
-  if (x == nullptr || w == nullptr || y == nullptr) return pn::fail("pn_linear_fwd: null operand");
-  if (!pn::aligned16(x, w, y) || (reinterpret_cast<uintptr_t>(b) & 3)) return pn::fail("pn_linear_fwd: operands must be 16-byte aligned");
-  // an output that shares bytes with anything the launch reads: other workgroups still read x, w and b while a tile of y is stored
-  const size_t ny = (size_t)rows * (size_t)out_f * sizeof(float), nx = (size_t)rows * (size_t)in_f * sizeof(float),
-               nw = (size_t)out_f * (size_t)in_f * sizeof(float), nb = (size_t)out_f * sizeof(float);
-  if (overlap(y, ny, x, nx) || overlap(y, ny, w, nw) || overlap(y, ny, b, nb))
-    return pn::fail("pn_linear_fwd: y must not alias x, w or b (other workgroups still read them)");
-  FwdArgs a;
-  a.x = (const float *)x, a.w = (const float *)w, a.b = (const float *)b, a.y = (float *)y;
-  a.rows = (int)rows, a.out_f = (int)out_f, a.in_f = (int)in_f, a.act = act;
-  a.ntn = (int)((out_f + FN - 1) / FN);
-  const unsigned blocks = (unsigned)((rows + FM - 1) / FM) * (unsigned)a.ntn;
-  const bool ragged = rows % FM != 0 || out_f % FN != 0;
-  const bool plain = (flags & PN_LINEAR_FORM_PLAIN) || (in_f / FK) % 2 != 0;       // (the pipelined loop takes an even number of slabs)
-  auto kern = ragged ? pn_linear_fwd_kernel_f32x3_ragged : (plain ? pn_linear_fwd_kernel_f32x3 : pn_linear_fwd_kernel_f32x3_pipe);
-  return pn::launch("pn_linear_fwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, a);
+  return fwd_pair(stream, dtype, rows, out_f, in_f, x, w, b, act, y, nullptr, flags);
 }
 
+int pn_linear_fwd_pre(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
+                      void *y, void *z, int flags) {
+  if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_fwd_pre: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
+  if (z == nullptr) return pn::fail("pn_linear_fwd_pre: z is null (y alone: pn_linear_fwd_form)");
+  return fwd_pair(stream, dtype, rows, out_f, in_f, x, w, b, act, y, z, flags);
+}
 int pn_linear_bwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f) {
   if (dtype != PN_F32) return 0;
   const int64_t lim = (int64_t)1 << 30;
@@ -1363,8 +1448,8 @@ int pn_linear_bwd_act(void *stream, int dtype, int64_t rows, int64_t out_f, int6
                       void *gz, void *dx, int flags) {
   if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_bwd_act: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
   if (act == PN_ACT_IDENTITY) return pn::fail("pn_linear_bwd_act: PN_ACT_IDENTITY has no prologue and no gz: use pn_linear_dx");
-  if (act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID)
-    return pn::fail("pn_linear_bwd_act: act is PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID (PN_ACT_IDENTITY: use pn_linear_dx)");
+  if (act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID && act != PN_ACT_GELU)
+    return pn::fail("pn_linear_bwd_act: act is PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID or PN_ACT_GELU (PN_ACT_IDENTITY: use pn_linear_dx)");
   return bwd_pair(stream, dtype, rows, out_f, in_f, g, a, w, act, gz, dx, flags);
 }
 

@@ -33,6 +33,12 @@ types): ``0``, the default, leaves such a Linear a stock module, or a bare layer
 ``pn_linear_fwd`` launch with ``PN_ACT_SIGMOID`` (``1 / (1 + expf(-z))``, within 2.5 * 2^-24 of sigma: not ``torch.sigmoid``'s bits) and
 its backward -- ``g_z = g a (1 - a)``, ``dx = g_z W`` -- as one ``pn_linear_bwd_act`` launch (``-pn_linear_bwd 0`` keeps
 ``sigmoid_backward`` and ``matmul``).  ``ode.linear_sigmoid`` reports what runs.  ``-pn_linear_fwd 0`` switches this off too.
+``-pn_linear_gelu 0|1`` (read there too; anything else is refused): the same for the ``nn.Linear -> nn.GELU`` pairs (exactly those types,
+``approximate='none'``): ``0``, the default, leaves such a Linear a stock module, or a bare layer under ``-pn_linear_bare 1``; ``1`` runs
+the pair as one launch that writes the pre-activation ``z`` beside ``y`` where the evaluation will be differentiated
+(``pn_linear_fwd_pre``; ``z`` is what the pair saves) and ``y`` alone elsewhere (``pn_linear_fwd`` with ``PN_ACT_GELU``), and its backward
+-- ``g_z = g (cdf + z pdf)``, ``dx = g_z W`` -- as one ``pn_linear_bwd_act`` launch reading ``z`` (``-pn_linear_bwd 0`` keeps
+``gelu_backward`` and ``matmul``).  ``ode.linear_gelu`` reports what runs.  ``-pn_linear_fwd 0`` switches this off too.
 """
 import os
 import shlex
