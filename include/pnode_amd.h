@@ -236,8 +236,14 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
  * PN_ACT_GELU (exact GELU, approximate='none': y = 0.5f * z * (1.f + erff(z * 0.70710678f)) of the biased sum z in fp32, never contracted,
  * spelled once: the same bits of y in every form.  erff is the device library's, whose bound this file does not know: the error is
  * MEASURED, see pn_linear_fwd_pre below; y is exactly z from z >= 6 on and exactly -0 from z <= -6 on, NaN for NaN; not F.gelu's bits.
- * y alone is for evaluations nobody differentiates: GELU's derivative needs z, which pn_linear_fwd_pre writes beside y); any other
- * act -- 3, 5 and 7 too, which name nothing -- is refused, nothing launched.  The product is the split-bf16 one of pn_linear_wgrad
+ * y alone is for evaluations nobody differentiates: GELU's derivative needs z, which pn_linear_fwd_pre writes beside y) or
+ * PN_ACT_SOFTPLUS (nn.Softplus at beta 1, threshold 20, aten's formula: y = z > 20.f ? z : log1pf(expf(z)) of the biased sum z in fp32;
+ * y == z above the threshold, an exact +0 once expf underflows (z <= -104), NaN for NaN) or PN_ACT_ELU (nn.ELU at alpha 1:
+ * y = z > 0.f ? z : expm1f(z); z's bits where z > 0, -0 for -0, exactly -1 from z of about -17.4 down, NaN for NaN).  log1pf and expm1f
+ * are the device library's, which states no bound: the error of both is MEASURED against float64 on the kernel's own z
+ * (profiles/linear_softplus_elu.txt, tests/test_gpu_linear_softplus_elu.py) and held to the figure of F.softplus / F.elu on the same z
+ * plus one unit of 2^-24, at most 4 * 2^-24 relative to y.  Both are spelled once: the same bits of y in every form; any other
+ * act -- 3, 5, 6, 7, 9 ... 15, 17 ... too, which name nothing -- is refused, nothing launched.  The product is the split-bf16 one of pn_linear_wgrad
  * (three exact bf16 terms per operand, the six largest cross products, fp32 accumulation on v_mfma_f32_32x32x16_bf16; an infinite
  * operand gives NaN); one workgroup owns a 64 x 128 tile of y over all of in_f and writes it once: no atomics, no work buffers, the
  * same bits on every launch.  x, w, y non-NULL and 16-byte aligned, b 4-byte aligned; y shares no byte with x, w or b (other workgroups
@@ -250,6 +256,8 @@ int pn_linear_wgrad_finish(void *stream, int dtype, int64_t out_f, int64_t in_f,
 #define PN_ACT_RELU 2
 #define PN_ACT_SIGMOID 4 /* (3 names nothing and is refused) */
 #define PN_ACT_GELU 8    /* (5 and 7 name nothing and are refused) */
+#define PN_ACT_SOFTPLUS 16 /* beta 1, threshold 20 (6, 9 ... 15 name nothing and are refused) */
+#define PN_ACT_ELU 32      /* alpha 1 (17 ... 31, 33 ... name nothing and are refused: the values are names, not bits to combine) */
 int pn_linear_fwd_supported(int dtype, int64_t rows, int64_t out_f, int64_t in_f);
 int pn_linear_fwd(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
                   void *y);
@@ -319,6 +327,18 @@ int pn_linear_bwd_form(void *stream, int dtype, int64_t rows, int64_t out_f, int
  * from z >= 6 on (gz == g); from z <= -6 down cdf is 0 and d = z pdf, below 4e-8 in size, an exact -0 once expf underflows; a NaN in a or g stays in its own element of gz and its own row of dx; g = +-inf
  * where d is 0 gives NaN, as in aten.gelu_backward.  dx has the bits of pn_linear_dx fed that gz, in every form.  Replaces the
  * gelu_backward kernel and the library GEMM of the pair.
+ * act == PN_ACT_SOFTPLUS is the backward of an nn.Linear -> nn.Softplus pair (beta 1, threshold 20), a its output:
+ *   gz[r][k] = g[r][k] * (-expm1f(-a[r][k]))      dx[r][n] = sum_k gz[r][k] w[k][n]
+ * -- 1 - e^(-a) is sigma(z) written in the output: no cancellation for any a >= 0, exactly 1 from a of about 17.4 on (gz == g bit for bit
+ * from a >= 18), +-0 at a == 0; ONE rounded product, never contracted, spelled once: the same bits of gz in every form.  The error of
+ * expm1f is measured (profiles/linear_softplus_elu.txt): |gz - g (1 - e^(-a))| is held to the figure of g * (-torch.expm1(-a)) plus
+ * one unit of 2^-24 |g|, at most 4 * 2^-24 |g|.
+ * act == PN_ACT_ELU is the backward of an nn.Linear -> nn.ELU pair (alpha 1), a its output:
+ *   gz[r][k] = a[r][k] > 0 ? g[r][k] : g[r][k] * (a[r][k] + 1.f)
+ * -- aten.elu_backward on the result: g's bits where a > 0, else one rounded add and ONE rounded product (within 1.5 * 2^-24 |g| of
+ * g (a + 1)), never contracted; the comparison is a > 0, so a NaN in a gives a NaN in gz.  For both: a NaN or +-inf in g stays in its
+ * own element of gz and its own row of dx; dx has the bits of pn_linear_dx fed that gz, in every form.  They replace the elementwise
+ * backward kernel and the library GEMM of the pair.
  * PN_ACT_IDENTITY is refused (no prologue, no gz: use pn_linear_dx); so is any other value, and an unknown flag; nothing is launched. */
 int pn_linear_bwd_act(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
                       void *gz, void *dx, int flags);

@@ -48,6 +48,8 @@ PN_WGRAD_TILE_64 = 2
 PN_ACT_IDENTITY, PN_ACT_TANH, PN_ACT_RELU = 0, 1, 2
 PN_ACT_SIGMOID = 4            # (3 names nothing: refused)
 PN_ACT_GELU = 8               # (5 and 7 name nothing: refused)
+PN_ACT_SOFTPLUS = 16          # nn.Softplus at beta 1, threshold 20 (6, 9 ... 15 name nothing: refused)
+PN_ACT_ELU = 32               # nn.ELU at alpha 1 (17 ... 31, 33 ... name nothing: refused)
 PN_LINEAR_FORM_PLAIN = 1      # pn_linear_fwd_form / pn_linear_bwd_form flag: the plain K loop on an aligned shape too
 PN_ABI_VERSION = 4
 PN_DENSE_MAX_POW = 4          # columns of a continuous extension's P matrix (pn_tableau_dense)

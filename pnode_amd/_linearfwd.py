@@ -75,7 +75,21 @@ Self-checks as the Sigmoid pairs': the forward against ``F.gelu(F.linear)`` to `
 at ``z = 0``: rows of scale 0 must have a bar above 0), ``z`` against ``F.linear`` in the bare layer's measure; ``g_z`` to ``32 * 2^-24 |g|``
 of ``gelu_backward``'s -- absolute in the derivative, which crosses zero near ``z = -0.7518``: two evaluations of ``erff``, each within
 the 16 ulp that OpenCL allows ``erf``, halved in ``cdf`` --; ``dx`` in the pairs' measure.  A miss switches off the GELU pairs, or their
-backward, only."""
+backward, only.
+
+Softplus and ELU pairs (``-pn_linear_softplus 0|1``, ``-pn_linear_elu 0|1``, default ``0``: nothing below happens).  Both derivatives are
+functions of the pair's OUTPUT -- ``1 - e^-a`` and ``a > 0 ? 1 : a + 1`` --, so these are saved-output pairs through ``_LinearTanh``, one
+record each (``LinearFwd.softplus``, ``LinearFwd.elu``) that also names the kernel's ``act``, the torch expressions the pair replaces and
+the bar of ``g_z``: nothing about them is spelled per kind outside ``_KINDS``.  With ``1`` two consecutive children ``nn.Linear``, exactly
+``nn.Softplus`` with ``beta == 1`` and ``threshold == 20`` (exactly ``nn.ELU`` with ``alpha == 1``, either ``inplace``: the module is not
+called) of an eligible container are a pair under the rules of the Sigmoid pairs; a module with other parameters is none -- the C entries
+have no slot for one --, its reason in ``refused`` under ``(class name, "Softplus")`` / ``(class name, "ELU")`` and in the status.  Forward
+``pn_linear_fwd`` with ``PN_ACT_SOFTPLUS`` / ``PN_ACT_ELU``; backward one ``pn_linear_bwd_act`` launch on a backend with
+``linear_softplus`` / ``linear_elu``, else ``g * (-expm1(-a))`` / ``aten.elu_backward(g, 1, 1, 1, True, a)`` and ``matmul``.  Self-checks:
+the forward against ``F.softplus(F.linear)`` / ``F.elu(F.linear)`` at the Sigmoid pairs' bar (Softplus maps a zero pre-activation to
+``log 2``: the absolute term again); ``g_z`` against those torch expressions to ``4 * 2^-24 |g|`` (Softplus: the cap on either side's
+``expm1``) and ``1.5 * 2^-24 |g|`` (ELU: one rounded add, one rounded product); ``dx`` in the pairs' measure.  A miss switches off that
+kind, or its backward, only."""
 import contextlib
 import warnings
 import weakref
@@ -116,7 +130,7 @@ def _user_hooked(m):
 
 def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
     """The static half of the eligibility rules for the Linear `lin` (and the activation `act` behind it, exactly a `kind`: nn.Tanh or
-    nn.ReLU or nn.Sigmoid or nn.GELU; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
+    nn.ReLU or nn.Sigmoid or nn.GELU or nn.Softplus or nn.ELU; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
     mods = (lin,) if act is None else (lin, act)
     if type(seq) is not nn.Sequential or "forward" in seq.__dict__:
         return "the container's forward is not nn.Sequential's own"
@@ -137,7 +151,19 @@ def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
     return why
 
 
-def find_layers(func, params, relu=False, sigmoid=False, gelu=False):
+def _softplus_why(act):
+    if act.beta != 1 or act.threshold != 20:
+        return "nn.Softplus(beta=%r, threshold=%r): only beta == 1 and threshold == 20 are owned" % (act.beta, act.threshold)
+    return None
+
+
+def _elu_why(act):
+    if act.alpha != 1.0:
+        return "nn.ELU(alpha=%r): only alpha == 1 is owned" % (act.alpha,)
+    return None
+
+
+def find_layers(func, params, relu=False, sigmoid=False, gelu=False, softplus=False, elu=False):
     """(plans, refused, bare): [(sequential, {index of the Linear child: (linear, tanh)})] of func; {class name of a container: reason}
     for the Linear -> Tanh pairs that cannot be fused (what -pn_linear_fwd 1 warns about); and [(sequential, {index of the child:
     linear})] for the bare layers -- exactly nn.Linear, opening no fused pair, under the same static rules (-pn_linear_bare 1).
@@ -146,7 +172,10 @@ def find_layers(func, params, relu=False, sigmoid=False, gelu=False):
     `refused` under the key (class name of the container, "ReLU").  Without it the three are what they were before there was the option.
     sigmoid (-pn_linear_sigmoid 1): the same for nn.Linear, nn.Sigmoid; the key in `refused` is (class name, "Sigmoid").
     gelu (-pn_linear_gelu 1): the same for nn.Linear, nn.GELU with approximate == 'none'; the key in `refused` is (class name, "GELU"),
-    also for an nn.GELU(approximate='tanh'), whose Linear is then a stock module or a bare layer."""
+    also for an nn.GELU(approximate='tanh'), whose Linear is then a stock module or a bare layer.
+    softplus (-pn_linear_softplus 1), elu (-pn_linear_elu 1): the same for nn.Linear, nn.Softplus with beta == 1 and threshold == 20, and
+    for nn.Linear, nn.ELU with alpha == 1; the keys in `refused` are (class name, "Softplus") and (class name, "ELU"), also for a module
+    with other parameters."""
     plans, refused, bare = [], {}, []
     if not isinstance(func, nn.Module):
         return plans, refused, bare
@@ -175,11 +204,19 @@ def find_layers(func, params, relu=False, sigmoid=False, gelu=False):
                 kind, key = nn.Sigmoid, (type(seq).__name__, "Sigmoid")
             elif gelu and isinstance(act, nn.GELU):
                 kind, key = nn.GELU, (type(seq).__name__, "GELU")
+            elif softplus and isinstance(act, nn.Softplus):
+                kind, key = nn.Softplus, (type(seq).__name__, "Softplus")
+            elif elu and isinstance(act, nn.ELU):
+                kind, key = nn.ELU, (type(seq).__name__, "ELU")
             else:
                 continue
             why = _static_why(seq, kids, lin, act, index, owners, kind)
             if why is None and kind is nn.GELU and getattr(act, "approximate", "none") != "none":
                 why = "nn.GELU(approximate=%r): only the exact GELU (approximate='none') is owned" % (act.approximate,)
+            if why is None and kind is nn.Softplus:
+                why = _softplus_why(act)
+            if why is None and kind is nn.ELU:
+                why = _elu_why(act)
             if why is None:
                 pairs[i] = (lin, act)
             else:
@@ -200,15 +237,18 @@ def find_pairs(func, params):
 
 class _Call(object):
     """What one fused call carries into its backward."""
-    __slots__ = ("owner", "module", "grads", "ev", "version", "relu", "sigmoid", "pre")
+    __slots__ = ("owner", "module", "grads", "ev", "version", "relu", "sigmoid", "pre", "state")
 
 
 class _PairState(object):
     """The state of one further kind of pair beside the tanh and ReLU pairs, whose fields are LinearFwd's own: the map, the option, the
     self-checks' flags and reasons, the counters.  `name` is the activation's class name, `torch_fwd` / `torch_bwd` the expressions the
     pair replaces (in the wording of the warnings)."""
-    def __init__(self, name, option, torch_fwd, torch_bwd):
+    def __init__(self, name, option, torch_fwd, torch_bwd, kind=None, act=None, fwd=None, gz=None, gz_bar=None):
         self.name, self.option, self.torch_fwd, self.torch_bwd = name, option, torch_fwd, torch_bwd
+        # the Softplus and ELU pairs (_KINDS): the module class, the backend's name of the activation, the torch functions behind
+        # `torch_fwd` and `torch_bwd`'s first half -- fwd(z), gz(g, a) --, and the self-check's bar of g_z in units of 2^-24 |g|
+        self.kind, self.act, self.fwd, self.gz, self.gz_bar = kind, act, fwd, gz, gz_bar
         self.plans = []            # [(sequential, {child index: (linear, activation)})]
         self.mode = "0"
         self.disabled = False      # the forward check failed
@@ -247,6 +287,21 @@ class _PairState(object):
             "" if self.refused is None else "; the stock modules where a call is refused, last: " + self.refused)
 
 
+def _softplus_gz(g, a):
+    return g * (-torch.expm1(-a))
+
+
+def _elu_gz(g, a):
+    return torch.ops.aten.elu_backward(g, 1, 1, 1, True, a)
+
+
+def _KINDS():
+    """The records of the saved-output pairs that are told by their record alone (LinearFwd.softplus, LinearFwd.elu), fresh ones."""
+    return (_PairState("Softplus", "-pn_linear_softplus", "F.softplus(F.linear)", "g * (-expm1(-a)) + matmul", nn.Softplus, "softplus",
+                       F.softplus, _softplus_gz, 4.0),
+            _PairState("ELU", "-pn_linear_elu", "F.elu(F.linear)", "elu_backward + matmul", nn.ELU, "elu", F.elu, _elu_gz, 1.5))
+
+
 def _shaped(y2, shape):
     """The kernel's (rows, out_f) result in the shape of the layer's output.  A 2-D input gets the tensor itself: a view made inside a
     Function's forward may not be written in place, and an nn.ReLU(inplace=True) behind a bare layer does just that."""
@@ -255,11 +310,16 @@ def _shaped(y2, shape):
 
 class _LinearTanh(torch.autograd.Function):
     """A Linear -> Tanh pair or, with call.relu (-pn_linear_relu 1), a Linear -> ReLU pair, or, with call.sigmoid (-pn_linear_sigmoid 1), a
-    Linear -> Sigmoid pair: the same structure, the other activation."""
+    Linear -> Sigmoid pair, or, with call.state (a record of _KINDS: -pn_linear_softplus 1, -pn_linear_elu 1), a Linear -> Softplus or
+    Linear -> ELU pair: the same structure, the other activation."""
     @staticmethod
     def forward(ctx, x, w, b, call):
-        kernel = call.owner.kernel_sigmoid if call.sigmoid else (call.owner.kernel_relu if call.relu else call.owner.kernel)
-        a = _shaped(kernel(x.reshape(-1, w.shape[1]), w, b), x.shape[:-1] + (w.shape[0],))
+        if call.state is not None:
+            a2 = call.owner.kernel_act(call.state.act, x.reshape(-1, w.shape[1]), w, b)
+        else:
+            kernel = call.owner.kernel_sigmoid if call.sigmoid else (call.owner.kernel_relu if call.relu else call.owner.kernel)
+            a2 = kernel(x.reshape(-1, w.shape[1]), w, b)
+        a = _shaped(a2, x.shape[:-1] + (w.shape[0],))
         ctx.save_for_backward(x, w, a)
         ctx.call = call
         ctx.has_bias = b is not None
@@ -272,6 +332,8 @@ class _LinearTanh(torch.autograd.Function):
         # both in one launch (pn_linear_bwd, pn_linear_bwd_act) where LinearFwd._bwd_fusable allows it, else the two torch operations
         if not ctx.needs_input_grad[0]:
             fused = None
+        elif call.state is not None:
+            fused = call.owner._backward(g, a, w, st=call.state)
         elif call.sigmoid:
             fused = call.owner._backward(g, a, w, sigmoid=True)
         else:
@@ -279,7 +341,9 @@ class _LinearTanh(torch.autograd.Function):
         if fused is not None:
             g_z, dx = fused
         else:
-            if call.sigmoid:
+            if call.state is not None:
+                g_z = call.state.gz(g, a)
+            elif call.sigmoid:
                 g_z = torch.ops.aten.sigmoid_backward(g, a)
             else:
                 g_z = torch.ops.aten.threshold_backward(g, a, 0) if call.relu else torch.ops.aten.tanh_backward(g, a)
@@ -407,11 +471,14 @@ class LinearFwd(object):
         self.sig = _PairState("Sigmoid", "-pn_linear_sigmoid", "torch.sigmoid(F.linear)", "sigmoid_backward + matmul")
         # the Linear -> GELU pairs (-pn_linear_gelu 0|1): one more record; the pairs that save their pre-activation
         self.gelu = _PairState("GELU", "-pn_linear_gelu", "F.gelu(F.linear)", "gelu_backward + matmul")
+        # the Linear -> Softplus and Linear -> ELU pairs (-pn_linear_softplus 0|1, -pn_linear_elu 0|1): a record each
+        self.softplus, self.elu = self.kinds = _KINDS()
 
-    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0", relu_mode="0", sigmoid_mode="0", gelu_mode="0"):
+    def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0", relu_mode="0", sigmoid_mode="0", gelu_mode="0",
+                softplus_mode="0", elu_mode="0"):
         """Find the eligible pairs of `func` (and, with bare_mode "1", its bare layers; with relu_mode "1", its Linear -> ReLU pairs; with
-        sigmoid_mode "1", its Linear -> Sigmoid pairs; with gelu_mode "1", its Linear -> GELU pairs); returns True when there is at least
-        one."""
+        sigmoid_mode "1", its Linear -> Sigmoid pairs; with gelu_mode "1", its Linear -> GELU pairs; with softplus_mode / elu_mode "1",
+        its Linear -> Softplus / Linear -> ELU pairs); returns True when there is at least one."""
         self.mode = mode
         self.bwd_mode = bwd_mode
         self.bare_mode = bare_mode
@@ -420,19 +487,26 @@ class LinearFwd(object):
         self.sig.refused = None
         self.gelu.mode = gelu_mode
         self.gelu.refused = None
-        found, refused, self.bare = find_layers(func, params, relu_mode == "1", sigmoid=sigmoid_mode == "1", gelu=gelu_mode == "1")
-        self.gelu.static_why = next((why for key, why in refused.items() if isinstance(key, tuple) and key[1] == "GELU"), None)
+        self.softplus.mode, self.elu.mode = softplus_mode, elu_mode
+        found, refused, self.bare = find_layers(func, params, relu_mode == "1", sigmoid=sigmoid_mode == "1", gelu=gelu_mode == "1",
+                                                softplus=softplus_mode == "1", elu=elu_mode == "1")
+        for st in (self.gelu,) + self.kinds:
+            st.static_why = next((why for key, why in refused.items() if isinstance(key, tuple) and key[1] == st.name), None)
         self.plans, self.relu, self.sig.plans, self.gelu.plans = [], [], [], []
+        for st in self.kinds:
+            st.plans, st.refused = [], None
         for seq, pairs in found:
-            for kind, plans in ((nn.Tanh, self.plans), (nn.ReLU, self.relu), (nn.Sigmoid, self.sig.plans), (nn.GELU, self.gelu.plans)):
+            for kind, plans in ((nn.Tanh, self.plans), (nn.ReLU, self.relu), (nn.Sigmoid, self.sig.plans), (nn.GELU, self.gelu.plans)) \
+                    + tuple((st.kind, st.plans) for st in self.kinds):
                 mine = {i: p for i, p in pairs.items() if type(p[1]) is kind}
                 if mine:
                     plans.append((seq, mine))
         if mode == "1" and refused:
             for key, why in refused.items():
                 cls, name = key if isinstance(key, tuple) else (key, "Tanh")
-                if name == "GELU":
-                    if self.gelu.warned:
+                by_name = {st.name: st for st in (self.gelu,) + self.kinds}
+                if name in by_name:
+                    if by_name[name].warned:
                         continue
                 elif self.sig.warned if name == "Sigmoid" else (self._warned_relu if name == "ReLU" else self._warned):
                     continue
@@ -440,8 +514,9 @@ class LinearFwd(object):
             self._warned = self._warned or any(not isinstance(key, tuple) for key in refused)
             self._warned_relu = self._warned_relu or any(isinstance(key, tuple) and key[1] == "ReLU" for key in refused)
             self.sig.warned = self.sig.warned or any(isinstance(key, tuple) and key[1] == "Sigmoid" for key in refused)
-            self.gelu.warned = self.gelu.warned or any(isinstance(key, tuple) and key[1] == "GELU" for key in refused)
-        return bool(self.plans) or self.bare_active or self.relu_active or self.sig.active or self.gelu.active
+            for st in (self.gelu,) + self.kinds:
+                st.warned = st.warned or any(isinstance(key, tuple) and key[1] == st.name for key in refused)
+        return self.active or bool(self.plans)
 
     @property
     def bare_active(self):
@@ -453,7 +528,8 @@ class LinearFwd(object):
 
     @property
     def active(self):
-        return (bool(self.plans) and not self.disabled) or self.bare_active or self.relu_active or self.sig.active or self.gelu.active
+        return (bool(self.plans) and not self.disabled) or self.bare_active or self.relu_active or self.sig.active or self.gelu.active \
+            or any(st.active for st in self.kinds)
 
     # what the Sigmoid pairs' record holds, under the names the tanh and ReLU pairs' fields have
     @property
@@ -493,6 +569,19 @@ class LinearFwd(object):
     def n_gelu_bwd(self):
         return self.gelu.n_bwd
 
+    # ... and the Softplus and ELU pairs' (`softplus` and `elu` are the records themselves)
+    @property
+    def softplus_status(self):
+        return self.softplus.status
+
+    @property
+    def elu_status(self):
+        return self.elu.status
+
+    def _state(self, act):
+        """The record of `act`'s kind where the kind is told by its record alone (Softplus, ELU), else None."""
+        return next((st for st in self.kinds if type(act) is st.kind), None)
+
     # the one place the device is touched: tests of the eligibility rules replace it by the torch expression
     def kernel(self, x2, w, b):
         return self._ode()._ops.linear_fwd(x2, w, b, True)
@@ -505,6 +594,10 @@ class LinearFwd(object):
 
     def kernel_sigmoid(self, x2, w, b):
         return self._ode()._ops.linear_fwd(x2, w, b, False, act="sigmoid")
+
+    def kernel_act(self, act, x2, w, b):
+        """The saved-output pairs named by `act` ("softplus", "elu")."""
+        return self._ode()._ops.linear_fwd(x2, w, b, False, act=act)
 
     def kernel_gelu(self, x2, w, b, pre):
         """(y, z): z the pre-activation from the same launch (pn_linear_fwd_pre) when `pre`, else None and no tensor allocated for it."""
@@ -522,11 +615,12 @@ class LinearFwd(object):
             ok = self._ok[key] = bool(hasattr(ops, "linear_fwd_supported") and ops.linear_fwd_supported(rows, out_f, in_f))
         return ok
 
-    def _refuse(self, why, relu=False, sigmoid=False, gelu=False):
-        if gelu:
-            if self.mode == "1" and not self.gelu.warned:
-                self.gelu.warned = True
-                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> GELU pair runs the stock modules: %s" % why, RuntimeWarning)
+    def _refuse(self, why, relu=False, sigmoid=False, gelu=False, st=None):
+        st = self.gelu if gelu else st
+        if st is not None:
+            if self.mode == "1" and not st.warned:
+                st.warned = True
+                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair runs the stock modules: %s" % (st.name, why), RuntimeWarning)
             return None
         if self.mode == "1" and not (self.sig.warned if sigmoid else (self._warned_relu if relu else self._warned)):
             if sigmoid:
@@ -567,6 +661,30 @@ class LinearFwd(object):
         with torch.no_grad():
             x2 = x.reshape(-1, w.shape[1])
             ref = torch.sigmoid(F.linear(x2, w, b))
+            scale = x2.abs() @ w.abs().t()
+            if b is not None:
+                scale = scale + b.abs()
+            ok = torch.isfinite(ref) & torch.isfinite(scale)
+            if not bool(ok.any()):
+                st.checked = False
+                return True
+            bar = CHECK_TOL * scale + 4.0 * 2.0 ** -24
+            over = ((a.reshape(ref.shape) - ref).abs() / bar)[ok].max()
+        if not float(over) <= 1.0:
+            st.disabled = True
+            st.why = "pn_linear_fwd and %s differ by %.2f times the bar %.0e (sum |x w| + |b|) + 4 * 2^-24" % (st.torch_fwd, float(over), CHECK_TOL)
+            warnings.warn("pnode_amd: the fused Linear -> %s forward is switched off for this solver: %s" % (st.name, st.why), RuntimeWarning)
+            return False
+        return True
+
+    def _check_state(self, st, x, w, b, a):
+        """First fused call of a Softplus or ELU pair of a solver: against st.fwd(F.linear) at the Sigmoid pairs' bar, |y - ref| <=
+        CHECK_TOL (sum |x w| + |b|) + 4 * 2^-24.  The absolute term: Softplus maps a zero pre-activation to log 2, with a rounding of
+        its own on either side; ELU's rows of scale 0 are an exact 0 and need a bar above 0.  A miss switches off that kind only."""
+        st.checked = True
+        with torch.no_grad():
+            x2 = x.reshape(-1, w.shape[1])
+            ref = st.fwd(F.linear(x2, w, b))
             scale = x2.abs() @ w.abs().t()
             if b is not None:
                 scale = scale + b.abs()
@@ -671,14 +789,18 @@ class LinearFwd(object):
     def kernel_bwd_sigmoid(self, g2, a2, w):
         return self._ode()._ops.linear_bwd(g2, a2, w, act="sigmoid")
 
+    def kernel_bwd_act(self, act, g2, a2, w):
+        return self._ode()._ops.linear_bwd(g2, a2, w, act=act)
+
     def kernel_bwd_gelu(self, g2, z2, w):
         return self._ode()._ops.linear_bwd(g2, z2, w, act="gelu")
 
-    def _bwd_fusable(self, g, a, w, relu=False, sigmoid=False, gelu=False):
+    def _bwd_fusable(self, g, a, w, relu=False, sigmoid=False, gelu=False, st=None):
         """None, or the reason (a string) this backward runs the torch operations.  a: the pair's output; None for a bare layer
         (pn_linear_dx: the same rules minus everything about a).  relu: a ReLU pair (pn_linear_bwd_act: the rules of a tanh pair, and
         a backend with `linear_relu`).  sigmoid: a Sigmoid pair (the same, and a backend with `linear_sigmoid`).  gelu: a GELU pair (the same, and a
-        backend with `linear_gelu`; `a` is then the pair's pre-activation)."""
+        backend with `linear_gelu`; `a` is then the pair's pre-activation).  st: a Softplus or ELU pair's record (the same, and a backend with
+        `linear_softplus` / `linear_elu`)."""
         bare = a is None
         entry = "linear_dx" if bare else "linear_bwd"
         ode = self._ode()
@@ -690,9 +812,14 @@ class LinearFwd(object):
             return "the backend has no linear_sigmoid"
         if gelu and not getattr(ode._ops, "linear_gelu", False):
             return "the backend has no linear_gelu"
+        if st is not None and not getattr(ode._ops, "linear_" + st.act, False):
+            return "the backend has no linear_" + st.act
         if self.bwd_mode == "0":
             return "-pn_linear_bwd 0"
-        if gelu:
+        if st is not None:
+            if st.bwd_disabled:
+                return st.bwd_why
+        elif gelu:
             if self.gelu.bwd_disabled:
                 return self.gelu.bwd_why
         elif sigmoid:
@@ -787,6 +914,31 @@ class LinearFwd(object):
             return gz_t, dx_t
         return None
 
+    def _check_state_bwd(self, st, g2, a2, w, gz, dx):
+        """First fused backward of a Softplus or ELU pair of a solver: both results through torch as well.  gz to st.gz_bar * 2^-24 |g|
+        of st.gz(g, a), elementwise -- Softplus 4: either side's expm1 is held to that of the exact g (1 - e^-a) (the kernel's by its GPU
+        test), and they are the same function of the same library; ELU 1.5: one rounded add, one rounded product on both sides --; dx to
+        CHECK_TOL of |gz| |w| (the pairs' measure).  Returns None, or the torch results after switching that kind's fused backward --
+        only it -- off."""
+        st.bwd_checked = True
+        gz_t = st.gz(g2, a2)
+        dx_t = torch.matmul(gz_t, w)
+        scale = gz_t.abs() @ w.abs()
+        fin = torch.isfinite(gz_t)
+        ok = torch.isfinite(dx_t) & (scale > 0)
+        if not bool(fin.any()) or not bool(ok.any()):
+            st.bwd_checked = False                 # nothing to judge by: the next call is checked
+            return None
+        bad_z = bool((~((gz - gz_t).abs() <= st.gz_bar * 2.0 ** -24 * g2.abs()) & fin).any())
+        err = float(((dx - dx_t).abs() / scale)[ok].max())
+        if bad_z or not err <= CHECK_TOL:
+            st.bwd_disabled = True
+            st.bwd_why = "pn_linear_bwd_act and %s differ: " % st.torch_bwd + (
+                "g_z by more than %g * 2^-24 |g|" % st.gz_bar if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
+            warnings.warn("pnode_amd: the fused Linear -> %s backward is switched off for this solver: %s" % (st.name, st.bwd_why), RuntimeWarning)
+            return gz_t, dx_t
+        return None
+
     def _check_gelu_bwd(self, g2, z2, w, gz, dx):
         """First fused backward of a GELU pair of a solver: both results through torch as well.  gz to 32 * 2^-24 |g| of gelu_backward's,
         elementwise and ABSOLUTE in the derivative d = cdf + z pdf, which crosses zero near z = -0.7518 (a bar relative to |g d| would be 0
@@ -813,12 +965,14 @@ class LinearFwd(object):
             return gz_t, dx_t
         return None
 
-    def _backward(self, g, a, w, relu=False, sigmoid=False, gelu=False):
-        """(g_z, dx) of one pair by pn_linear_bwd (relu, sigmoid, gelu: pn_linear_bwd_act; gelu: `a` is the pre-activation), or None: the
-        caller runs tanh_backward (threshold_backward, sigmoid_backward, gelu_backward) and matmul."""
-        st = self.gelu if gelu else self.sig
-        sigmoid = sigmoid or gelu                  # (below: the pairs whose state is a record, `st`)
-        why = self._bwd_fusable(g, a, w, relu, sigmoid and not gelu, gelu)
+    def _backward(self, g, a, w, relu=False, sigmoid=False, gelu=False, st=None):
+        """(g_z, dx) of one pair by pn_linear_bwd (relu, sigmoid, gelu, st: pn_linear_bwd_act; gelu: `a` is the pre-activation; st: the
+        record of a Softplus or ELU pair), or None: the caller runs tanh_backward (threshold_backward, sigmoid_backward, gelu_backward,
+        st.gz) and matmul."""
+        kind = st                                  # (a record of _KINDS, or None)
+        st = kind if kind is not None else (self.gelu if gelu else self.sig)
+        why = self._bwd_fusable(g, a, w, relu, sigmoid, gelu, kind)
+        sigmoid = sigmoid or gelu or kind is not None      # (below: the pairs whose state is a record, `st`)
         if why is not None:
             if self.bwd_mode == "1" and not (st.warned_bwd if sigmoid else (self._warned_relu_bwd if relu else self._warned_bwd)):
                 if sigmoid:
@@ -833,7 +987,10 @@ class LinearFwd(object):
         out_f, in_f = w.shape
         g2, a2 = g.reshape(-1, out_f), a.reshape(-1, out_f)
         with torch.no_grad():
-            if gelu:
+            if kind is not None:
+                gz, dx = self.kernel_bwd_act(kind.act, g2, a2, w)
+                checked, check = st.bwd_checked, lambda *args: self._check_state_bwd(kind, *args)
+            elif gelu:
                 gz, dx = self.kernel_bwd_gelu(g2, a2, w)
                 checked, check = st.bwd_checked, self._check_gelu_bwd
             elif sigmoid:
@@ -928,15 +1085,18 @@ class LinearFwd(object):
 
     def _pair(self, lin, act, x, grads):
         """One pair: Linear -> Tanh or, where `act` is an nn.ReLU, Linear -> ReLU (its module is not called: either `inplace` will do), or,
-        where it is an nn.Sigmoid, Linear -> Sigmoid."""
+        where it is an nn.Sigmoid, Linear -> Sigmoid, an nn.GELU, Linear -> GELU, an nn.Softplus or nn.ELU, that pair (its record: `st`)."""
         relu, sigmoid, gelu = type(act) is nn.ReLU, type(act) is nn.Sigmoid, type(act) is nn.GELU
+        st = self._state(act)
         why = self._fusable(lin, x)
         if why is not None:
             if sigmoid:
                 self.sig.refused = why
             if gelu:
                 self.gelu.refused = why
-            self._refuse(why, relu, sigmoid, gelu)
+            if st is not None:
+                st.refused = why
+            self._refuse(why, relu, sigmoid, gelu, st)
             return act(lin(x))
         w, b = lin.weight, lin.bias
         ev = grads.recording if grads is not None else None
@@ -944,6 +1104,7 @@ class LinearFwd(object):
             ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
         call = _Call()
         call.owner, call.module, call.grads, call.ev, call.version, call.relu, call.sigmoid = self, lin, grads, ev, x._version, relu, sigmoid
+        call.state = st
         if gelu:
             # the saved-pre-activation form only where somebody will differentiate the call: else y alone, and no z is allocated
             call.pre = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad))
@@ -951,9 +1112,13 @@ class LinearFwd(object):
         else:
             a = _LinearTanh.apply(x, w, b, call)
         checked = self.gelu.checked if gelu else (self.sig.checked if sigmoid else (self.relu_checked if relu else self.checked))
+        if st is not None:
+            checked = st.checked
         if not checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
             args = (x.detach(), w.detach(), None if b is None else b.detach(), a.detach())
-            if gelu:
+            if st is not None:
+                good = self._check_state(st, *args)
+            elif gelu:
                 z = a.grad_fn.saved_tensors[2] if call.pre and a.grad_fn is not None else None
                 good = self._check_gelu(*args, z=z)
             else:
@@ -962,7 +1127,9 @@ class LinearFwd(object):
                 return act(lin(x))
         if ev is not None and a.grad_fn is not None:
             ev.through[a.grad_fn] = x.grad_fn     # Evaluation.clean passes the pair along its input edge only
-        if gelu:
+        if st is not None:
+            st.n += 1
+        elif gelu:
             self.gelu.n += 1
             self.gelu.n_pre += 1 if call.pre else 0
         elif sigmoid:
@@ -982,7 +1149,7 @@ class LinearFwd(object):
         if ev is not None and not grads.note_fused(lin, x):
             ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
         call = _Call()
-        call.owner, call.module, call.grads, call.ev, call.version = self, lin, grads, ev, x._version
+        call.owner, call.module, call.grads, call.ev, call.version, call.state = self, lin, grads, ev, x._version, None
         y = _Linear.apply(x, w, b, call)
         if not self.bare_checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
             if not self._check(x.detach(), w.detach(), None if b is None else b.detach(), y.detach(), bare=True):
@@ -998,6 +1165,8 @@ class LinearFwd(object):
             return self.sig.disabled
         if type(act) is nn.GELU:
             return self.gelu.disabled
+        if self._state(act) is not None:
+            return self._state(act).disabled
         return self.relu_disabled if type(act) is nn.ReLU else self.disabled
 
     def _runner(self, seq, pairs, alone, grads):
@@ -1021,13 +1190,14 @@ class LinearFwd(object):
 
     def _containers(self):
         """[(sequential, its pairs, its bare layers)]: the pairs while their forward is on (the ReLU pairs with -pn_linear_relu 1, the
-        Sigmoid pairs with -pn_linear_sigmoid 1, the GELU pairs with -pn_linear_gelu 1), the bare layers with -pn_linear_bare 1."""
+        Sigmoid pairs with -pn_linear_sigmoid 1, the GELU pairs with -pn_linear_gelu 1, the Softplus and ELU pairs with their options), the
+        bare layers with -pn_linear_bare 1."""
         out = {}
         if not self.disabled:
             for seq, pairs in self.plans:
                 out[id(seq)] = (seq, pairs, {})
         for plans in ((self.relu,) if self.relu_active else ()) + ((self.sig.plans,) if self.sig.active else ()) \
-                + ((self.gelu.plans,) if self.gelu.active else ()):
+                + ((self.gelu.plans,) if self.gelu.active else ()) + tuple(st.plans for st in self.kinds if st.active):
             for seq, pairs in plans:
                 both = dict(out[id(seq)][1]) if id(seq) in out else {}      # (a copy: the container's tanh pairs stay their own map)
                 both.update(pairs)
@@ -1049,8 +1219,11 @@ class LinearFwd(object):
                         continue
                     if _user_hooked(seq) or any(_user_hooked(m) for pr in pairs.values() for m in pr):
                         for relu, sigmoid, gelu in sorted({(type(pr[1]) is nn.ReLU, type(pr[1]) is nn.Sigmoid, type(pr[1]) is nn.GELU)
-                                                           for pr in pairs.values()}):
+                                                           for pr in pairs.values() if self._state(pr[1]) is None}):
                             self._refuse("a forward, pre-forward or backward hook on the pair or its container", relu, sigmoid, gelu)
+                        for st in self.kinds:
+                            if any(type(pr[1]) is st.kind for pr in pairs.values()):
+                                self._refuse("a forward, pre-forward or backward hook on the pair or its container", st=st)
                         if _user_hooked(seq):
                             continue
                         pairs = {}                # (a hooked pair keeps the stock modules; the bare layers of the container stay)

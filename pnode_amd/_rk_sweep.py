@@ -922,7 +922,9 @@ class RKSweep(object):
         -pn_linear_bare 0|1 (default 0): func's bare nn.Linear layers through pn_linear_fwd with the identity and pn_linear_dx.
         -pn_linear_relu 0|1 (default 0; anything else is refused): func's Linear -> ReLU pairs as the Tanh ones.
         -pn_linear_sigmoid 0|1 (default 0; anything else is refused): func's Linear -> Sigmoid pairs as the Tanh ones.
-        -pn_linear_gelu 0|1 (default 0; anything else is refused): func's Linear -> GELU pairs, which save their pre-activation."""
+        -pn_linear_gelu 0|1 (default 0; anything else is refused): func's Linear -> GELU pairs, which save their pre-activation.
+        -pn_linear_softplus 0|1, -pn_linear_elu 0|1 (default 0; anything else is refused): func's Linear -> Softplus (beta 1, threshold
+        20) and Linear -> ELU (alpha 1) pairs as the Sigmoid ones."""
         mode = str(options.get_all().get("pn_linear_fwd", "auto"))
         mode = "auto" if mode == "auto" else ("1" if options.truthy(mode, False) else "0")
         bwd = str(options.get_all().get("pn_linear_bwd", "auto"))
@@ -942,20 +944,28 @@ class RKSweep(object):
         gelu = str(options.get_all().get("pn_linear_gelu", "0"))
         if gelu not in ("0", "1"):
             raise PnError("-pn_linear_gelu must be 0 or 1 (got '%s')" % gelu)
+        # -pn_linear_softplus 0|1, -pn_linear_elu 0|1 (default 0): func's nn.Linear -> nn.Softplus / nn.ELU pairs through pn_linear_fwd with
+        # PN_ACT_SOFTPLUS / PN_ACT_ELU and pn_linear_bwd_act
+        softplus = str(options.get_all().get("pn_linear_softplus", "0"))
+        if softplus not in ("0", "1"):
+            raise PnError("-pn_linear_softplus must be 0 or 1 (got '%s')" % softplus)
+        elu = str(options.get_all().get("pn_linear_elu", "0"))
+        if elu not in ("0", "1"):
+            raise PnError("-pn_linear_elu must be 0 or 1 (got '%s')" % elu)
         form = options.linear_form()
         if hasattr(self._ops, "linear_flags"):
             self._ops.linear_flags = _lib.PN_LINEAR_FORM_PLAIN if form == "plain" else 0
         from ._linearfwd import LinearFwd
         on = mode != "0" and self._stepper_kind in (None, "imex") and self.device.type == LinearFwd.device_type \
             and self.tensor_dtype == torch.float32 and hasattr(self._ops, "linear_fwd")
-        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form, bare, relu, sigmoid, gelu)
+        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form, bare, relu, sigmoid, gelu, softplus, elu)
         if sig == self._fwd_sig:
             return
         self._fwd_sig = sig
         self._fwd = None
         if on and self._paramsE:
             fwd = LinearFwd(self)
-            if fwd.install(self.funcEX, self._paramsE, mode, bwd, bare, relu, sigmoid, gelu):
+            if fwd.install(self.funcEX, self._paramsE, mode, bwd, bare, relu, sigmoid, gelu, softplus, elu):
                 self._fwd = fwd
 
     @property
@@ -1016,6 +1026,25 @@ class RKSweep(object):
             return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" \
                 if str(options.get_all().get("pn_linear_gelu", "0")) == "1" else "off (-pn_linear_gelu 0)"
         return fwd.gelu_status
+
+    def _pair_status(self, name):
+        fwd = self._fwd
+        if fwd is None:
+            return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" \
+                if str(options.get_all().get("pn_linear_" + name, "0")) == "1" else "off (-pn_linear_%s 0)" % name
+        return getattr(fwd, name).status
+
+    @property
+    def linear_softplus(self):
+        """How func's nn.Linear -> nn.Softplus pairs (beta 1, threshold 20) run in the solver's evaluations: "off (-pn_linear_softplus
+        0)", "fused (N pairs; F forward, R backward calls so far)" or "stock modules (why)"."""
+        return self._pair_status("softplus")
+
+    @property
+    def linear_elu(self):
+        """How func's nn.Linear -> nn.ELU pairs (alpha 1) run in the solver's evaluations: "off (-pn_linear_elu 0)", "fused (N pairs; F
+        forward, R backward calls so far)" or "stock modules (why)"."""
+        return self._pair_status("elu")
 
     def _flush_param_accum(self):
         self._flush_bias_accum()

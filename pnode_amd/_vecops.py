@@ -231,7 +231,10 @@ class HipVecOps(object):
     # linear_act_fwd and linear_bwd take act="gelu" (PN_ACT_GELU; -pn_linear_gelu 1), linear_act_fwd a second output z (pn_linear_fwd_pre).
     # linear_fwd keeps refusing the name: its callers save the pair's OUTPUT, and GELU's backward needs the pre-activation
     linear_gelu = True
-    _ACTS = {"identity": _lib.PN_ACT_IDENTITY, "tanh": _lib.PN_ACT_TANH, "relu": _lib.PN_ACT_RELU, "sigmoid": _lib.PN_ACT_SIGMOID}
+    linear_softplus = True     # linear_fwd, linear_act_fwd and linear_bwd take act="softplus" (PN_ACT_SOFTPLUS; -pn_linear_softplus 1)
+    linear_elu = True          # ... and act="elu" (PN_ACT_ELU; -pn_linear_elu 1)
+    _ACTS = {"identity": _lib.PN_ACT_IDENTITY, "tanh": _lib.PN_ACT_TANH, "relu": _lib.PN_ACT_RELU, "sigmoid": _lib.PN_ACT_SIGMOID,
+             "softplus": _lib.PN_ACT_SOFTPLUS, "elu": _lib.PN_ACT_ELU}
     _ACTS_PRE = dict(_ACTS, gelu=_lib.PN_ACT_GELU)
 
     def linear_fwd(self, x, w, b, tanh, y=None, flags=None, act=None):
@@ -239,9 +242,10 @@ class HipVecOps(object):
         Refused (PnError), never run another way, outside pn_linear_fwd_supported and where y shares memory with x, w or b.  flags: pn_linear_fwd_form's (default: linear_flags).
         act: None -- `tanh` says which of the two --, or "identity", "tanh", "relu", "sigmoid" by name (`tanh` is then not looked at);
         "relu" gives relu of what the identity gives, value for value; "sigmoid" 1 / (1 + expf(-z)) of it, within 2.5 * 2^-24 of sigma.
-        ("gelu" is linear_act_fwd's.)"""
+        "softplus": nn.Softplus at beta 1, threshold 20 of it (z > 20 ? z : log1pf(expf(z))); "elu": nn.ELU at alpha 1 (z > 0 ? z :
+        expm1f(z)).  ("gelu" is linear_act_fwd's.)"""
         if act is not None and act not in self._ACTS:
-            raise PnError("pn_linear_fwd: act %r: identity, tanh or relu or sigmoid (gelu, and the pre-activation beside y: linear_act_fwd)" % (act,))
+            raise PnError("pn_linear_fwd: act %r: identity, tanh or relu or sigmoid or softplus or elu (gelu, and the pre-activation beside y: linear_act_fwd)" % (act,))
         return self._linear_fwd(self._ACTS[act] if act is not None else (_lib.PN_ACT_TANH if tanh else _lib.PN_ACT_IDENTITY), x, w, b, y, None, flags)
 
     def linear_act_fwd(self, x, w, b, act, y=None, z=None, flags=None):
@@ -250,7 +254,7 @@ class HipVecOps(object):
         receives the pre-activation x w^T + b beside y (pn_linear_fwd_pre; any act): the bits of what "identity" gives, and y the bits
         it has without z.  Returns y."""
         if act not in self._ACTS_PRE:
-            raise PnError("pn_linear_fwd_pre: act %r: identity, tanh or relu or sigmoid or gelu" % (act,))
+            raise PnError("pn_linear_fwd_pre: act %r: identity, tanh or relu or sigmoid or gelu or softplus or elu" % (act,))
         return self._linear_fwd(self._ACTS_PRE[act], x, w, b, y, z, flags)
 
     def _linear_fwd(self, code, x, w, b, y, z, flags):
@@ -287,9 +291,11 @@ class HipVecOps(object):
         flags: pn_linear_bwd_form's (default: linear_flags).  act="relu" (pn_linear_bwd_act): gz = threshold_backward(g, a, 0) bit for bit,
         dx the bits of linear_dx(gz, w).  act="sigmoid" (pn_linear_bwd_act): gz = g fmaf(-a, a, a), two roundings, the same bits in every
         form; dx the bits of linear_dx(gz, w).  act="gelu" (pn_linear_bwd_act): `a` is the pair's PRE-activation z; gz = g (cdf + z pdf),
-        aten.gelu_backward's formula, the same bits in every form; dx the bits of linear_dx(gz, w)."""
-        if act not in ("tanh", "relu", "sigmoid", "gelu"):
-            raise PnError("pn_linear_bwd: act %r: tanh or relu or sigmoid or gelu (no activation: linear_dx)" % (act,))
+        aten.gelu_backward's formula, the same bits in every form; dx the bits of linear_dx(gz, w).  act="softplus" (pn_linear_bwd_act),
+        a the pair's output: gz = g (-expm1f(-a)); act="elu": gz = a > 0 ? g : g (a + 1); the same bits in every form, dx the bits of
+        linear_dx(gz, w)."""
+        if act not in ("tanh", "relu", "sigmoid", "gelu", "softplus", "elu"):
+            raise PnError("pn_linear_bwd: act %r: tanh or relu or sigmoid or gelu or softplus or elu (no activation: linear_dx)" % (act,))
         rows, out_f = g.shape
         in_f = w.shape[1]
         for v in (g, a, w, gz, dx):

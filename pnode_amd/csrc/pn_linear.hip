@@ -681,25 +681,25 @@ struct Frags {                   // one slab's operand fragments of a wave: A (h
   s16x8 ah, am, al, b0h, b0m, b0l, b1h, b1m, b1l;
 };
 
-template <int I, int NREAD, int RPG, bool RD, bool ST>
+template <int I, int NREAD, int RPG, bool RD, bool ST, int NVALU = 8>
 __device__ __forceinline__ void pipe_groups() {
   if constexpr (I < 12) {
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          // one MFMA
     constexpr int left = NREAD - I * RPG, nr = left < 0 ? 0 : (left < RPG ? left : RPG);
-    if constexpr (ST) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);        // the split's VALU work
+    if constexpr (ST) __builtin_amdgcn_sched_group_barrier(0x002, NVALU, 0);    // the split's VALU work
     if constexpr (RD && nr > 0) __builtin_amdgcn_sched_group_barrier(0x100, nr, 0);      // fragment reads of the next slab
     if constexpr (ST) {
       // its LDS stores (the nine ds_write_b64 of a thread leave the compiler as five: pairs a part apart go as ds_write2st64_b64)
       if constexpr (I >= 3 && (I & 1)) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
     }
-    pipe_groups<I + 1, NREAD, RPG, RD, ST>();
+    pipe_groups<I + 1, NREAD, RPG, RD, ST, NVALU>();
   }
 }
 
 // NREAD: LDS read instructions per slab and wave (9 ds_read_b128 forward; 3 + 12 transposed ones backward); NLOAD: global loads per slab
 // and thread.  gload(G &, slab), lstore(const G &, slab, byte offset of the buffer), read(Frags &, byte offset of the buffer).
 // nslab is even and >= 2.
-template <int NREAD, int NLOAD, typename G, typename GL, typename LS, typename RF>
+template <int NREAD, int NLOAD, typename G, int NVALU = 8, typename GL, typename LS, typename RF>
 __device__ __forceinline__ void pipelined_slabs(const int nslab, const int BUF, f32x16 &acc0, f32x16 &acc1, GL gload, LS lstore, RF read) {
   constexpr int RPG = NREAD > 12 ? 2 : 1;
   G g0, g1;
@@ -717,7 +717,7 @@ __device__ __forceinline__ void pipelined_slabs(const int nslab, const int BUF, 
       __builtin_amdgcn_sched_group_barrier(0x002, 2 * NLOAD, 0);
       __builtin_amdgcn_sched_group_barrier(0x020, NLOAD, 0);
     }
-    pipe_groups<0, NREAD, RPG, RD, ST>();
+    pipe_groups<0, NREAD, RPG, RD, ST, NVALU>();
     // nothing of a step moves across its barrier: the MFMAs of the next step would wait for fragments that were read just now
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
@@ -782,6 +782,22 @@ struct FwdArgs {
 __device__ __forceinline__ float gelu_y(const float z) {
 #pragma clang fp contract(off)
   return 0.5f * z * (1.f + erff(z * 0.70710678f));
+}
+
+// Softplus of the biased sum at aten's default parameters (beta 1, threshold 20), aten's formula: z itself above the threshold (where
+// log1pf(expf(z)) - z is below 2.1e-9, under half an ulp of z), else log1pf(expf(z)).  expf underflows to +0 from z of about -104 on:
+// y is an exact +0; above that y is positive.  A NaN fails the comparison and goes through expf and log1pf.  Contraction has nothing to
+// fuse here; it is off so that the spelling stays what is written wherever this is inlined.
+__device__ __forceinline__ float softplus_y(const float z) {
+#pragma clang fp contract(off)
+  return z > 20.f ? z : log1pf(expf(z));
+}
+
+// ELU of the biased sum at alpha 1: z itself where z > 0, else expm1f(z) -- -0 for -0, exactly -1 from z of about -17.4 down; a NaN
+// fails the comparison and goes through expm1f.
+__device__ __forceinline__ float elu_y(const float z) {
+#pragma clang fp contract(off)
+  return z > 0.f ? z : expm1f(z);
 }
 
 struct FwdLoads {                // one slab's global loads of a thread
@@ -904,8 +920,11 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
   // (a.z, pn_linear_fwd_pre): the loops of a launch without z are what they were before there was one -- one more uniform branch in
   // front of them.  With z: the biased sum goes to z at y's tile positions under y's guards, one more 4-byte store per element; the
   // GELU pairs -- the ones that save z -- have that loop to themselves, every other act shares one that tests act per element.
-  auto finish = [&](auto sigmoid_c, auto gelu_c, auto pre_c) {
-    constexpr bool SIGMOID = decltype(sigmoid_c)::value, GELU = decltype(gelu_c)::value, PRE = decltype(pre_c)::value;
+  // The Softplus and ELU epilogues (softplus_y, elu_y) are loops of their own too, behind the last two uniform branches, and with z as
+  // well, as GELU's: as two more per-element tests inside the shared loop with z they cost all three kernels four scalar registers.
+  auto finish = [&](auto own_c, auto pre_c) {
+    constexpr int OWN = decltype(own_c)::value;                     // the act that has this loop to itself, or PN_ACT_IDENTITY: the shared one
+    constexpr bool SIGMOID = OWN == PN_ACT_SIGMOID, GELU = OWN == PN_ACT_GELU, PRE = decltype(pre_c)::value;
     const bool sigmoid_act = a.act == PN_ACT_SIGMOID;               // (looked at by the shared loop with z only)
     float *zp = PRE ? a.z + (size_t)row0 * out_f + col : nullptr;
 #pragma unroll
@@ -916,6 +935,10 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
       const float pre = z;
       if constexpr (GELU) {
         z = gelu_y(z);
+      } else if constexpr (OWN == PN_ACT_SOFTPLUS) {
+        z = softplus_y(z);
+      } else if constexpr (OWN == PN_ACT_ELU) {
+        z = elu_y(z);
       } else if constexpr (PRE) {
         if (sigmoid_act) z = 1.f / (1.f + expf(-z));                // (the Sigmoid loop's expression)
         if (tanh_act) z = tanhf(z);
@@ -939,17 +962,30 @@ __device__ __forceinline__ void linear_fwd_body(const FwdArgs &a) {
   };
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
+  constexpr std::integral_constant<int, PN_ACT_IDENTITY> shared{};
+  constexpr std::integral_constant<int, PN_ACT_SIGMOID> sigmoid{};
+  constexpr std::integral_constant<int, PN_ACT_GELU> gelu{};
+  constexpr std::integral_constant<int, PN_ACT_SOFTPLUS> softplus{};
+  constexpr std::integral_constant<int, PN_ACT_ELU> elu{};
   if (a.z != nullptr) {
     if (a.act == PN_ACT_GELU)
-      finish(no, yes, yes);
+      finish(gelu, yes);
+    else if (a.act == PN_ACT_SOFTPLUS)
+      finish(softplus, yes);
+    else if (a.act == PN_ACT_ELU)
+      finish(elu, yes);
     else
-      finish(no, no, yes);
+      finish(shared, yes);
   } else if (a.act == PN_ACT_GELU)
-    finish(no, yes, no);
+    finish(gelu, no);
   else if (a.act == PN_ACT_SIGMOID)
-    finish(yes, no, no);
+    finish(sigmoid, no);
+  else if (a.act == PN_ACT_SOFTPLUS)
+    finish(softplus, no);
+  else if (a.act == PN_ACT_ELU)
+    finish(elu, no);
   else
-    finish(no, no, no);
+    finish(shared, no);
 }
 
 // (pipelined: two sets of fragment and of load registers -- two waves per SIMD, as the LDS allows anyway)
@@ -1023,12 +1059,44 @@ __device__ __forceinline__ f32x4 gelu_gz(const f32x4 g, const f32x4 zin) {
   return r;
 }
 
+// PN_ACT_SOFTPLUS (pn_linear_bwd_act), a the pair's output log(1 + e^z) >= 0:
+//   gz[r][k] = g[r][k] (1 - e^(-a[r][k]))
+// -- sigma(z) written in the OUTPUT: 1 - e^(-a) = e^z / (1 + e^z).  -expm1f(-a) has no cancellation for any a >= 0: exactly 1 from a of
+// about 17.4 on (gz == g; the forward's y == z branch starts at 20), +-0 at a == 0 (z below -104).  ONE rounded product, contraction off
+// (sigmoid_gz says why); a NaN in a or g stays in its element; g = +-inf at a == 0: NaN.
+__device__ __forceinline__ f32x4 softplus_gz(const f32x4 g, const f32x4 a) {
+#pragma clang fp contract(off)
+  f32x4 z;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) z[e] = g[e] * (-expm1f(-a[e]));
+  return z;
+}
+
+// PN_ACT_ELU (pn_linear_bwd_act), a the pair's output (alpha 1: z where z > 0, else e^z - 1):
+//   gz[r][k] = a[r][k] > 0 ? g[r][k] : g[r][k] (a[r][k] + 1)
+// -- aten.elu_backward on the result: g's bits where a > 0; else one rounded add (e^z from the output) and ONE rounded product,
+// contraction off.  The comparison is a > 0 and not a <= 0, so that a NaN in a takes the arithmetic branch and gives a NaN (ReLU's
+// comparison lets g through); a == -1 with finite g gives 0.
+__device__ __forceinline__ f32x4 elu_gz(const f32x4 g, const f32x4 a) {
+#pragma clang fp contract(off)
+  f32x4 z;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) z[e] = a[e] > 0.f ? g[e] : g[e] * (a[e] + 1.f);
+  return z;
+}
+
 template <bool RAGGED, bool PIPE, int ACT = PN_ACT_TANH>
 __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
   static_assert(!(RAGGED && PIPE), "the pipelined loop loads without tests");
-  static_assert(ACT == PN_ACT_TANH || ACT == PN_ACT_IDENTITY || ACT == PN_ACT_RELU || ACT == PN_ACT_SIGMOID || ACT == PN_ACT_GELU,
-                "tanh, none, ReLU, sigmoid or GELU");
+  static_assert(ACT == PN_ACT_TANH || ACT == PN_ACT_IDENTITY || ACT == PN_ACT_RELU || ACT == PN_ACT_SIGMOID || ACT == PN_ACT_GELU ||
+                    ACT == PN_ACT_SOFTPLUS || ACT == PN_ACT_ELU,
+                "tanh, none, ReLU, sigmoid, GELU, softplus or ELU");
   constexpr bool BARE = ACT == PN_ACT_IDENTITY, RELU = ACT == PN_ACT_RELU, SIGMOID = ACT == PN_ACT_SIGMOID, GELU = ACT == PN_ACT_GELU;
+  constexpr bool SOFTPLUS = ACT == PN_ACT_SOFTPLUS, ELU = ACT == PN_ACT_ELU;
+  // VALU instructions per MFMA group of the pipelined loop (pipe_groups): the split's eight, plus room for the prologue's -- ELU's
+  // sixteen per step (a compare, an add, a product and a select per element), Softplus' four inlined expm1f.  With the siblings' eight
+  // the work that does not fit piles up behind the last MFMA and the kernels need 234 and 230 VGPRs; so: 227 and 225 (Sigmoid: 228)
+  constexpr int PVALU = ELU ? 12 : (SOFTPLUS ? 24 : 8);
   constexpr int AROWB = 2 * FK, APART = FM * AROWB;              // gz: [64 rows][32 bf16], 4 KB per part
   constexpr int WROWB = 128, WIMG = FK * WROWB, WPART = 2 * WIMG;      // W: two [32 k][64 bf16] images, 8 KB per part
   constexpr int BUF = 3 * APART + 3 * WPART;                     // 36 KB
@@ -1084,6 +1152,9 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
     } else if constexpr (GELU) {
       z = gelu_gz(gv, av);
       if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
+    } else if constexpr (SOFTPLUS || ELU) {
+      z = SOFTPLUS ? softplus_gz(gv, av) : elu_gz(gv, av);
+      if (keep) *reinterpret_cast<f32x4 *>(q.gz + aoff + slab * FK) = z;
     } else if constexpr (!BARE) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[e] = gv[e] * (1.f - av[e] * av[e]);
@@ -1129,7 +1200,7 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
     // stays one basic block for the interleave)
     auto run = [&](auto keep_c) {
       constexpr bool KEEP = decltype(keep_c)::value;
-      pipelined_slabs<15, BARE ? 3 : 4, BwdLoads>(
+      pipelined_slabs<15, BARE ? 3 : 4, BwdLoads, PVALU>(
           nslab, BUF, acc0, acc1,
           [&](BwdLoads &l, int slab) {
             l.g = *reinterpret_cast<const f32x4 *>(G + aoff + slab * FK);
@@ -1149,6 +1220,8 @@ __device__ __forceinline__ void linear_bwd_body(const BwdArgs &q) {
               z = sigmoid_gz(l.g, l.a);
             } else if constexpr (GELU) {
               z = gelu_gz(l.g, l.a);
+            } else if constexpr (SOFTPLUS || ELU) {
+              z = SOFTPLUS ? softplus_gz(l.g, l.a) : elu_gz(l.g, l.a);
             } else if constexpr (!BARE) {
 #pragma clang fp contract(off)
 #pragma unroll
@@ -1222,6 +1295,13 @@ __global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_sigmoid_kernel_f
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_gelu_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_GELU>(a); }
 __global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_gelu_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_GELU>(a); }
 __global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_gelu_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_GELU>(a); }
+// the Softplus and ELU pairs' (pn_linear_bwd_act with PN_ACT_SOFTPLUS / PN_ACT_ELU): the same
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_softplus_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_SOFTPLUS>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_softplus_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_SOFTPLUS>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_softplus_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_SOFTPLUS>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_elu_kernel_f32x3(BwdArgs a) { linear_bwd_body<false, false, PN_ACT_ELU>(a); }
+__global__ __launch_bounds__(kFwdThreads, 4) void pn_linear_bwd_elu_kernel_f32x3_ragged(BwdArgs a) { linear_bwd_body<true, false, PN_ACT_ELU>(a); }
+__global__ __launch_bounds__(kFwdThreads, 2) void pn_linear_bwd_elu_kernel_f32x3_pipe(BwdArgs a) { linear_bwd_body<false, true, PN_ACT_ELU>(a); }
 
 int cu_count() {
   static int n = 0;             // (the calling thread's current device; every device of a node is the same part)
@@ -1255,7 +1335,8 @@ int finish_t(hipStream_t st, int64_t out_f, int64_t in_f, void *pw, void *pb, vo
 }
 
 // what pn_linear_bwd_form and pn_linear_bwd_act share behind their own checks of `flags` (and of `act`): the shape rules, the null,
-// alignment and aliasing refusals, the choice of the form; act is PN_ACT_TANH, PN_ACT_RELU, PN_ACT_SIGMOID or PN_ACT_GELU
+// alignment and aliasing refusals, the choice of the form; act is PN_ACT_TANH, PN_ACT_RELU, PN_ACT_SIGMOID, PN_ACT_GELU, PN_ACT_SOFTPLUS
+// or PN_ACT_ELU
 int bwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *g, const void *a, const void *w, int act,
              void *gz, void *dx, int flags) {
   if (!pn_linear_bwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_bwd: unsupported dtype or shape (see pn_linear_bwd_supported)");
@@ -1288,6 +1369,15 @@ int bwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f,
     auto kern = ragged ? pn_linear_bwd_gelu_kernel_f32x3_ragged : (plain ? pn_linear_bwd_gelu_kernel_f32x3 : pn_linear_bwd_gelu_kernel_f32x3_pipe);
     return pn::launch("pn_linear_bwd_act", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
   }
+  if (act == PN_ACT_SOFTPLUS) {
+    auto kern = ragged ? pn_linear_bwd_softplus_kernel_f32x3_ragged
+                       : (plain ? pn_linear_bwd_softplus_kernel_f32x3 : pn_linear_bwd_softplus_kernel_f32x3_pipe);
+    return pn::launch("pn_linear_bwd_act", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
+  }
+  if (act == PN_ACT_ELU) {
+    auto kern = ragged ? pn_linear_bwd_elu_kernel_f32x3_ragged : (plain ? pn_linear_bwd_elu_kernel_f32x3 : pn_linear_bwd_elu_kernel_f32x3_pipe);
+    return pn::launch("pn_linear_bwd_act", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
+  }
   auto kern = ragged ? pn_linear_bwd_kernel_f32x3_ragged : (plain ? pn_linear_bwd_kernel_f32x3 : pn_linear_bwd_kernel_f32x3_pipe);
   return pn::launch("pn_linear_bwd", kern, dim3(blocks), dim3(kFwdThreads), (hipStream_t)stream, q);
 }
@@ -1296,8 +1386,9 @@ int bwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f,
 int fwd_pair(void *stream, int dtype, int64_t rows, int64_t out_f, int64_t in_f, const void *x, const void *w, const void *b, int act,
              void *y, void *z, int flags) {
   if (!pn_linear_fwd_supported(dtype, rows, out_f, in_f)) return pn::fail("pn_linear_fwd: unsupported dtype or shape (see pn_linear_fwd_supported)");
-  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID && act != PN_ACT_GELU)
-    return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY, PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID or PN_ACT_GELU");
+  if (act != PN_ACT_IDENTITY && act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID && act != PN_ACT_GELU &&
+      act != PN_ACT_SOFTPLUS && act != PN_ACT_ELU)
+    return pn::fail("pn_linear_fwd: act is PN_ACT_IDENTITY, PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID or PN_ACT_GELU or PN_ACT_SOFTPLUS or PN_ACT_ELU");
   if (x == nullptr || w == nullptr || y == nullptr) return pn::fail("pn_linear_fwd: null operand");
   if (!pn::aligned16(x, w, y) || (reinterpret_cast<uintptr_t>(b) & 3)) return pn::fail("pn_linear_fwd: operands must be 16-byte aligned");
   // an output that shares bytes with anything the launch reads: other workgroups still read x, w and b while a tile of y is stored
@@ -1448,8 +1539,9 @@ int pn_linear_bwd_act(void *stream, int dtype, int64_t rows, int64_t out_f, int6
                       void *gz, void *dx, int flags) {
   if (flags & ~PN_LINEAR_FORM_PLAIN) return pn::fail("pn_linear_bwd_act: unknown flag (PN_LINEAR_FORM_PLAIN is the only one)");
   if (act == PN_ACT_IDENTITY) return pn::fail("pn_linear_bwd_act: PN_ACT_IDENTITY has no prologue and no gz: use pn_linear_dx");
-  if (act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID && act != PN_ACT_GELU)
-    return pn::fail("pn_linear_bwd_act: act is PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID or PN_ACT_GELU (PN_ACT_IDENTITY: use pn_linear_dx)");
+  if (act != PN_ACT_TANH && act != PN_ACT_RELU && act != PN_ACT_SIGMOID && act != PN_ACT_GELU && act != PN_ACT_SOFTPLUS && act != PN_ACT_ELU)
+    return pn::fail("pn_linear_bwd_act: act is PN_ACT_TANH or PN_ACT_RELU or PN_ACT_SIGMOID or PN_ACT_GELU or PN_ACT_SOFTPLUS or PN_ACT_ELU "
+                    "(PN_ACT_IDENTITY: use pn_linear_dx)");
   return bwd_pair(stream, dtype, rows, out_f, in_f, g, a, w, act, gz, dx, flags);
 }
 

@@ -39,6 +39,7 @@ the pair as one launch that writes the pre-activation ``z`` beside ``y`` where t
 (``pn_linear_fwd_pre``; ``z`` is what the pair saves) and ``y`` alone elsewhere (``pn_linear_fwd`` with ``PN_ACT_GELU``), and its backward
 -- ``g_z = g (cdf + z pdf)``, ``dx = g_z W`` -- as one ``pn_linear_bwd_act`` launch reading ``z`` (``-pn_linear_bwd 0`` keeps
 ``gelu_backward`` and ``matmul``).  ``ode.linear_gelu`` reports what runs.  ``-pn_linear_fwd 0`` switches this off too.
+``-pn_linear_softplus 0|1``, ``-pn_linear_elu 0|1`` (read there too; anything else is refused): the same for the ``nn.Linear -> nn.Softplus`` (``beta == 1``, ``threshold == 20``) and ``nn.Linear -> nn.ELU`` (``alpha == 1``) pairs, saved-output pairs as the Sigmoid ones (``PN_ACT_SOFTPLUS``, ``PN_ACT_ELU``; ``ode.linear_softplus``, ``ode.linear_elu``).
 """
 import os
 import shlex
