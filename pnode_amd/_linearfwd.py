@@ -1,95 +1,94 @@
-"""func's ``nn.Linear -> nn.Tanh`` pairs as ONE launch in the solver's own evaluations of func (``pn_linear_fwd``, csrc/pn_linear.hip).
+"""func's ``nn.Linear`` layers, alone or with the activation behind them, as ONE launch in the solver's own evaluations of func
+(``pn_linear_fwd`` and its siblings, csrc/pn_linear.hip).
 
 The body of ``evalRHSFunction`` (pa.py:393-412) at BASELINE's target configuration is four library GEMMs and three elementwise
-``tanh`` launches; each ``tanh`` moves 16 MiB in about 6 us, twice what its traffic needs -- mostly dispatch floor.  A pair is
-therefore run as one MFMA kernel with the bias and ``tanhf`` in its epilogue, where ALL of this holds:
+``tanh`` launches; each ``tanh`` moves 16 MiB in about 6 us, twice what its traffic needs -- mostly dispatch floor.  A Linear and the
+activation behind it are therefore run as one MFMA kernel with the bias and the activation in its epilogue.
+
+THE RULES, the same for every kind of owned layer.  A pair is owned where ALL of this holds:
 
 * the pair is two consecutive children of an ``nn.Sequential`` whose ``forward`` is ``nn.Sequential``'s own; the first is exactly
   ``nn.Linear`` (no subclass; weight and bias trainable parameters of the solver, owned by no other module -- the rules of
-  ``LinearParamGrads.install``), the second exactly ``nn.Tanh``;
+  ``LinearParamGrads.install``), the second exactly the kind's module class with the parameters the kernel has (``_static_why`` and the
+  kind's ``param_why``; the activation module itself is never called, so either ``inplace`` will do);
 * neither module nor the container carries a hook that is not the engine's own, and no global module hook is registered;
-* at call time: the input is a contiguous CUDA fp32 tensor of the state's dtype, autocast is off, ``pn_linear_fwd_supported``.
+* at call time (``_fusable``): the input is a contiguous CUDA fp32 tensor of the state's dtype, autocast is off,
+  ``pn_linear_fwd_supported``.
 
 Anything else runs the stock modules.  Only evaluations inside ``LinearFwd.window`` are affected -- the solver opens it around its own
 calls of func; for its duration the eligible containers carry an instance-level ``forward`` (the runner below), removed when the window
 closes, also when func raises: func is left exactly as found (pnode_amd/_funcguard.py sees no change between two calls).
 
-Autograd: the pair is one ``torch.autograd.Function``.  Its backward forms ``g_z = g_a (1 - a^2)`` and ``dx = g_z W`` in ONE launch
-(``pn_linear_bwd``: the tanh' prologue in registers, W read as it lies) where the backend has ``linear_bwd``, ``-pn_linear_bwd`` is not
-``0``, the input needs a gradient, ``g_a`` is a contiguous, 16-byte aligned fp32 tensor of the pair's shape on the weight's device,
-autocast is off, the backward is not itself differentiated and ``pn_linear_bwd_supported``; otherwise with the torch operations
-autograd runs for the stock modules (``tanh_backward``, ``matmul``).  A solver's first fused backward outside a capture is formed both
-ways: ``g_z`` must agree to ``3 * 2^-24 |g_a|`` (two roundings in ``1 - a^2``, one in the product, with or without an fma) and ``dx``
-to 1e-6 of ``|g_z| |W|``; a miss switches the fused BACKWARD off for that solver (the forward stays), ``bwd_why`` recorded, and the
-torch results are returned.  Either way the backward hands ``(g_z, x)`` to
-``LinearParamGrads._grad_hook`` (the queue, the grouped launch, the side stream, the deferral under per-evaluation graphs) when that
-is active for the evaluation; otherwise it returns ``dW = g_z^T x`` and ``db = colsum(g_z)`` to autograd.  ``Evaluation.clean`` sees
-the pair's node as it sees a hooked layer: the walk goes on along the input edge only.
+Autograd: a pair is one ``torch.autograd.Function`` (``_LinearTanh``, for every kind) that saves ``(x, w, s)``, ``s`` the tensor the
+activation's derivative is a function of.  Its backward forms ``g_z = g act'(s)`` and ``dx = g_z W`` in ONE launch (the prologue in
+registers, W read as it lies) where the backend has the entry and the kind's capability flag, ``-pn_linear_bwd`` is not ``0``, the input
+needs a gradient, ``g`` is a contiguous, 16-byte aligned fp32 tensor of the pair's shape on the weight's device, autocast is off, the
+backward is not itself differentiated and ``pn_linear_bwd_supported`` (``_bwd_fusable``); otherwise with the torch operations autograd
+runs for the stock modules (the kind's ``gz``, then ``matmul``).  Either way the backward hands ``(g_z, x)`` to
+``LinearParamGrads._grad_hook`` (the queue, the grouped launch, the side stream, the deferral under per-evaluation graphs) when that is
+active for the evaluation; otherwise it returns ``dW = g_z^T x`` and ``db = colsum(g_z)`` to autograd.  ``Evaluation.clean`` sees the
+pair's node as it sees a hooked layer: the walk goes on along the input edge only.
 
-At a solver's first fused evaluation outside a capture the pair is computed through torch as well; a difference above 1e-6 of
-``sum |x w| + |b|`` (the library path's own 1.0e-7, the split product's 5.7e-8 and a few ulp of the two tanh, with room) switches
-fusing off for that solver, ``why`` recorded.  ``-pn_linear_fwd auto|0|1``, ``-pn_linear_bwd auto|0|1``.
+Self-checks, per kind and per solver.  The first fused call of a kind outside a capture is computed through torch as well, and so is
+its first fused backward: ``dx`` must agree to 1e-6 of ``|g_z| |W|``, the forward and ``g_z`` to the kind's bars below.  A check that
+finds no cell to judge by leaves the next call to be checked.  A miss switches off that kind's forward (``why``), or that kind's
+backward (``bwd_why``; its forward stays), and nothing else; the call returns the torch results.  Under stream capture nothing is
+checked.  Each record counts the calls that ran as one launch (``n``, ``n_bwd``): a call only after it passed or skipped its check.
 
-BARE layers (``-pn_linear_bare 0|1``, default ``0``: nothing below happens).  A child of an eligible container that is exactly
-``nn.Linear``, opens no fused pair and passes the static rules of a pair's Linear (``_static_why``, the same code) is a bare layer: the
-head of every ``... -> Linear`` net, a Linear in front of a ReLU or of a subclass of ``nn.Tanh``.  With ``1`` the runner sends it through
-``_Linear``: forward ``pn_linear_fwd`` with the identity under the call-time rules of ``_fusable``; backward ``dx = g W`` by
-``pn_linear_dx`` (the kernel body of ``pn_linear_bwd`` without the tanh' prologue: no ``a`` read, no ``g_z`` written) under the rules of
-``_bwd_fusable`` minus everything about ``a``, else ``matmul``; ``(g, x)`` then goes to ``LinearParamGrads._grad_hook`` exactly as a
-pair's ``(g_z, x)`` does.  A container whose only eligible members are bare layers is active too.  The self-checks are the pair's in
-the pair's measures (forward against ``F.linear``, ``dx`` against ``matmul``); a miss switches off the bare path, or its backward,
-only -- the pairs are not touched.  The bare layers are kept in ``LinearFwd.bare``, beside ``plans``.
+THE TABLE.  ``KINDS`` has one ``_Kind`` per kind of owned layer -- tanh, relu, sigmoid, gelu, softplus, elu, bare -- and holds everything
+that differs between them; no code outside it asks which kind it has.  Its columns:
 
-ReLU pairs (``-pn_linear_relu 0|1``, default ``0``: nothing below happens, a Linear in front of a ReLU stays a stock module or a bare
-layer).  With ``1`` two consecutive children ``nn.Linear``, exactly ``nn.ReLU`` (either ``inplace``: the module is not called) of an
-eligible container are a pair under the static and hook rules of a tanh pair, kept in ``LinearFwd.relu``; such a Linear is no bare layer.
-The pair runs through ``_LinearTanh`` with ``call.relu``: forward ``pn_linear_fwd`` with ``PN_ACT_RELU`` under ``_fusable``; backward
-``g_z = threshold_backward(g, a, 0)`` and ``dx = g_z W`` in one launch (``pn_linear_bwd_act``) under ``_bwd_fusable`` on a backend with
-``linear_relu``, else ``threshold_backward`` and ``matmul``; ``(g_z, x)`` goes to ``LinearParamGrads._grad_hook`` as a tanh pair's.
-Self-checks of their own: the forward against ``torch.relu(F.linear)`` in the pair's measure; ``g_z`` must be ``threshold_backward``'s
-bit for bit (the kernel does no arithmetic on it), ``dx`` in the pair's measure.  A miss switches off the ReLU pairs, or their backward,
-only.  ``n_relu`` / ``n_relu_bwd`` count them; ``n_fused`` / ``n_fused_bwd`` stay the tanh pairs'.
+``key``            the backend's name of the activation (``act=`` of ``linear_fwd`` / ``linear_bwd``), the stem of the option and of
+                   ``LinearFwd``'s names;
+``module``, ``param_why``  the module class, and the reason (or None) a module of that class has parameters the kernel has no slot for;
+``option``, ``always``  tanh pairs are always looked for and ``-pn_linear_fwd auto|0|1`` governs them (as it does every kind: with ``0``
+                   there is no ``LinearFwd``); every other kind only with its own ``-pn_linear_<key> 1`` (default ``0``: nothing happens);
+``class_key``      ``find_layers`` reports a pair that cannot be owned under the container's class name alone (tanh) or under
+                   ``(class name, name)``;
+``call_fwd``, ``call_bwd``  the form of the call into the backend (``_fwd_tanh`` ... ``_bwd_bare``); ``capability`` the flag of the backend
+                   the backward needs beside ``bwd_entry`` (``linear_<key>``; none where not ``flagged``); ``bwd_kernel`` the kernel's name in the messages;
+``saves_pre``      the derivative is a function of the PRE-activation (GELU), not of the output;
+``fwd``, ``torch_fwd``, ``gz``, ``gz_text``  the torch expressions the pair replaces, and their wording in the messages;
+``check``          the form of the forward check: ``_relative`` -- cells with ``sum |x w| + |b| > 0``, the difference at most 1e-6 of it (the
+                   library path's own 1.0e-7, the split product's 5.7e-8 and a few ulp of the activation, with room) -- or ``_barred``
+                   -- cells with a finite scale, the bar ``1e-6 (sum |x w| + |b|) + 4 * 2^-24`` for the activations that do not map a
+                   zero pre-activation to an exact 0;
+``gz_bar``         the bar of ``g_z`` in units of ``2^-24 |g|``, or None: bit for bit;
+``says``           what the status adds to its text; ``legacy`` the names ``LinearFwd`` has for the record's fields.
 
-Sigmoid pairs (``-pn_linear_sigmoid 0|1``, default ``0``: nothing below happens).  With ``1`` two consecutive children ``nn.Linear``,
-exactly ``nn.Sigmoid`` of an eligible container are a pair under the same rules; such a Linear is no bare layer.  Their maps, flags and
-counters are one record, ``LinearFwd.sig`` (a ``_PairState``), not a third copy of every field; ``n_sigmoid`` / ``n_sigmoid_bwd`` read
-it.  The pair runs through ``_LinearTanh`` with ``call.sigmoid``: forward ``pn_linear_fwd`` with ``PN_ACT_SIGMOID``; backward
-``g_z = g a (1 - a)`` and ``dx = g_z W`` in one launch (``pn_linear_bwd_act``) on a backend with ``linear_sigmoid``, else
-``sigmoid_backward`` and ``matmul``.  The arithmetic is not exact, so the self-checks are bounds: the forward against
-``torch.sigmoid(F.linear)`` to ``1e-6 (sum |x w| + |b|) + 4 * 2^-24`` -- the absolute term because a zero pre-activation maps to 0.5 with
-a rounding of its own on either side (the kernel at most 2.5, the library about 1 ulp of 2^-24), where tanh and ReLU give an exact 0;
-``g_z`` to ``1.5 * 2^-24 |g|`` of ``sigmoid_backward``'s (two roundings here, three there, relative to ``g a (1 - a) <= |g| / 4``); ``dx``
-in the pairs' measure.  A miss switches off the Sigmoid pairs, or their backward, only.
+A ``LinearFwd`` has one ``_PairState`` per row (``records``): the row's fields and, beside them, all that changes while a solver runs
+-- the plans, the option's value, the checks' flags and reasons, the counters, the warn-once flags.
 
-GELU pairs (``-pn_linear_gelu 0|1``, default ``0``: nothing below happens): the SAVED PRE-ACTIVATION form.  The derivative of every
-activation above is a function of the pair's output ``a``, so their Function saves ``(x, w, a)``.  GELU is not monotonic: its derivative
-needs ``z = x W^T + b``, which cannot be had back from ``a``.  With ``1`` two consecutive children ``nn.Linear``, exactly ``nn.GELU`` with
-``approximate == 'none'`` of an eligible container are a pair under the same rules (``approximate='tanh'`` is none: its reason is in
-``refused`` under ``(class name, "GELU")`` and in the status); one record, ``LinearFwd.gelu``.  The pair runs through ``_LinearGelu``.
-An evaluation that will be differentiated (grad mode on and the input or a parameter requires a gradient) launches ``pn_linear_fwd_pre``:
-``y`` and ``z`` from one epilogue; ``(x, w, z)`` is saved and ``y`` is not -- the memory of the stock pair.  Any other evaluation (the
-forward sweep without retained tapes) launches ``pn_linear_fwd`` with ``PN_ACT_GELU`` and allocates no ``z``.  ``LinearFwd.gelu.n``
-counts both, ``n_pre`` the first kind, ``n_y`` the second.  Backward: ``g_z = g (cdf + z pdf)`` and ``dx = g_z W`` in one launch
-(``pn_linear_bwd_act`` with ``PN_ACT_GELU``, reading ``z``) on a backend with ``linear_gelu``, else ``gelu_backward`` and ``matmul``.
-Self-checks as the Sigmoid pairs': the forward against ``F.gelu(F.linear)`` to ``1e-6 (sum |x w| + |b|) + 4 * 2^-24`` (GELU crosses zero
-at ``z = 0``: rows of scale 0 must have a bar above 0), ``z`` against ``F.linear`` in the bare layer's measure; ``g_z`` to ``32 * 2^-24 |g|``
-of ``gelu_backward``'s -- absolute in the derivative, which crosses zero near ``z = -0.7518``: two evaluations of ``erff``, each within
-the 16 ulp that OpenCL allows ``erf``, halved in ``cdf`` --; ``dx`` in the pairs' measure.  A miss switches off the GELU pairs, or their
-backward, only.
+THE KINDS, what is particular to each.
 
-Softplus and ELU pairs (``-pn_linear_softplus 0|1``, ``-pn_linear_elu 0|1``, default ``0``: nothing below happens).  Both derivatives are
-functions of the pair's OUTPUT -- ``1 - e^-a`` and ``a > 0 ? 1 : a + 1`` --, so these are saved-output pairs through ``_LinearTanh``, one
-record each (``LinearFwd.softplus``, ``LinearFwd.elu``) that also names the kernel's ``act``, the torch expressions the pair replaces and
-the bar of ``g_z``: nothing about them is spelled per kind outside ``_KINDS``.  With ``1`` two consecutive children ``nn.Linear``, exactly
-``nn.Softplus`` with ``beta == 1`` and ``threshold == 20`` (exactly ``nn.ELU`` with ``alpha == 1``, either ``inplace``: the module is not
-called) of an eligible container are a pair under the rules of the Sigmoid pairs; a module with other parameters is none -- the C entries
-have no slot for one --, its reason in ``refused`` under ``(class name, "Softplus")`` / ``(class name, "ELU")`` and in the status.  Forward
-``pn_linear_fwd`` with ``PN_ACT_SOFTPLUS`` / ``PN_ACT_ELU``; backward one ``pn_linear_bwd_act`` launch on a backend with
-``linear_softplus`` / ``linear_elu``, else ``g * (-expm1(-a))`` / ``aten.elu_backward(g, 1, 1, 1, True, a)`` and ``matmul``.  Self-checks:
-the forward against ``F.softplus(F.linear)`` / ``F.elu(F.linear)`` at the Sigmoid pairs' bar (Softplus maps a zero pre-activation to
-``log 2``: the absolute term again); ``g_z`` against those torch expressions to ``4 * 2^-24 |g|`` (Softplus: the cap on either side's
-``expm1``) and ``1.5 * 2^-24 |g|`` (ELU: one rounded add, one rounded product); ``dx`` in the pairs' measure.  A miss switches off that
-kind, or its backward, only."""
+Tanh: the first kind and the one with the older entry points -- ``linear_fwd(x, w, b, True)`` and ``linear_bwd(g, a, w)``
+(``pn_linear_bwd``) without ``act=``, no capability flag.  ``g_z = g_a (1 - a^2)``.
+
+ReLU: ``g_z`` has no arithmetic in it, so it must be ``threshold_backward``'s bit for bit, and a ``g_z`` that is not is a miss even
+where no cell of ``dx`` can be judged.  ReLU is 1-Lipschitz: the bare layer's forward bar carries over.
+
+Sigmoid: ``g_z = g a (1 - a)``.  The first kind with the barred forward check: sigma maps a zero pre-activation to 0.5 with a rounding
+of its own on either side (the kernel at most 2.5 ulp of 2^-24, the library about 1), where tanh and ReLU give an exact 0.
+
+GELU (exact only; ``approximate='tanh'`` is refused with its reason): the SAVED PRE-ACTIVATION kind.  GELU is not monotonic: its
+derivative needs ``z = x W^T + b``, which cannot be had back from the output.  An evaluation that will be differentiated (grad mode on
+and the input or a parameter requires a gradient) launches ``pn_linear_fwd_pre`` -- ``y`` and ``z`` from one epilogue; ``(x, w, z)`` is
+saved and ``y`` is not: the memory of the stock pair.  Any other evaluation (the forward sweep without retained tapes) launches
+``pn_linear_fwd`` with ``PN_ACT_GELU``, allocates no ``z`` and saves nothing.  Both go through ``linear_act_fwd`` (``linear_fwd`` refuses
+the name).  ``n`` counts both, ``n_pre`` the first, ``n_y`` the second.  The forward check also holds ``z``, where the call wrote it,
+against ``F.linear`` under the same bar.  Backward: ``g_z = g (cdf + z pdf)``.
+
+Softplus (``beta == 1`` and ``threshold == 20`` only) and ELU (``alpha == 1`` only): both derivatives are functions of the OUTPUT,
+``1 - e^-a`` and ``a > 0 ? 1 : a + 1``.  Softplus maps a zero pre-activation to ``log 2``, and ELU's rows of scale 0 are an exact 0 and
+need a bar above 0: the barred forward check.
+
+Bare (``-pn_linear_bare 0|1``): a child of an eligible container that is exactly ``nn.Linear``, opens no owned pair and passes the
+static rules of a pair's Linear -- the head of every ``... -> Linear`` net, a Linear in front of an activation whose option is off or
+of a subclass of ``nn.Tanh``.  It runs through ``_Linear``: forward ``linear_fwd(x, w, b, False)`` under ``_fusable``; backward
+``dx = g W`` by ``pn_linear_dx`` (the kernel body of ``pn_linear_bwd`` without the prologue: no ``a`` read, no ``g_z`` written) under the
+rules of ``_bwd_fusable`` minus everything about ``a``, else ``matmul``; ``(g, x)`` goes to ``LinearParamGrads._grad_hook`` as a pair's
+``(g_z, x)`` does.  A container whose only eligible members are bare layers is active too.  Neither a refused call nor a refused
+backward warns."""
 import contextlib
 import warnings
 import weakref
@@ -129,8 +128,8 @@ def _user_hooked(m):
 
 
 def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
-    """The static half of the eligibility rules for the Linear `lin` (and the activation `act` behind it, exactly a `kind`: nn.Tanh or
-    nn.ReLU or nn.Sigmoid or nn.GELU or nn.Softplus or nn.ELU; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
+    """The static half of the eligibility rules for the Linear `lin` (and the activation `act` behind it, exactly a `kind`, the module
+    class of a row of KINDS; None for a bare layer) among the children `kids` of `seq`: None, or the reason as a string."""
     mods = (lin,) if act is None else (lin, act)
     if type(seq) is not nn.Sequential or "forward" in seq.__dict__:
         return "the container's forward is not nn.Sequential's own"
@@ -151,6 +150,13 @@ def _static_why(seq, kids, lin, act, index, owners, kind=nn.Tanh):
     return why
 
 
+# ---- what the rows of KINDS are made of: the parameter rules, the torch expressions, the forms of the backend call and of the check
+def _gelu_why(act):
+    if getattr(act, "approximate", "none") != "none":
+        return "nn.GELU(approximate=%r): only the exact GELU (approximate='none') is owned" % (act.approximate,)
+    return None
+
+
 def _softplus_why(act):
     if act.beta != 1 or act.threshold != 20:
         return "nn.Softplus(beta=%r, threshold=%r): only beta == 1 and threshold == 20 are owned" % (act.beta, act.threshold)
@@ -163,19 +169,157 @@ def _elu_why(act):
     return None
 
 
-def find_layers(func, params, relu=False, sigmoid=False, gelu=False, softplus=False, elu=False):
-    """(plans, refused, bare): [(sequential, {index of the Linear child: (linear, tanh)})] of func; {class name of a container: reason}
-    for the Linear -> Tanh pairs that cannot be fused (what -pn_linear_fwd 1 warns about); and [(sequential, {index of the child:
-    linear})] for the bare layers -- exactly nn.Linear, opening no fused pair, under the same static rules (-pn_linear_bare 1).
-    relu (-pn_linear_relu 1): two consecutive children nn.Linear, nn.ReLU are a pair too, under the rules of a tanh pair -- (linear, relu)
-    in `plans`, told from a tanh pair by its second member, and such a Linear is no bare layer; a ReLU pair that cannot be fused is in
-    `refused` under the key (class name of the container, "ReLU").  Without it the three are what they were before there was the option.
-    sigmoid (-pn_linear_sigmoid 1): the same for nn.Linear, nn.Sigmoid; the key in `refused` is (class name, "Sigmoid").
-    gelu (-pn_linear_gelu 1): the same for nn.Linear, nn.GELU with approximate == 'none'; the key in `refused` is (class name, "GELU"),
-    also for an nn.GELU(approximate='tanh'), whose Linear is then a stock module or a bare layer.
-    softplus (-pn_linear_softplus 1), elu (-pn_linear_elu 1): the same for nn.Linear, nn.Softplus with beta == 1 and threshold == 20, and
-    for nn.Linear, nn.ELU with alpha == 1; the keys in `refused` are (class name, "Softplus") and (class name, "ELU"), also for a module
-    with other parameters."""
+def _relu_gz(g, a):
+    return torch.ops.aten.threshold_backward(g, a, 0)
+
+
+def _gelu_gz(g, z):
+    return torch.ops.aten.gelu_backward(g, z, approximate="none")
+
+
+def _softplus_gz(g, a):
+    return g * (-torch.expm1(-a))
+
+
+def _elu_gz(g, a):
+    return torch.ops.aten.elu_backward(g, 1, 1, 1, True, a)
+
+
+def _identity(z):
+    return z
+
+
+# the one place the device is touched.  (ops, key, x2, w, b, z) -> y; z: None, or the tensor the pre-activation goes to
+def _fwd_tanh(ops, key, x2, w, b, z):
+    return ops.linear_fwd(x2, w, b, True)
+
+
+def _fwd_bare(ops, key, x2, w, b, z):
+    return ops.linear_fwd(x2, w, b, False)
+
+
+def _fwd_act(ops, key, x2, w, b, z):
+    return ops.linear_fwd(x2, w, b, False, act=key)
+
+
+def _fwd_pre(ops, key, x2, w, b, z):
+    return ops.linear_act_fwd(x2, w, b, key) if z is None else ops.linear_act_fwd(x2, w, b, key, z=z)
+
+
+# (ops, key, g2, s2, w) -> (g_z, dx); a bare layer: dx alone
+def _bwd_tanh(ops, key, g2, s2, w):
+    return ops.linear_bwd(g2, s2, w)
+
+
+def _bwd_act(ops, key, g2, s2, w):
+    return ops.linear_bwd(g2, s2, w, act=key)
+
+
+def _bwd_bare(ops, key, g2, s2, w):
+    return ops.linear_dx(g2, w)
+
+
+# the two forms of the forward check.  (kind, a, ref, z, lin, scale) -> (True when there was a cell to judge by, None or the miss)
+def _relative(kind, a, ref, z, lin, scale):
+    ok = torch.isfinite(ref) & (scale > 0)
+    if not bool(ok.any()):
+        return False, None
+    err = float(((a - ref).abs() / scale)[ok].max())
+    if err <= CHECK_TOL:
+        return True, None
+    return True, "pn_linear_fwd and %s differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (kind.torch_fwd, err, CHECK_TOL)
+
+
+def _barred(kind, a, ref, z, lin, scale):
+    ok = torch.isfinite(ref) & torch.isfinite(scale)
+    if not bool(ok.any()):
+        return False, None
+    bar = CHECK_TOL * scale + 4.0 * 2.0 ** -24
+    over = ((a - ref).abs() / bar)[ok].max()
+    what = "pn_linear_fwd and %s" % kind.torch_fwd
+    if z is not None and float(over) <= 1.0:      # the pre-activation, where the call wrote it: against F.linear under the same bar
+        over = ((z.reshape(ref.shape) - lin).abs() / bar)[ok].max()
+        what = "the pre-activation of pn_linear_fwd_pre and F.linear"
+    if float(over) <= 1.0:
+        return True, None
+    return True, "%s differ by %.2f times the bar %.0e (sum |x w| + |b|) + 4 * 2^-24" % (what, float(over), CHECK_TOL)
+
+
+_FLAGS = ("mode", "disabled", "why", "checked", "bwd_disabled", "bwd_why", "bwd_checked")
+
+
+def _legacy(stem, fields, plans=None, record=None, count=None):
+    """{name on LinearFwd: field of the record, None for the record itself}: `fields` under `stem`_<field>, the two counters under
+    n_<count or stem> and n_<count or stem>_bwd, the plans and the record under the names given."""
+    names = {(stem + "_" + f if stem else f): f for f in fields}
+    names.update({"n_" + (count or stem): "n", "n_%s_bwd" % (count or stem): "n_bwd"})
+    if plans is not None:
+        names[plans] = "plans"
+    if record is not None:
+        names[record] = None
+    return names
+
+
+class _Kind(object):
+    """One row of KINDS (the columns: the module's docstring).  What is not given is what a kind added as a PN_ACT_* code has."""
+    def __init__(self, key, module, torch_fwd, fwd, gz_text, gz, gz_bar, check, legacy, param_why=None, option=None, always=False,
+                 class_key=False, call_fwd=_fwd_act, call_bwd=_bwd_act, flagged=True, bwd_entry="linear_bwd",
+                 bwd_kernel="pn_linear_bwd_act", saves_pre=False, says=(), none=None, plural="pairs", fwd_off=None):
+        self.key, self.module, self.param_why = key, module, param_why
+        self.name = module.__name__
+        self.option = option or "-pn_linear_" + key
+        self.always, self.class_key = always, class_key
+        self.call_fwd, self.call_bwd = call_fwd, call_bwd
+        self.capability = "linear_" + key if flagged else None
+        self.bwd_entry, self.bwd_kernel = bwd_entry, bwd_kernel
+        self.saves_pre = saves_pre
+        self.torch_fwd, self.fwd = torch_fwd, fwd
+        self.gz_text, self.gz, self.gz_bar = gz_text, gz, gz_bar
+        self.torch_bwd = gz_text + " + matmul"
+        self.check = check
+        self.says, self.legacy = says, legacy
+        # the wording of the status and of the forward check's warning
+        self.none = none or "no eligible Linear -> %s pair" % self.name
+        self.plural = plural
+        self.fwd_off = fwd_off or "the fused Linear -> %s forward is switched off for this solver: " % self.name
+
+
+KINDS = (
+    # g_z to 3 * 2^-24 |g|: two roundings in 1 - a^2, one in the product, with or without an fma
+    _Kind("tanh", nn.Tanh, "torch.tanh(F.linear)", torch.tanh, "tanh_backward", torch.ops.aten.tanh_backward, 3.0, _relative,
+          _legacy("", _FLAGS + ("bwd_mode",), plans="plans", count="fused"), option="-pn_linear_fwd", always=True, class_key=True,
+          call_fwd=_fwd_tanh, call_bwd=_bwd_tanh, flagged=False, bwd_kernel="pn_linear_bwd"),
+    # g_z bit for bit: the kernel does no arithmetic on it
+    _Kind("relu", nn.ReLU, "torch.relu(F.linear)", torch.relu, "threshold_backward", _relu_gz, None, _relative,
+          _legacy("relu", _FLAGS + ("active", "status"), plans="relu")),
+    # g_z to 1.5 * 2^-24 |g|: two roundings here, three in sigmoid_backward, each relative to |g a (1 - a)| <= |g| / 4
+    _Kind("sigmoid", nn.Sigmoid, "torch.sigmoid(F.linear)", torch.sigmoid, "sigmoid_backward", torch.ops.aten.sigmoid_backward, 1.5,
+          _barred, _legacy("sigmoid", ("active", "status"), plans="sigmoid", record="sig"), says=("refused",)),
+    # g_z to 32 * 2^-24 |g|, ABSOLUTE in the derivative d = cdf + z pdf, which crosses zero near z = -0.7518 (a bar relative to |g d|
+    # would be 0 there): each side evaluates erff once, within the 16 ulp OpenCL allows erf, of a value up to 1, halved in cdf --
+    # 8 * 2^-24 a side; z pdf <= 0.25 adds less than one more; twice that for the two sides
+    _Kind("gelu", nn.GELU, "F.gelu(F.linear)", F.gelu, "gelu_backward", _gelu_gz, 32.0, _barred,
+          _legacy("gelu", ("active", "status"), record="gelu"), param_why=_gelu_why, call_fwd=_fwd_pre, saves_pre=True,
+          says=("static", "refused")),
+    # g_z to 4 * 2^-24 |g|: either side's expm1 is held to that of the exact g (1 - e^-a) (the kernel's by its GPU test), and they are
+    # the same function of the same library
+    _Kind("softplus", nn.Softplus, "F.softplus(F.linear)", F.softplus, "g * (-expm1(-a))", _softplus_gz, 4.0, _barred,
+          _legacy("softplus", ("status",), record="softplus"), param_why=_softplus_why, says=("static", "refused")),
+    # g_z to 1.5 * 2^-24 |g|: one rounded add, one rounded product on both sides
+    _Kind("elu", nn.ELU, "F.elu(F.linear)", F.elu, "elu_backward", _elu_gz, 1.5, _barred,
+          _legacy("elu", ("status",), record="elu"), param_why=_elu_why, says=("static", "refused")),
+    # the bare layer: no activation, so no g_z -- its backward check is _check_bare_bwd
+    _Kind("bare", nn.Linear, "F.linear", _identity, "", None, None, _relative,
+          _legacy("bare", _FLAGS + ("active", "status"), plans="bare"), call_fwd=_fwd_bare, call_bwd=_bwd_bare, flagged=False,
+          bwd_entry="linear_dx", bwd_kernel="pn_linear_dx", none="no eligible bare layer", plural="layers",
+          fwd_off="the bare Linear layers run the stock modules for this solver: "),
+)
+PAIRS, BARE = KINDS[:-1], KINDS[-1]
+
+
+def _find(func, params, kinds):
+    """find_layers for the rows `kinds` of PAIRS: ([(sequential, {index of the Linear child: (linear, activation, row)})], {(row, class
+    name of a container): reason}, bare)."""
     plans, refused, bare = [], {}, []
     if not isinstance(func, nn.Module):
         return plans, refused, bare
@@ -196,31 +340,16 @@ def find_layers(func, params, relu=False, sigmoid=False, gelu=False, softplus=Fa
             lin, act = kids[i], kids[i + 1]
             if not isinstance(lin, nn.Linear):
                 continue
-            if isinstance(act, nn.Tanh):
-                kind, key = nn.Tanh, type(seq).__name__
-            elif relu and isinstance(act, nn.ReLU):
-                kind, key = nn.ReLU, (type(seq).__name__, "ReLU")
-            elif sigmoid and isinstance(act, nn.Sigmoid):
-                kind, key = nn.Sigmoid, (type(seq).__name__, "Sigmoid")
-            elif gelu and isinstance(act, nn.GELU):
-                kind, key = nn.GELU, (type(seq).__name__, "GELU")
-            elif softplus and isinstance(act, nn.Softplus):
-                kind, key = nn.Softplus, (type(seq).__name__, "Softplus")
-            elif elu and isinstance(act, nn.ELU):
-                kind, key = nn.ELU, (type(seq).__name__, "ELU")
-            else:
+            kind = next((k for k in kinds if isinstance(act, k.module)), None)
+            if kind is None:
                 continue
-            why = _static_why(seq, kids, lin, act, index, owners, kind)
-            if why is None and kind is nn.GELU and getattr(act, "approximate", "none") != "none":
-                why = "nn.GELU(approximate=%r): only the exact GELU (approximate='none') is owned" % (act.approximate,)
-            if why is None and kind is nn.Softplus:
-                why = _softplus_why(act)
-            if why is None and kind is nn.ELU:
-                why = _elu_why(act)
+            why = _static_why(seq, kids, lin, act, index, owners, kind.module)
+            if why is None and kind.param_why is not None:
+                why = kind.param_why(act)
             if why is None:
-                pairs[i] = (lin, act)
+                pairs[i] = (lin, act, kind)
             else:
-                refused.setdefault(key, why)
+                refused.setdefault((kind, type(seq).__name__), why)
         if pairs:
             plans.append((seq, pairs))
         alone = {i: m for i, m in enumerate(kids)
@@ -230,76 +359,71 @@ def find_layers(func, params, relu=False, sigmoid=False, gelu=False, softplus=Fa
     return plans, refused, bare
 
 
+def find_layers(func, params, relu=False, sigmoid=False, gelu=False, softplus=False, elu=False):
+    """(plans, refused, bare): [(sequential, {index of the Linear child: (linear, activation)})] of func, the pairs of every kind that
+    is looked for -- Linear -> Tanh always, every other row of PAIRS with its keyword (its option is 1), told apart by their second
+    member; {key: reason} for the pairs that cannot be owned (what -pn_linear_fwd 1 warns about), the key the class name of the
+    container for a tanh pair and (class name, "ReLU") ... (class name, "ELU") for the others, also for a module with parameters the
+    kernel has no slot for (nn.GELU(approximate='tanh'), nn.Softplus(beta=2)); and [(sequential, {index of the child: linear})] for
+    the bare layers -- exactly nn.Linear, opening no pair that is looked for, under the same static rules (-pn_linear_bare 1)."""
+    on = dict(relu=relu, sigmoid=sigmoid, gelu=gelu, softplus=softplus, elu=elu)
+    found, refused, bare = _find(func, params, [k for k in PAIRS if k.always or on[k.key]])
+    plans = [(seq, {i: p[:2] for i, p in pairs.items()}) for seq, pairs in found]
+    return plans, {(cls if kind.class_key else (cls, kind.name)): why for (kind, cls), why in refused.items()}, bare
+
+
 def find_pairs(func, params):
     """The first two of find_layers."""
     return find_layers(func, params)[:2]
 
 
 class _Call(object):
-    """What one fused call carries into its backward."""
-    __slots__ = ("owner", "module", "grads", "ev", "version", "relu", "sigmoid", "pre", "state")
+    """What one fused call carries into its backward.  state: the record of its kind; pre: the call also writes the pre-activation."""
+    __slots__ = ("owner", "module", "grads", "ev", "version", "pre", "state")
 
 
 class _PairState(object):
-    """The state of one further kind of pair beside the tanh and ReLU pairs, whose fields are LinearFwd's own: the map, the option, the
-    self-checks' flags and reasons, the counters.  `name` is the activation's class name, `torch_fwd` / `torch_bwd` the expressions the
-    pair replaces (in the wording of the warnings)."""
-    def __init__(self, name, option, torch_fwd, torch_bwd, kind=None, act=None, fwd=None, gz=None, gz_bar=None):
-        self.name, self.option, self.torch_fwd, self.torch_bwd = name, option, torch_fwd, torch_bwd
-        # the Softplus and ELU pairs (_KINDS): the module class, the backend's name of the activation, the torch functions behind
-        # `torch_fwd` and `torch_bwd`'s first half -- fwd(z), gz(g, a) --, and the self-check's bar of g_z in units of 2^-24 |g|
-        self.kind, self.act, self.fwd, self.gz, self.gz_bar = kind, act, fwd, gz, gz_bar
-        self.plans = []            # [(sequential, {child index: (linear, activation)})]
-        self.mode = "0"
+    """One kind of owned layer in one solver: the fields of its row of KINDS (`kind`) and, beside them, everything that changes."""
+    def __init__(self, kind):
+        self.kind = kind
+        self.__dict__.update(vars(kind))
+        self.plans = []            # [(sequential, {child index: (linear, activation)})]; the bare layers: {child index: linear}
+        self.mode = "auto" if kind.always else "0"
+        self.bwd_mode = "auto"     # -pn_linear_bwd, which governs every kind's backward: the tanh record's holds it
         self.disabled = False      # the forward check failed
         self.why = None
         self.checked = False
-        self.n = 0                 # pair calls that ran as one launch
-        self.n_pre = 0             # ... those of them that also wrote the pre-activation (pn_linear_fwd_pre; the GELU pairs)
+        self.n = 0                 # calls that ran as one launch
+        self.n_pre = 0             # ... those of them that also wrote the pre-activation (pn_linear_fwd_pre; `saves_pre`)
         self.static_why = None     # why a pair of this kind is none (find_layers' `refused`), for the status
         self.bwd_disabled = False  # the backward check failed (the forward stays)
         self.bwd_why = None
         self.bwd_checked = False
-        self.n_bwd = 0             # pair backwards that ran as one launch (pn_linear_bwd_act)
+        self.n_bwd = 0             # backwards that ran as one launch
         self.warned = False
         self.warned_bwd = False
         self.refused = None        # the reason of the last call-time refusal (LinearFwd._fusable): that call ran the stock modules
 
     @property
     def active(self):
-        return self.mode == "1" and bool(self.plans) and not self.disabled
+        return (self.always or self.mode == "1") and bool(self.plans) and not self.disabled
 
     @property
     def n_y(self):
-        """Pair calls that ran the y-only form: nobody differentiates them."""
+        """Calls that ran the y-only form: nobody differentiates them."""
         return self.n - self.n_pre
 
     @property
     def status(self):
-        if self.mode != "1":
+        if not (self.always or self.mode == "1"):
             return "off (%s 0)" % self.option
         if not self.plans:
-            return "stock modules (no eligible Linear -> %s pair%s)" % (self.name, "" if self.static_why is None else ": " + self.static_why)
+            return "stock modules (%s%s)" % (self.none, "" if "static" not in self.says or self.static_why is None else ": " + self.static_why)
         if self.disabled:
             return "stock modules (%s)" % self.why
-        return "fused (%d pairs; %d forward, %d backward calls so far%s)" % (
-            sum(len(p) for _, p in self.plans), self.n, self.n_bwd,
-            "" if self.refused is None else "; the stock modules where a call is refused, last: " + self.refused)
-
-
-def _softplus_gz(g, a):
-    return g * (-torch.expm1(-a))
-
-
-def _elu_gz(g, a):
-    return torch.ops.aten.elu_backward(g, 1, 1, 1, True, a)
-
-
-def _KINDS():
-    """The records of the saved-output pairs that are told by their record alone (LinearFwd.softplus, LinearFwd.elu), fresh ones."""
-    return (_PairState("Softplus", "-pn_linear_softplus", "F.softplus(F.linear)", "g * (-expm1(-a)) + matmul", nn.Softplus, "softplus",
-                       F.softplus, _softplus_gz, 4.0),
-            _PairState("ELU", "-pn_linear_elu", "F.elu(F.linear)", "elu_backward + matmul", nn.ELU, "elu", F.elu, _elu_gz, 1.5))
+        return "fused (%d %s; %d forward, %d backward calls so far%s)" % (
+            sum(len(p) for _, p in self.plans), self.plural, self.n, self.n_bwd,
+            "" if "refused" not in self.says or self.refused is None else "; the stock modules where a call is refused, last: " + self.refused)
 
 
 def _shaped(y2, shape):
@@ -309,71 +433,34 @@ def _shaped(y2, shape):
 
 
 class _LinearTanh(torch.autograd.Function):
-    """A Linear -> Tanh pair or, with call.relu (-pn_linear_relu 1), a Linear -> ReLU pair, or, with call.sigmoid (-pn_linear_sigmoid 1), a
-    Linear -> Sigmoid pair, or, with call.state (a record of _KINDS: -pn_linear_softplus 1, -pn_linear_elu 1), a Linear -> Softplus or
-    Linear -> ELU pair: the same structure, the other activation."""
+    """A pair of any kind (call.state: its record; the name is the first kind's).  Saved: (x, w, s), s the pair's output or, for a
+    kind that `saves_pre`, the pre-activation from the same launch when somebody will differentiate the call (call.pre) -- the output
+    is then not saved -- and nothing when nobody will."""
     @staticmethod
     def forward(ctx, x, w, b, call):
-        if call.state is not None:
-            a2 = call.owner.kernel_act(call.state.act, x.reshape(-1, w.shape[1]), w, b)
-        else:
-            kernel = call.owner.kernel_sigmoid if call.sigmoid else (call.owner.kernel_relu if call.relu else call.owner.kernel)
-            a2 = kernel(x.reshape(-1, w.shape[1]), w, b)
-        a = _shaped(a2, x.shape[:-1] + (w.shape[0],))
-        ctx.save_for_backward(x, w, a)
+        st = call.state
+        x2 = x.reshape(-1, w.shape[1])
+        shape = x.shape[:-1] + (w.shape[0],)
+        z2 = torch.empty((x2.shape[0], w.shape[0]), dtype=x2.dtype, device=x2.device) if call.pre else None
+        a = _shaped(call.owner.kernel(st, x2, w, b, z2), shape)
+        if call.pre:
+            ctx.save_for_backward(x, w, _shaped(z2, shape))
+        elif not st.saves_pre:
+            ctx.save_for_backward(x, w, a)
         ctx.call = call
         ctx.has_bias = b is not None
         return a
 
     @staticmethod
     def backward(ctx, g):
-        x, w, a = ctx.saved_tensors
+        x, w, s = ctx.saved_tensors
         call = ctx.call
-        # both in one launch (pn_linear_bwd, pn_linear_bwd_act) where LinearFwd._bwd_fusable allows it, else the two torch operations
-        if not ctx.needs_input_grad[0]:
-            fused = None
-        elif call.state is not None:
-            fused = call.owner._backward(g, a, w, st=call.state)
-        elif call.sigmoid:
-            fused = call.owner._backward(g, a, w, sigmoid=True)
-        else:
-            fused = call.owner._backward(g, a, w, call.relu)
+        # both in one launch where LinearFwd._bwd_fusable allows it, else the two torch operations
+        fused = call.owner._backward(call.state, g, s, w) if ctx.needs_input_grad[0] else None
         if fused is not None:
             g_z, dx = fused
         else:
-            if call.state is not None:
-                g_z = call.state.gz(g, a)
-            elif call.sigmoid:
-                g_z = torch.ops.aten.sigmoid_backward(g, a)
-            else:
-                g_z = torch.ops.aten.threshold_backward(g, a, 0) if call.relu else torch.ops.aten.tanh_backward(g, a)
-            dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
-        dw, db = _param_grads(ctx, call, g_z, x, w)
-        return dx, dw, db, None
-
-
-class _LinearGelu(torch.autograd.Function):
-    """A Linear -> GELU pair (-pn_linear_gelu 1): the sibling of _LinearTanh that saves the PRE-activation.  call.pre: somebody will
-    differentiate this evaluation -- y and z from one launch, (x, w, z) saved, y not; else y alone and nothing saved."""
-    @staticmethod
-    def forward(ctx, x, w, b, call):
-        y2, z2 = call.owner.kernel_gelu(x.reshape(-1, w.shape[1]), w, b, call.pre)
-        shape = x.shape[:-1] + (w.shape[0],)
-        if call.pre:
-            ctx.save_for_backward(x, w, _shaped(z2, shape))
-        ctx.call = call
-        ctx.has_bias = b is not None
-        return _shaped(y2, shape)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w, z = ctx.saved_tensors
-        call = ctx.call
-        fused = call.owner._backward(g, z, w, gelu=True) if ctx.needs_input_grad[0] else None
-        if fused is not None:
-            g_z, dx = fused
-        else:
-            g_z = torch.ops.aten.gelu_backward(g, z, approximate="none")
+            g_z = call.state.gz(g, s)
             dx = torch.matmul(g_z, w) if ctx.needs_input_grad[0] else None
         dw, db = _param_grads(ctx, call, g_z, x, w)
         return dx, dw, db, None
@@ -401,7 +488,7 @@ class _Linear(torch.autograd.Function):
     """A bare layer (-pn_linear_bare 1): _LinearTanh without the activation."""
     @staticmethod
     def forward(ctx, x, w, b, call):
-        y = _shaped(call.owner.kernel_bare(x.reshape(-1, w.shape[1]), w, b), x.shape[:-1] + (w.shape[0],))
+        y = _shaped(call.owner.kernel(call.state, x.reshape(-1, w.shape[1]), w, b, None), x.shape[:-1] + (w.shape[0],))
         ctx.save_for_backward(x, w)
         ctx.call = call
         ctx.has_bias = b is not None
@@ -422,190 +509,61 @@ class _Linear(torch.autograd.Function):
 
 
 class LinearFwd(object):
+    """The records of one solver (`records`: {key: _PairState}, in the order of KINDS) and the code that runs them.  The names the
+    records' fields have had on this object -- `plans`, `n_fused`, `relu_disabled`, `sig`, `gelu_status` ... -- read them (`legacy`)."""
     device_type = "cuda"           # (the tests of the eligibility rules run the rules on host tensors)
 
     def __init__(self, ode):
         self._ode = weakref.ref(ode)
-        self.plans = []            # [(sequential, {child index: (linear, tanh)})]
-        self.mode = "auto"
-        self.disabled = False      # the forward check failed
-        self.why = None
-        self.checked = False
-        self.n_fused = 0           # pair calls that ran as one launch
-        self._warned = False
+        self.records = {kind.key: _PairState(kind) for kind in KINDS}
+        self._tanh, self._bare_st = self.records["tanh"], self.records[BARE.key]
         self._ok = {}              # (rows, out_f, in_f) -> pn_linear_fwd_supported
-        # the pair's backward as one launch (pn_linear_bwd): -pn_linear_bwd auto|0|1
-        self.bwd_mode = "auto"
-        self.bwd_disabled = False  # the backward check failed (the forward stays fused)
-        self.bwd_why = None
-        self.bwd_checked = False
-        self.n_fused_bwd = 0       # pair backwards that ran as one launch
-        self._warned_bwd = False
-        self._ok_bwd = {}          # (rows, out_f, in_f) -> pn_linear_bwd_supported
-        # the bare layers (-pn_linear_bare 0|1): a map of their own; their checks switch off nothing but themselves
-        self.bare = []             # [(sequential, {child index: linear})]
-        self.bare_mode = "0"
-        self.bare_disabled = False      # the bare forward check failed
-        self.bare_why = None
-        self.bare_checked = False
-        self.n_bare = 0            # bare layer calls that ran pn_linear_fwd with the identity
-        self.bare_bwd_disabled = False  # the bare backward check failed (the bare forward stays)
-        self.bare_bwd_why = None
-        self.bare_bwd_checked = False
-        self.n_bare_bwd = 0        # bare backwards that ran pn_linear_dx
-        self._ok_dx = {}           # (rows, out_f, in_f) -> pn_linear_dx_supported
-        # the Linear -> ReLU pairs (-pn_linear_relu 0|1): a map, flags and counters of their own, as the bare layers'
-        self.relu = []             # [(sequential, {child index: (linear, relu)})]
-        self.relu_mode = "0"
-        self.relu_disabled = False      # the ReLU forward check failed
-        self.relu_why = None
-        self.relu_checked = False
-        self.n_relu = 0            # ReLU pair calls that ran as one launch
-        self.relu_bwd_disabled = False  # the ReLU backward check failed (the ReLU forward stays)
-        self.relu_bwd_why = None
-        self.relu_bwd_checked = False
-        self.n_relu_bwd = 0        # ReLU pair backwards that ran as one launch (pn_linear_bwd_act)
-        self._warned_relu = False
-        self._warned_relu_bwd = False
-        # the Linear -> Sigmoid pairs (-pn_linear_sigmoid 0|1): the same in one record
-        self.sig = _PairState("Sigmoid", "-pn_linear_sigmoid", "torch.sigmoid(F.linear)", "sigmoid_backward + matmul")
-        # the Linear -> GELU pairs (-pn_linear_gelu 0|1): one more record; the pairs that save their pre-activation
-        self.gelu = _PairState("GELU", "-pn_linear_gelu", "F.gelu(F.linear)", "gelu_backward + matmul")
-        # the Linear -> Softplus and Linear -> ELU pairs (-pn_linear_softplus 0|1, -pn_linear_elu 0|1): a record each
-        self.softplus, self.elu = self.kinds = _KINDS()
+        self._ok_bwd = {}          # (entry, rows, out_f, in_f) -> pn_<entry>_supported
 
     def install(self, func, params, mode="auto", bwd_mode="auto", bare_mode="0", relu_mode="0", sigmoid_mode="0", gelu_mode="0",
                 softplus_mode="0", elu_mode="0"):
-        """Find the eligible pairs of `func` (and, with bare_mode "1", its bare layers; with relu_mode "1", its Linear -> ReLU pairs; with
-        sigmoid_mode "1", its Linear -> Sigmoid pairs; with gelu_mode "1", its Linear -> GELU pairs; with softplus_mode / elu_mode "1",
-        its Linear -> Softplus / Linear -> ELU pairs); returns True when there is at least one."""
-        self.mode = mode
-        self.bwd_mode = bwd_mode
-        self.bare_mode = bare_mode
-        self.relu_mode = relu_mode
-        self.sig.mode = sigmoid_mode
-        self.sig.refused = None
-        self.gelu.mode = gelu_mode
-        self.gelu.refused = None
-        self.softplus.mode, self.elu.mode = softplus_mode, elu_mode
-        found, refused, self.bare = find_layers(func, params, relu_mode == "1", sigmoid=sigmoid_mode == "1", gelu=gelu_mode == "1",
-                                                softplus=softplus_mode == "1", elu=elu_mode == "1")
-        for st in (self.gelu,) + self.kinds:
-            st.static_why = next((why for key, why in refused.items() if isinstance(key, tuple) and key[1] == st.name), None)
-        self.plans, self.relu, self.sig.plans, self.gelu.plans = [], [], [], []
-        for st in self.kinds:
-            st.plans, st.refused = [], None
+        """Find the eligible pairs of `func` (the tanh pairs, and those of every kind whose mode is "1") and its bare layers; returns
+        True when there is at least one that will run fused."""
+        modes = dict(tanh=mode, bare=bare_mode, relu=relu_mode, sigmoid=sigmoid_mode, gelu=gelu_mode, softplus=softplus_mode, elu=elu_mode)
+        for st in self.records.values():
+            st.mode, st.plans, st.refused, st.static_why = modes[st.key], [], None, None
+        self._tanh.bwd_mode = bwd_mode
+        found, refused, self._bare_st.plans = _find(func, params, [k for k in PAIRS if k.always or modes[k.key] == "1"])
         for seq, pairs in found:
-            for kind, plans in ((nn.Tanh, self.plans), (nn.ReLU, self.relu), (nn.Sigmoid, self.sig.plans), (nn.GELU, self.gelu.plans)) \
-                    + tuple((st.kind, st.plans) for st in self.kinds):
-                mine = {i: p for i, p in pairs.items() if type(p[1]) is kind}
+            for st in self.records.values():
+                mine = {i: p[:2] for i, p in pairs.items() if p[2] is st.kind}
                 if mine:
-                    plans.append((seq, mine))
-        if mode == "1" and refused:
-            for key, why in refused.items():
-                cls, name = key if isinstance(key, tuple) else (key, "Tanh")
-                by_name = {st.name: st for st in (self.gelu,) + self.kinds}
-                if name in by_name:
-                    if by_name[name].warned:
-                        continue
-                elif self.sig.warned if name == "Sigmoid" else (self._warned_relu if name == "ReLU" else self._warned):
-                    continue
-                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair of %s runs the stock modules: %s" % (name, cls, why), RuntimeWarning)
-            self._warned = self._warned or any(not isinstance(key, tuple) for key in refused)
-            self._warned_relu = self._warned_relu or any(isinstance(key, tuple) and key[1] == "ReLU" for key in refused)
-            self.sig.warned = self.sig.warned or any(isinstance(key, tuple) and key[1] == "Sigmoid" for key in refused)
-            for st in (self.gelu,) + self.kinds:
-                st.warned = st.warned or any(isinstance(key, tuple) and key[1] == st.name for key in refused)
+                    st.plans.append((seq, mine))
+        told = []
+        for (kind, cls), why in refused.items():
+            st = self.records[kind.key]
+            if st.static_why is None:
+                st.static_why = why
+            if mode == "1" and not st.warned:
+                told.append(st)
+                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair of %s runs the stock modules: %s" % (st.name, cls, why), RuntimeWarning)
+        for st in told:
+            st.warned = True
         return self.active or bool(self.plans)
 
     @property
-    def bare_active(self):
-        return self.bare_mode == "1" and bool(self.bare) and not self.bare_disabled
-
-    @property
-    def relu_active(self):
-        return self.relu_mode == "1" and bool(self.relu) and not self.relu_disabled
-
-    @property
     def active(self):
-        return (bool(self.plans) and not self.disabled) or self.bare_active or self.relu_active or self.sig.active or self.gelu.active \
-            or any(st.active for st in self.kinds)
-
-    # what the Sigmoid pairs' record holds, under the names the tanh and ReLU pairs' fields have
-    @property
-    def sigmoid(self):
-        return self.sig.plans
+        return any(st.active for st in self.records.values())
 
     @property
-    def sigmoid_active(self):
-        return self.sig.active
-
-    @property
-    def sigmoid_status(self):
-        return self.sig.status
-
-    @property
-    def n_sigmoid(self):
-        return self.sig.n
-
-    @property
-    def n_sigmoid_bwd(self):
-        return self.sig.n_bwd
-
-    # ... and the GELU pairs' (`gelu` is the record itself)
-    @property
-    def gelu_active(self):
-        return self.gelu.active
-
-    @property
-    def gelu_status(self):
-        return self.gelu.status
-
-    @property
-    def n_gelu(self):
-        return self.gelu.n
-
-    @property
-    def n_gelu_bwd(self):
-        return self.gelu.n_bwd
-
-    # ... and the Softplus and ELU pairs' (`softplus` and `elu` are the records themselves)
-    @property
-    def softplus_status(self):
-        return self.softplus.status
-
-    @property
-    def elu_status(self):
-        return self.elu.status
+    def kinds(self):
+        """The Softplus and the ELU record (what the name held when only those two were told by their record)."""
+        return self.softplus, self.elu
 
     def _state(self, act):
-        """The record of `act`'s kind where the kind is told by its record alone (Softplus, ELU), else None."""
-        return next((st for st in self.kinds if type(act) is st.kind), None)
+        """The record of the pairs whose activation is exactly of `act`'s class, or None."""
+        return next((st for st in self.records.values() if type(act) is st.module and st.kind is not BARE), None)
 
-    # the one place the device is touched: tests of the eligibility rules replace it by the torch expression
-    def kernel(self, x2, w, b):
-        return self._ode()._ops.linear_fwd(x2, w, b, True)
+    def kernel(self, st, x2, w, b, z):
+        return st.call_fwd(self._ode()._ops, st.key, x2, w, b, z)
 
-    def kernel_bare(self, x2, w, b):
-        return self._ode()._ops.linear_fwd(x2, w, b, False)
-
-    def kernel_relu(self, x2, w, b):
-        return self._ode()._ops.linear_fwd(x2, w, b, False, act="relu")
-
-    def kernel_sigmoid(self, x2, w, b):
-        return self._ode()._ops.linear_fwd(x2, w, b, False, act="sigmoid")
-
-    def kernel_act(self, act, x2, w, b):
-        """The saved-output pairs named by `act` ("softplus", "elu")."""
-        return self._ode()._ops.linear_fwd(x2, w, b, False, act=act)
-
-    def kernel_gelu(self, x2, w, b, pre):
-        """(y, z): z the pre-activation from the same launch (pn_linear_fwd_pre) when `pre`, else None and no tensor allocated for it."""
-        ops = self._ode()._ops
-        if not pre:
-            return ops.linear_act_fwd(x2, w, b, "gelu"), None
-        z = torch.empty((x2.shape[0], w.shape[0]), dtype=x2.dtype, device=x2.device)
-        return ops.linear_act_fwd(x2, w, b, "gelu", z=z), z
+    def kernel_bwd(self, st, g2, s2, w):
+        return st.call_bwd(self._ode()._ops, st.key, g2, s2, w)
 
     def supported(self, rows, out_f, in_f):
         key = (rows, out_f, in_f)
@@ -615,23 +573,10 @@ class LinearFwd(object):
             ok = self._ok[key] = bool(hasattr(ops, "linear_fwd_supported") and ops.linear_fwd_supported(rows, out_f, in_f))
         return ok
 
-    def _refuse(self, why, relu=False, sigmoid=False, gelu=False, st=None):
-        st = self.gelu if gelu else st
-        if st is not None:
-            if self.mode == "1" and not st.warned:
-                st.warned = True
-                warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair runs the stock modules: %s" % (st.name, why), RuntimeWarning)
-            return None
-        if self.mode == "1" and not (self.sig.warned if sigmoid else (self._warned_relu if relu else self._warned)):
-            if sigmoid:
-                self.sig.warned = True
-            elif relu:
-                self._warned_relu = True
-            else:
-                self._warned = True
-            warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair runs the stock modules: %s"
-                          % ("Sigmoid" if sigmoid else ("ReLU" if relu else "Tanh"), why), RuntimeWarning)
-        return None
+    def _refuse(self, st, why):
+        if self._tanh.mode == "1" and not st.warned:
+            st.warned = True
+            warnings.warn("pnode_amd: -pn_linear_fwd 1: a Linear -> %s pair runs the stock modules: %s" % (st.name, why), RuntimeWarning)
 
     def _fusable(self, lin, x):
         """The call-time half of the eligibility rules; None or the reason as a string."""
@@ -651,535 +596,219 @@ class LinearFwd(object):
             return "outside pn_linear_fwd_supported"
         return None
 
-    def _check_sigmoid(self, x, w, b, a):
-        """First fused call of a Sigmoid pair of a solver: against torch.sigmoid(F.linear), |y - ref| <= CHECK_TOL (sum |x w| + |b|) +
-        4 * 2^-24.  The absolute term: sigma maps a zero pre-activation to 0.5 with a rounding of its own on either side (the kernel at
-        most 2.5 ulp of 2^-24, the library about 1), where tanh and ReLU give an exact 0 -- a small sum |x w| + |b| is no miss.  A miss
-        switches off the Sigmoid pairs only."""
-        st = self.sig
-        st.checked = True
-        with torch.no_grad():
-            x2 = x.reshape(-1, w.shape[1])
-            ref = torch.sigmoid(F.linear(x2, w, b))
-            scale = x2.abs() @ w.abs().t()
-            if b is not None:
-                scale = scale + b.abs()
-            ok = torch.isfinite(ref) & torch.isfinite(scale)
-            if not bool(ok.any()):
-                st.checked = False
-                return True
-            bar = CHECK_TOL * scale + 4.0 * 2.0 ** -24
-            over = ((a.reshape(ref.shape) - ref).abs() / bar)[ok].max()
-        if not float(over) <= 1.0:
-            st.disabled = True
-            st.why = "pn_linear_fwd and %s differ by %.2f times the bar %.0e (sum |x w| + |b|) + 4 * 2^-24" % (st.torch_fwd, float(over), CHECK_TOL)
-            warnings.warn("pnode_amd: the fused Linear -> %s forward is switched off for this solver: %s" % (st.name, st.why), RuntimeWarning)
-            return False
-        return True
-
-    def _check_state(self, st, x, w, b, a):
-        """First fused call of a Softplus or ELU pair of a solver: against st.fwd(F.linear) at the Sigmoid pairs' bar, |y - ref| <=
-        CHECK_TOL (sum |x w| + |b|) + 4 * 2^-24.  The absolute term: Softplus maps a zero pre-activation to log 2, with a rounding of
-        its own on either side; ELU's rows of scale 0 are an exact 0 and need a bar above 0.  A miss switches off that kind only."""
-        st.checked = True
-        with torch.no_grad():
-            x2 = x.reshape(-1, w.shape[1])
-            ref = st.fwd(F.linear(x2, w, b))
-            scale = x2.abs() @ w.abs().t()
-            if b is not None:
-                scale = scale + b.abs()
-            ok = torch.isfinite(ref) & torch.isfinite(scale)
-            if not bool(ok.any()):
-                st.checked = False
-                return True
-            bar = CHECK_TOL * scale + 4.0 * 2.0 ** -24
-            over = ((a.reshape(ref.shape) - ref).abs() / bar)[ok].max()
-        if not float(over) <= 1.0:
-            st.disabled = True
-            st.why = "pn_linear_fwd and %s differ by %.2f times the bar %.0e (sum |x w| + |b|) + 4 * 2^-24" % (st.torch_fwd, float(over), CHECK_TOL)
-            warnings.warn("pnode_amd: the fused Linear -> %s forward is switched off for this solver: %s" % (st.name, st.why), RuntimeWarning)
-            return False
-        return True
-
-    def _check_gelu(self, x, w, b, a, z=None):
-        """First fused call of a GELU pair of a solver: against F.gelu(F.linear), |y - ref| <= CHECK_TOL (sum |x w| + |b|) + 4 * 2^-24.
-        The absolute term: GELU crosses zero at z = 0 -- a row with x = 0 and b = 0 has the scale 0 and the bar must stay above it; next
-        to it the two erff (the kernel's and the library's) differ by their own ulps of a value up to 1, not of y.  z, where the call
-        wrote it: against F.linear in the bare layer's measure.  A miss switches off the GELU pairs only."""
-        st = self.gelu
+    def _check(self, st, x, w, b, a, z=None):
+        """First fused call of a kind in a solver: through torch as well, in the form of the kind's `check` (_relative, _barred), `z`
+        the pre-activation where the call wrote it.  True, or False after switching off that kind's forward -- only it."""
         st.checked = True
         with torch.no_grad():
             x2 = x.reshape(-1, w.shape[1])
             lin = F.linear(x2, w, b)
-            ref = F.gelu(lin)
+            ref = st.fwd(lin)
             scale = x2.abs() @ w.abs().t()
             if b is not None:
                 scale = scale + b.abs()
-            ok = torch.isfinite(ref) & torch.isfinite(scale)
-            if not bool(ok.any()):
-                st.checked = False
-                return True
-            bar = CHECK_TOL * scale + 4.0 * 2.0 ** -24
-            over = ((a.reshape(ref.shape) - ref).abs() / bar)[ok].max()
-            what = "pn_linear_fwd and %s" % st.torch_fwd
-            if z is not None and float(over) <= 1.0:
-                over = ((z.reshape(ref.shape) - lin).abs() / bar)[ok].max()
-                what = "the pre-activation of pn_linear_fwd_pre and F.linear"
-        if not float(over) <= 1.0:
-            st.disabled = True
-            st.why = "%s differ by %.2f times the bar %.0e (sum |x w| + |b|) + 4 * 2^-24" % (what, float(over), CHECK_TOL)
-            warnings.warn("pnode_amd: the fused Linear -> %s forward is switched off for this solver: %s" % (st.name, st.why), RuntimeWarning)
-            return False
-        return True
-
-    def _check(self, x, w, b, a, bare=False, relu=False):
-        """First fused call of a solver: the pair through torch as well.  bare: a bare layer's first call, against F.linear in the same
-        measure; a miss switches off the bare path only.  relu: a ReLU pair's first call, against torch.relu(F.linear) in the same
-        measure (ReLU is 1-Lipschitz: the bare layer's bar carries over); a miss switches off the ReLU pairs only."""
-        done = "bare_checked" if bare else ("relu_checked" if relu else "checked")
-        setattr(self, done, True)
-        with torch.no_grad():
-            x2 = x.reshape(-1, w.shape[1])
-            ref = F.linear(x2, w, b)
-            if relu:
-                ref = torch.relu(ref)
-            elif not bare:
-                ref = torch.tanh(ref)
-            scale = x2.abs() @ w.abs().t()
-            if b is not None:
-                scale = scale + b.abs()
-            ok = torch.isfinite(ref) & (scale > 0)
-            if not bool(ok.any()):
-                setattr(self, done, False)
-                return True
-            err = float(((a.reshape(ref.shape) - ref).abs() / scale)[ok].max())
-        if not err <= CHECK_TOL:
-            if bare:
-                self.bare_disabled = True
-                self.bare_why = "pn_linear_fwd and F.linear differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
-                warnings.warn("pnode_amd: the bare Linear layers run the stock modules for this solver: " + self.bare_why, RuntimeWarning)
-                return False
-            if relu:
-                self.relu_disabled = True
-                self.relu_why = "pn_linear_fwd and torch.relu(F.linear) differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
-                warnings.warn("pnode_amd: the fused Linear -> ReLU forward is switched off for this solver: " + self.relu_why, RuntimeWarning)
-                return False
-            self.disabled = True
-            self.why = "pn_linear_fwd and torch.tanh(F.linear) differ by %.2e of sum |x w| + |b| (allowed: %.0e)" % (err, CHECK_TOL)
-            warnings.warn("pnode_amd: the fused Linear -> Tanh forward is switched off for this solver: " + self.why, RuntimeWarning)
-            return False
-        return True
+            judged, why = st.check(st, a.reshape(ref.shape), ref, z, lin, scale)
+        if not judged:
+            st.checked = False                     # nothing to judge by: the next call is checked
+        if why is not None:
+            st.disabled, st.why = True, why
+            warnings.warn("pnode_amd: " + st.fwd_off + why, RuntimeWarning)
+        return why is None
 
     # ---- the backward of a pair (called from _LinearTanh.backward)
-    def kernel_bwd(self, g2, a2, w):
-        return self._ode()._ops.linear_bwd(g2, a2, w)
-
     def supported_bwd(self, rows, out_f, in_f, entry="linear_bwd"):
-        key = (rows, out_f, in_f)
-        cache = self._ok_bwd if entry == "linear_bwd" else self._ok_dx
-        ok = cache.get(key)
+        key = (entry, rows, out_f, in_f)
+        ok = self._ok_bwd.get(key)
         if ok is None:
             ops = self._ode()._ops
-            ok = cache[key] = bool(hasattr(ops, entry + "_supported") and getattr(ops, entry + "_supported")(rows, out_f, in_f))
+            ok = self._ok_bwd[key] = bool(hasattr(ops, entry + "_supported") and getattr(ops, entry + "_supported")(rows, out_f, in_f))
         return ok
 
-    def kernel_bwd_relu(self, g2, a2, w):
-        return self._ode()._ops.linear_bwd(g2, a2, w, act="relu")
-
-    def kernel_bwd_sigmoid(self, g2, a2, w):
-        return self._ode()._ops.linear_bwd(g2, a2, w, act="sigmoid")
-
-    def kernel_bwd_act(self, act, g2, a2, w):
-        return self._ode()._ops.linear_bwd(g2, a2, w, act=act)
-
-    def kernel_bwd_gelu(self, g2, z2, w):
-        return self._ode()._ops.linear_bwd(g2, z2, w, act="gelu")
-
-    def _bwd_fusable(self, g, a, w, relu=False, sigmoid=False, gelu=False, st=None):
-        """None, or the reason (a string) this backward runs the torch operations.  a: the pair's output; None for a bare layer
-        (pn_linear_dx: the same rules minus everything about a).  relu: a ReLU pair (pn_linear_bwd_act: the rules of a tanh pair, and
-        a backend with `linear_relu`).  sigmoid: a Sigmoid pair (the same, and a backend with `linear_sigmoid`).  gelu: a GELU pair (the same, and a
-        backend with `linear_gelu`; `a` is then the pair's pre-activation).  st: a Softplus or ELU pair's record (the same, and a backend with
-        `linear_softplus` / `linear_elu`)."""
-        bare = a is None
-        entry = "linear_dx" if bare else "linear_bwd"
+    def _bwd_fusable(self, st, g, s, w):
+        """None, or the reason (a string) this backward of a layer of `st` runs the torch operations.  s: the tensor the pair saved; None
+        for a bare layer (pn_linear_dx: the same rules minus everything about s)."""
         ode = self._ode()
-        if ode is None or not hasattr(ode._ops, entry):
-            return "the backend has no " + entry
-        if relu and not getattr(ode._ops, "linear_relu", False):
-            return "the backend has no linear_relu"
-        if sigmoid and not getattr(ode._ops, "linear_sigmoid", False):
-            return "the backend has no linear_sigmoid"
-        if gelu and not getattr(ode._ops, "linear_gelu", False):
-            return "the backend has no linear_gelu"
-        if st is not None and not getattr(ode._ops, "linear_" + st.act, False):
-            return "the backend has no linear_" + st.act
-        if self.bwd_mode == "0":
+        if ode is None or not hasattr(ode._ops, st.bwd_entry):
+            return "the backend has no " + st.bwd_entry
+        if st.capability is not None and not getattr(ode._ops, st.capability, False):
+            return "the backend has no " + st.capability
+        if self._tanh.bwd_mode == "0":
             return "-pn_linear_bwd 0"
-        if st is not None:
-            if st.bwd_disabled:
-                return st.bwd_why
-        elif gelu:
-            if self.gelu.bwd_disabled:
-                return self.gelu.bwd_why
-        elif sigmoid:
-            if self.sig.bwd_disabled:
-                return self.sig.bwd_why
-        elif relu:
-            if self.relu_bwd_disabled:
-                return self.relu_bwd_why
-        elif self.bare_bwd_disabled if bare else self.bwd_disabled:
-            return self.bare_bwd_why if bare else self.bwd_why
+        if st.bwd_disabled:
+            return st.bwd_why
         if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != w.device or g.device.type != self.device_type \
-                or (g.dim() < 1 or g.shape[-1] != w.shape[0] if bare else g.shape != a.shape):
+                or (g.dim() < 1 or g.shape[-1] != w.shape[0] if s is None else g.shape != s.shape):
             return "the cotangent is no fp32 tensor of the pair's shape on the weight's device"
-        if not (g.is_contiguous() and (bare or a.is_contiguous()) and w.is_contiguous()):
+        if not (g.is_contiguous() and (s is None or s.is_contiguous()) and w.is_contiguous()):
             return "the cotangent is not contiguous"
-        if g.data_ptr() % 16 or (not bare and a.data_ptr() % 16) or w.data_ptr() % 16:
+        if g.data_ptr() % 16 or (s is not None and s.data_ptr() % 16) or w.data_ptr() % 16:
             return "operands are not 16-byte aligned"
         if _autocast_on(g.device.type):
             return "autocast is on"
         if torch.is_grad_enabled():
             return "the backward pass is itself differentiated (create_graph)"
-        if not self.supported_bwd(g.numel() // w.shape[0], w.shape[0], w.shape[1], entry):
-            return "outside pn_%s_supported" % entry
+        if not self.supported_bwd(g.numel() // w.shape[0], w.shape[0], w.shape[1], st.bwd_entry):
+            return "outside pn_%s_supported" % st.bwd_entry
         return None
 
-    def _check_bwd(self, g2, a2, w, gz, dx):
-        """First fused backward of a solver: both results through torch as well.  gz to 3 * 2^-24 |g| (two roundings in 1 - a^2, one in
-        the product, with or without an fma), dx to CHECK_TOL of |gz| |w| (the forward's bar in the forward's measure).  Returns None, or
-        the torch results after switching the fused backward -- only it -- off."""
-        self.bwd_checked = True
-        gz_t = torch.ops.aten.tanh_backward(g2, a2)
-        dx_t = torch.matmul(gz_t, w)
-        scale = gz_t.abs() @ w.abs()
-        fin = torch.isfinite(gz_t)
-        ok = torch.isfinite(dx_t) & (scale > 0)
-        if not bool(fin.any()) or not bool(ok.any()):
-            self.bwd_checked = False               # nothing to judge by: the next call is checked
-            return None
-        bad_z = bool((~((gz - gz_t).abs() <= 3.0 * 2.0 ** -24 * g2.abs()) & fin).any())
-        err = float(((dx - dx_t).abs() / scale)[ok].max())
-        if bad_z or not err <= CHECK_TOL:
-            self.bwd_disabled = True
-            self.bwd_why = "pn_linear_bwd and tanh_backward + matmul differ: " + (
-                "g_z by more than 3 * 2^-24 |g|" if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
-            warnings.warn("pnode_amd: the fused Linear -> Tanh backward is switched off for this solver: " + self.bwd_why, RuntimeWarning)
-            return gz_t, dx_t
-        return None
-
-    def _check_relu_bwd(self, g2, a2, w, gz, dx):
-        """First fused backward of a ReLU pair of a solver: both results through torch as well.  gz has no arithmetic in it: it must be
-        threshold_backward's bit for bit; dx to CHECK_TOL of |gz| |w| (the tanh pair's bar in its measure).  Returns None, or the torch
-        results after switching the fused ReLU backward -- only it -- off."""
-        self.relu_bwd_checked = True
-        gz_t = torch.ops.aten.threshold_backward(g2, a2, 0)
-        dx_t = torch.matmul(gz_t, w)
-        scale = gz_t.abs() @ w.abs()
-        ok = torch.isfinite(dx_t) & (scale > 0)
-        bad_z = not torch.equal(gz.view(torch.int32), gz_t.view(torch.int32))
-        if not bad_z and not bool(ok.any()):
-            self.relu_bwd_checked = False          # nothing to judge dx by: the next call is checked
-            return None
-        err = float(((dx - dx_t).abs() / scale)[ok].max()) if bool(ok.any()) else 0.0
-        if bad_z or not err <= CHECK_TOL:
-            self.relu_bwd_disabled = True
-            self.relu_bwd_why = "pn_linear_bwd_act and threshold_backward + matmul differ: " + (
-                "g_z is not threshold_backward's bit for bit" if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
-            warnings.warn("pnode_amd: the fused Linear -> ReLU backward is switched off for this solver: " + self.relu_bwd_why, RuntimeWarning)
-            return gz_t, dx_t
-        return None
-
-    def _check_sigmoid_bwd(self, g2, a2, w, gz, dx):
-        """First fused backward of a Sigmoid pair of a solver: both results through torch as well.  gz to 1.5 * 2^-24 |g| of
-        sigmoid_backward's, elementwise (two roundings here, three there, each relative to |g a (1 - a)| <= |g| / 4); dx to CHECK_TOL of
-        |gz| |w| (the pairs' measure).  Returns None, or the torch results after switching the fused Sigmoid backward -- only it -- off."""
-        st = self.sig
+    def _check_bwd(self, st, g2, s2, w, gz, dx):
+        """First fused backward of a kind in a solver: both results through torch as well.  gz to st.gz_bar * 2^-24 |g| of st.gz(g, s),
+        elementwise (the bars: KINDS), or, with no bar, bit for bit -- then a g_z that differs is a miss even with no cell of dx to
+        judge by; dx to CHECK_TOL of |gz| |w| (the forward's bar in the forward's measure).  Returns None, or the torch results after
+        switching that kind's fused backward -- only it -- off."""
         st.bwd_checked = True
-        gz_t = torch.ops.aten.sigmoid_backward(g2, a2)
+        gz_t = st.gz(g2, s2)
         dx_t = torch.matmul(gz_t, w)
         scale = gz_t.abs() @ w.abs()
-        fin = torch.isfinite(gz_t)
         ok = torch.isfinite(dx_t) & (scale > 0)
-        if not bool(fin.any()) or not bool(ok.any()):
+        some = bool(ok.any())
+        if st.gz_bar is None:
+            bad_z, miss = not torch.equal(gz.view(torch.int32), gz_t.view(torch.int32)), "g_z is not %s's bit for bit" % st.gz_text
+            judged = bad_z or some
+        else:
+            fin = torch.isfinite(gz_t)
+            judged, miss = some and bool(fin.any()), "g_z by more than %g * 2^-24 |g|" % st.gz_bar
+            bad_z = judged and bool((~((gz - gz_t).abs() <= st.gz_bar * 2.0 ** -24 * g2.abs()) & fin).any())
+        if not judged:
             st.bwd_checked = False                 # nothing to judge by: the next call is checked
             return None
-        bad_z = bool((~((gz - gz_t).abs() <= 1.5 * 2.0 ** -24 * g2.abs()) & fin).any())
-        err = float(((dx - dx_t).abs() / scale)[ok].max())
+        err = float(((dx - dx_t).abs() / scale)[ok].max()) if some else 0.0
         if bad_z or not err <= CHECK_TOL:
             st.bwd_disabled = True
-            st.bwd_why = "pn_linear_bwd_act and %s differ: " % st.torch_bwd + (
-                "g_z by more than 1.5 * 2^-24 |g|" if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
+            st.bwd_why = "%s and %s differ: " % (st.bwd_kernel, st.torch_bwd) + (
+                miss if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
             warnings.warn("pnode_amd: the fused Linear -> %s backward is switched off for this solver: %s" % (st.name, st.bwd_why), RuntimeWarning)
             return gz_t, dx_t
         return None
 
-    def _check_state_bwd(self, st, g2, a2, w, gz, dx):
-        """First fused backward of a Softplus or ELU pair of a solver: both results through torch as well.  gz to st.gz_bar * 2^-24 |g|
-        of st.gz(g, a), elementwise -- Softplus 4: either side's expm1 is held to that of the exact g (1 - e^-a) (the kernel's by its GPU
-        test), and they are the same function of the same library; ELU 1.5: one rounded add, one rounded product on both sides --; dx to
-        CHECK_TOL of |gz| |w| (the pairs' measure).  Returns None, or the torch results after switching that kind's fused backward --
-        only it -- off."""
-        st.bwd_checked = True
-        gz_t = st.gz(g2, a2)
-        dx_t = torch.matmul(gz_t, w)
-        scale = gz_t.abs() @ w.abs()
-        fin = torch.isfinite(gz_t)
-        ok = torch.isfinite(dx_t) & (scale > 0)
-        if not bool(fin.any()) or not bool(ok.any()):
-            st.bwd_checked = False                 # nothing to judge by: the next call is checked
-            return None
-        bad_z = bool((~((gz - gz_t).abs() <= st.gz_bar * 2.0 ** -24 * g2.abs()) & fin).any())
-        err = float(((dx - dx_t).abs() / scale)[ok].max())
-        if bad_z or not err <= CHECK_TOL:
-            st.bwd_disabled = True
-            st.bwd_why = "pn_linear_bwd_act and %s differ: " % st.torch_bwd + (
-                "g_z by more than %g * 2^-24 |g|" % st.gz_bar if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
-            warnings.warn("pnode_amd: the fused Linear -> %s backward is switched off for this solver: %s" % (st.name, st.bwd_why), RuntimeWarning)
-            return gz_t, dx_t
-        return None
-
-    def _check_gelu_bwd(self, g2, z2, w, gz, dx):
-        """First fused backward of a GELU pair of a solver: both results through torch as well.  gz to 32 * 2^-24 |g| of gelu_backward's,
-        elementwise and ABSOLUTE in the derivative d = cdf + z pdf, which crosses zero near z = -0.7518 (a bar relative to |g d| would be 0
-        there): each side evaluates erff once, within the 16 ulp OpenCL allows erf, of a value up to 1, halved in cdf -- 8 * 2^-24 a
-        side; z pdf <= 0.25 adds less than one more; twice that for the two sides.  dx to CHECK_TOL of |gz| |w| (the pairs' measure).
-        Returns None, or the torch results after switching the fused GELU backward -- only it -- off."""
-        st = self.gelu
-        st.bwd_checked = True
-        gz_t = torch.ops.aten.gelu_backward(g2, z2, approximate="none")
-        dx_t = torch.matmul(gz_t, w)
-        scale = gz_t.abs() @ w.abs()
-        fin = torch.isfinite(gz_t)
-        ok = torch.isfinite(dx_t) & (scale > 0)
-        if not bool(fin.any()) or not bool(ok.any()):
-            st.bwd_checked = False                 # nothing to judge by: the next call is checked
-            return None
-        bad_z = bool((~((gz - gz_t).abs() <= 32.0 * 2.0 ** -24 * g2.abs()) & fin).any())
-        err = float(((dx - dx_t).abs() / scale)[ok].max())
-        if bad_z or not err <= CHECK_TOL:
-            st.bwd_disabled = True
-            st.bwd_why = "pn_linear_bwd_act and %s differ: " % st.torch_bwd + (
-                "g_z by more than 32 * 2^-24 |g|" if bad_z else "dx by %.2e of |g_z| |w| (allowed: %.0e)" % (err, CHECK_TOL))
-            warnings.warn("pnode_amd: the fused Linear -> %s backward is switched off for this solver: %s" % (st.name, st.bwd_why), RuntimeWarning)
-            return gz_t, dx_t
-        return None
-
-    def _backward(self, g, a, w, relu=False, sigmoid=False, gelu=False, st=None):
-        """(g_z, dx) of one pair by pn_linear_bwd (relu, sigmoid, gelu, st: pn_linear_bwd_act; gelu: `a` is the pre-activation; st: the
-        record of a Softplus or ELU pair), or None: the caller runs tanh_backward (threshold_backward, sigmoid_backward, gelu_backward,
-        st.gz) and matmul."""
-        kind = st                                  # (a record of _KINDS, or None)
-        st = kind if kind is not None else (self.gelu if gelu else self.sig)
-        why = self._bwd_fusable(g, a, w, relu, sigmoid, gelu, kind)
-        sigmoid = sigmoid or gelu or kind is not None      # (below: the pairs whose state is a record, `st`)
+    def _backward(self, st, g, s, w):
+        """(g_z, dx) of one pair of `st` in one launch (s: the tensor the pair saved), or None: the caller runs st.gz and matmul."""
+        why = self._bwd_fusable(st, g, s, w)
         if why is not None:
-            if self.bwd_mode == "1" and not (st.warned_bwd if sigmoid else (self._warned_relu_bwd if relu else self._warned_bwd)):
-                if sigmoid:
-                    st.warned_bwd = True
-                elif relu:
-                    self._warned_relu_bwd = True
-                else:
-                    self._warned_bwd = True
+            if self._tanh.bwd_mode == "1" and not st.warned_bwd:
+                st.warned_bwd = True
                 warnings.warn("pnode_amd: -pn_linear_bwd 1: the backward of a Linear -> %s pair runs the torch operations: %s"
-                              % (st.name if sigmoid else ("ReLU" if relu else "Tanh"), why), RuntimeWarning)
+                              % (st.name, why), RuntimeWarning)
             return None
         out_f, in_f = w.shape
-        g2, a2 = g.reshape(-1, out_f), a.reshape(-1, out_f)
+        g2, s2 = g.reshape(-1, out_f), s.reshape(-1, out_f)
         with torch.no_grad():
-            if kind is not None:
-                gz, dx = self.kernel_bwd_act(kind.act, g2, a2, w)
-                checked, check = st.bwd_checked, lambda *args: self._check_state_bwd(kind, *args)
-            elif gelu:
-                gz, dx = self.kernel_bwd_gelu(g2, a2, w)
-                checked, check = st.bwd_checked, self._check_gelu_bwd
-            elif sigmoid:
-                gz, dx = self.kernel_bwd_sigmoid(g2, a2, w)
-                checked, check = st.bwd_checked, self._check_sigmoid_bwd
-            elif relu:
-                gz, dx = self.kernel_bwd_relu(g2, a2, w)
-                checked, check = self.relu_bwd_checked, self._check_relu_bwd
-            else:
-                gz, dx = self.kernel_bwd(g2, a2, w)
-                checked, check = self.bwd_checked, self._check_bwd
-            if not checked and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
-                torch_way = check(g2, a2, w, gz, dx)
+            gz, dx = self.kernel_bwd(st, g2, s2, w)
+            if not st.bwd_checked and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
+                torch_way = self._check_bwd(st, g2, s2, w, gz, dx)
                 if torch_way is not None:
                     gz, dx = torch_way
                     return gz.view(g.shape), dx.view(g.shape[:-1] + (in_f,))
-        if sigmoid:
-            st.n_bwd += 1
-        elif relu:
-            self.n_relu_bwd += 1
-        else:
-            self.n_fused_bwd += 1
+        st.n_bwd += 1
         return gz.view(g.shape), dx.view(g.shape[:-1] + (in_f,))
 
     # ---- the backward of a bare layer (called from _Linear.backward)
-    def kernel_dx(self, g2, w):
-        return self._ode()._ops.linear_dx(g2, w)
-
-    def _check_bare_bwd(self, g2, w, dx):
+    def _check_bare_bwd(self, st, g2, w, dx):
         """First pn_linear_dx of a solver: through torch as well, to CHECK_TOL of |g| |w| (the pair's bar in the pair's measure).  Returns
         None, or the torch result after switching the bare backward -- only it -- off."""
-        self.bare_bwd_checked = True
+        st.bwd_checked = True
         dx_t = torch.matmul(g2, w)
         scale = g2.abs() @ w.abs()
         ok = torch.isfinite(dx_t) & (scale > 0)
         if not bool(ok.any()):
-            self.bare_bwd_checked = False          # nothing to judge by: the next call is checked
+            st.bwd_checked = False                 # nothing to judge by: the next call is checked
             return None
         err = float(((dx - dx_t).abs() / scale)[ok].max())
         if not err <= CHECK_TOL:
-            self.bare_bwd_disabled = True
-            self.bare_bwd_why = "pn_linear_dx and matmul differ: dx by %.2e of |g| |w| (allowed: %.0e)" % (err, CHECK_TOL)
-            warnings.warn("pnode_amd: the backward of the bare Linear layers runs matmul for this solver: " + self.bare_bwd_why, RuntimeWarning)
+            st.bwd_disabled = True
+            st.bwd_why = "pn_linear_dx and matmul differ: dx by %.2e of |g| |w| (allowed: %.0e)" % (err, CHECK_TOL)
+            warnings.warn("pnode_amd: the backward of the bare Linear layers runs matmul for this solver: " + st.bwd_why, RuntimeWarning)
             return dx_t
         return None
 
     def _backward_bare(self, g, w):
         """dx of one bare layer by pn_linear_dx, or None: the caller runs matmul."""
-        if self._bwd_fusable(g, None, w) is not None:
+        st = self._bare_st
+        if self._bwd_fusable(st, g, None, w) is not None:
             return None
         out_f, in_f = w.shape
         g2 = g.reshape(-1, out_f)
         with torch.no_grad():
-            dx = self.kernel_dx(g2, w)
-            if not self.bare_bwd_checked and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
-                torch_way = self._check_bare_bwd(g2, w, dx)
+            dx = self.kernel_bwd(st, g2, None, w)
+            if not st.bwd_checked and not (g.is_cuda and torch.cuda.is_current_stream_capturing()):
+                torch_way = self._check_bare_bwd(st, g2, w, dx)
                 if torch_way is not None:
                     return torch_way.view(g.shape[:-1] + (in_f,))
-        self.n_bare_bwd += 1
+        st.n_bwd += 1
         return dx.view(g.shape[:-1] + (in_f,))
 
     @property
-    def bare_status(self):
-        if self.bare_mode != "1":
-            return "off (-pn_linear_bare 0)"
-        if not self.bare:
-            return "stock modules (no eligible bare layer)"
-        if self.bare_disabled:
-            return "stock modules (%s)" % self.bare_why
-        return "fused (%d layers; %d forward, %d backward calls so far)" % (sum(len(b) for _, b in self.bare), self.n_bare, self.n_bare_bwd)
-
-    @property
-    def relu_status(self):
-        if self.relu_mode != "1":
-            return "off (-pn_linear_relu 0)"
-        if not self.relu:
-            return "stock modules (no eligible Linear -> ReLU pair)"
-        if self.relu_disabled:
-            return "stock modules (%s)" % self.relu_why
-        return "fused (%d pairs; %d forward, %d backward calls so far)" % (sum(len(p) for _, p in self.relu), self.n_relu, self.n_relu_bwd)
-
-    @property
     def bwd_status(self):
-        if self.bwd_mode == "0":
+        st = self._tanh
+        if st.bwd_mode == "0":
             return "torch operations (-pn_linear_bwd 0)"
         ode = self._ode()
-        if ode is None or not hasattr(ode._ops, "linear_bwd"):
-            return "torch operations (the backend has no linear_bwd)"
-        if self.bwd_disabled:
-            return "torch operations (%s)" % self.bwd_why
-        return "fused (%d calls so far)" % self.n_fused_bwd
+        if ode is None or not hasattr(ode._ops, st.bwd_entry):
+            return "torch operations (the backend has no %s)" % st.bwd_entry
+        if st.bwd_disabled:
+            return "torch operations (%s)" % st.bwd_why
+        return "fused (%d calls so far)" % st.n_bwd
 
-    def _pair(self, lin, act, x, grads):
-        """One pair: Linear -> Tanh or, where `act` is an nn.ReLU, Linear -> ReLU (its module is not called: either `inplace` will do), or,
-        where it is an nn.Sigmoid, Linear -> Sigmoid, an nn.GELU, Linear -> GELU, an nn.Softplus or nn.ELU, that pair (its record: `st`)."""
-        relu, sigmoid, gelu = type(act) is nn.ReLU, type(act) is nn.Sigmoid, type(act) is nn.GELU
-        st = self._state(act)
-        why = self._fusable(lin, x)
-        if why is not None:
-            if sigmoid:
-                self.sig.refused = why
-            if gelu:
-                self.gelu.refused = why
-            if st is not None:
-                st.refused = why
-            self._refuse(why, relu, sigmoid, gelu, st)
-            return act(lin(x))
-        w, b = lin.weight, lin.bias
+    def _call(self, st, lin, x, grads):
+        """(the _Call of one fused call of `lin`, the evaluation that records it or None)."""
         ev = grads.recording if grads is not None else None
         if ev is not None and not grads.note_fused(lin, x):
             ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
         call = _Call()
-        call.owner, call.module, call.grads, call.ev, call.version, call.relu, call.sigmoid = self, lin, grads, ev, x._version, relu, sigmoid
-        call.state = st
-        if gelu:
+        call.owner, call.module, call.grads, call.ev, call.version, call.state, call.pre = self, lin, grads, ev, x._version, st, False
+        return call, ev
+
+    def _pair(self, st, lin, act, x, grads):
+        """One pair of `st`: Linear -> `act` (the activation's module is not called)."""
+        why = self._fusable(lin, x)
+        if why is not None:
+            st.refused = why
+            self._refuse(st, why)
+            return act(lin(x))
+        w, b = lin.weight, lin.bias
+        call, ev = self._call(st, lin, x, grads)
+        if st.saves_pre:
             # the saved-pre-activation form only where somebody will differentiate the call: else y alone, and no z is allocated
             call.pre = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad))
-            a = _LinearGelu.apply(x, w, b, call)
-        else:
-            a = _LinearTanh.apply(x, w, b, call)
-        checked = self.gelu.checked if gelu else (self.sig.checked if sigmoid else (self.relu_checked if relu else self.checked))
-        if st is not None:
-            checked = st.checked
-        if not checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
-            args = (x.detach(), w.detach(), None if b is None else b.detach(), a.detach())
-            if st is not None:
-                good = self._check_state(st, *args)
-            elif gelu:
-                z = a.grad_fn.saved_tensors[2] if call.pre and a.grad_fn is not None else None
-                good = self._check_gelu(*args, z=z)
-            else:
-                good = self._check_sigmoid(*args) if sigmoid else self._check(*args, relu=relu)
-            if not good:
+        a = _LinearTanh.apply(x, w, b, call)
+        if not st.checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            z = a.grad_fn.saved_tensors[2] if call.pre and a.grad_fn is not None else None
+            if not self._check(st, x.detach(), w.detach(), None if b is None else b.detach(), a.detach(), z):
                 return act(lin(x))
         if ev is not None and a.grad_fn is not None:
             ev.through[a.grad_fn] = x.grad_fn     # Evaluation.clean passes the pair along its input edge only
-        if st is not None:
-            st.n += 1
-        elif gelu:
-            self.gelu.n += 1
-            self.gelu.n_pre += 1 if call.pre else 0
-        elif sigmoid:
-            self.sig.n += 1
-        elif relu:
-            self.n_relu += 1
-        else:
-            self.n_fused += 1
+        st.n += 1
+        st.n_pre += 1 if call.pre else 0
         return a
 
     def _bare(self, lin, x, grads):
         """One bare layer (-pn_linear_bare 1): _pair without the activation."""
+        st = self._bare_st
         if self._fusable(lin, x) is not None:
             return lin(x)
         w, b = lin.weight, lin.bias
-        ev = grads.recording if grads is not None else None
-        if ev is not None and not grads.note_fused(lin, x):
-            ev = None                             # (the evaluation is left to autograd: LinearParamGrads.end mutes it)
-        call = _Call()
-        call.owner, call.module, call.grads, call.ev, call.version, call.state = self, lin, grads, ev, x._version, None
+        call, ev = self._call(st, lin, x, grads)
         y = _Linear.apply(x, w, b, call)
-        if not self.bare_checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
-            if not self._check(x.detach(), w.detach(), None if b is None else b.detach(), y.detach(), bare=True):
+        if not st.checked and not (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            if not self._check(st, x.detach(), w.detach(), None if b is None else b.detach(), y.detach()):
                 return lin(x)
         if ev is not None and y.grad_fn is not None:
             ev.through[y.grad_fn] = x.grad_fn     # Evaluation.clean passes the layer along its input edge only
-        self.n_bare += 1
+        st.n += 1
         return y
 
-    def _off(self, act):
-        """The forward check of the pairs of `act`'s kind failed."""
-        if type(act) is nn.Sigmoid:
-            return self.sig.disabled
-        if type(act) is nn.GELU:
-            return self.gelu.disabled
-        if self._state(act) is not None:
-            return self._state(act).disabled
-        return self.relu_disabled if type(act) is nn.ReLU else self.disabled
-
     def _runner(self, seq, pairs, alone, grads):
+        bare = self._bare_st
+
         def forward(inp):
             kids = list(seq._modules.values())
             i, n = 0, len(kids)
             while i < n:
                 p = pairs.get(i)
-                if p is not None and i + 1 < n and kids[i] is p[0] and kids[i + 1] is p[1] \
-                        and not self._off(p[1]):
-                    inp = self._pair(p[0], p[1], inp, grads)
+                if p is not None and i + 1 < n and kids[i] is p[0] and kids[i + 1] is p[1] and not p[2].disabled:
+                    inp = self._pair(p[2], p[0], p[1], inp, grads)
                     i += 2
-                elif alone.get(i) is kids[i] and not self.bare_disabled:
+                elif alone.get(i) is kids[i] and not bare.disabled:
                     inp = self._bare(kids[i], inp, grads)
                     i += 1
                 else:
@@ -1189,22 +818,18 @@ class LinearFwd(object):
         return forward
 
     def _containers(self):
-        """[(sequential, its pairs, its bare layers)]: the pairs while their forward is on (the ReLU pairs with -pn_linear_relu 1, the
-        Sigmoid pairs with -pn_linear_sigmoid 1, the GELU pairs with -pn_linear_gelu 1, the Softplus and ELU pairs with their options), the
-        bare layers with -pn_linear_bare 1."""
+        """[(sequential, {child index: (linear, activation, record)}, its bare layers)]: the pairs of every kind that is active, the bare
+        layers with -pn_linear_bare 1."""
         out = {}
-        if not self.disabled:
-            for seq, pairs in self.plans:
-                out[id(seq)] = (seq, pairs, {})
-        for plans in ((self.relu,) if self.relu_active else ()) + ((self.sig.plans,) if self.sig.active else ()) \
-                + ((self.gelu.plans,) if self.gelu.active else ()) + tuple(st.plans for st in self.kinds if st.active):
-            for seq, pairs in plans:
-                both = dict(out[id(seq)][1]) if id(seq) in out else {}      # (a copy: the container's tanh pairs stay their own map)
-                both.update(pairs)
-                out[id(seq)] = (seq, both, {})
-        if self.bare_active:
-            for seq, alone in self.bare:
-                out[id(seq)] = (seq, out[id(seq)][1] if id(seq) in out else {}, alone)
+        for st in self.records.values():
+            if not st.active:
+                continue
+            for seq, plan in st.plans:
+                _, pairs, alone = out.setdefault(id(seq), (seq, {}, {}))
+                if st is self._bare_st:
+                    alone.update(plan)
+                else:
+                    pairs.update((i, p + (st,)) for i, p in plan.items())
         return list(out.values())
 
     @contextlib.contextmanager
@@ -1217,13 +842,10 @@ class LinearFwd(object):
                 for seq, pairs, alone in self._containers():
                     if "forward" in seq.__dict__ or type(seq) is not nn.Sequential:
                         continue
-                    if _user_hooked(seq) or any(_user_hooked(m) for pr in pairs.values() for m in pr):
-                        for relu, sigmoid, gelu in sorted({(type(pr[1]) is nn.ReLU, type(pr[1]) is nn.Sigmoid, type(pr[1]) is nn.GELU)
-                                                           for pr in pairs.values() if self._state(pr[1]) is None}):
-                            self._refuse("a forward, pre-forward or backward hook on the pair or its container", relu, sigmoid, gelu)
-                        for st in self.kinds:
-                            if any(type(pr[1]) is st.kind for pr in pairs.values()):
-                                self._refuse("a forward, pre-forward or backward hook on the pair or its container", st=st)
+                    if _user_hooked(seq) or any(_user_hooked(m) for pr in pairs.values() for m in pr[:2]):
+                        for st in self.records.values():
+                            if any(pr[2] is st for pr in pairs.values()):
+                                self._refuse(st, "a forward, pre-forward or backward hook on the pair or its container")
                         if _user_hooked(seq):
                             continue
                         pairs = {}                # (a hooked pair keeps the stock modules; the bare layers of the container stay)
@@ -1236,3 +858,14 @@ class LinearFwd(object):
         finally:
             for seq in put:
                 seq.__dict__.pop("forward", None)
+
+
+def _reader(key, field):
+    if field is None:
+        return property(lambda self: self.records[key])
+    return property(lambda self: getattr(self.records[key], field))
+
+
+for _kind in KINDS:
+    for _name, _field in _kind.legacy.items():
+        setattr(LinearFwd, _name, _reader(_kind.key, _field))

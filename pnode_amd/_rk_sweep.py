@@ -932,40 +932,28 @@ class RKSweep(object):
         # -pn_linear_form auto|plain: `plain` keeps the plain K loop of both kernels on aligned shapes too (PN_LINEAR_FORM_PLAIN; the
         # same bits as the pipelined loop they take by themselves) -- for comparisons inside one tree
         bare = "1" if options.truthy(options.get_all().get("pn_linear_bare", "0"), False) else "0"
-        # -pn_linear_relu 0|1 (default 0): func's nn.Linear -> nn.ReLU pairs through pn_linear_fwd with PN_ACT_RELU and pn_linear_bwd_act
-        relu = str(options.get_all().get("pn_linear_relu", "0"))
-        if relu not in ("0", "1"):
-            raise PnError("-pn_linear_relu must be 0 or 1 (got '%s')" % relu)
-        # -pn_linear_sigmoid 0|1 (default 0): func's nn.Linear -> nn.Sigmoid pairs through pn_linear_fwd with PN_ACT_SIGMOID and pn_linear_bwd_act
-        sigmoid = str(options.get_all().get("pn_linear_sigmoid", "0"))
-        if sigmoid not in ("0", "1"):
-            raise PnError("-pn_linear_sigmoid must be 0 or 1 (got '%s')" % sigmoid)
-        # -pn_linear_gelu 0|1 (default 0): func's nn.Linear -> nn.GELU pairs through pn_linear_fwd_pre / pn_linear_fwd with PN_ACT_GELU and pn_linear_bwd_act
-        gelu = str(options.get_all().get("pn_linear_gelu", "0"))
-        if gelu not in ("0", "1"):
-            raise PnError("-pn_linear_gelu must be 0 or 1 (got '%s')" % gelu)
-        # -pn_linear_softplus 0|1, -pn_linear_elu 0|1 (default 0): func's nn.Linear -> nn.Softplus / nn.ELU pairs through pn_linear_fwd with
-        # PN_ACT_SOFTPLUS / PN_ACT_ELU and pn_linear_bwd_act
-        softplus = str(options.get_all().get("pn_linear_softplus", "0"))
-        if softplus not in ("0", "1"):
-            raise PnError("-pn_linear_softplus must be 0 or 1 (got '%s')" % softplus)
-        elu = str(options.get_all().get("pn_linear_elu", "0"))
-        if elu not in ("0", "1"):
-            raise PnError("-pn_linear_elu must be 0 or 1 (got '%s')" % elu)
+        from ._linearfwd import PAIRS, LinearFwd
+        # -pn_linear_<key> 0|1 (default 0) of every kind of pair beside the tanh pairs: through pn_linear_fwd (pn_linear_fwd_pre) with the
+        # kind's PN_ACT_* code and pn_linear_bwd_act
+        acts = []
+        for kind in PAIRS:
+            if not kind.always:
+                acts.append(str(options.get_all().get(kind.option[1:], "0")))
+                if acts[-1] not in ("0", "1"):
+                    raise PnError("%s must be 0 or 1 (got '%s')" % (kind.option, acts[-1]))
         form = options.linear_form()
         if hasattr(self._ops, "linear_flags"):
             self._ops.linear_flags = _lib.PN_LINEAR_FORM_PLAIN if form == "plain" else 0
-        from ._linearfwd import LinearFwd
         on = mode != "0" and self._stepper_kind in (None, "imex") and self.device.type == LinearFwd.device_type \
             and self.tensor_dtype == torch.float32 and hasattr(self._ops, "linear_fwd")
-        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form, bare, relu, sigmoid, gelu, softplus, elu)
+        sig = (id(self.funcEX), mode, on, tuple(id(p) for p in self._paramsE), bwd, form, bare) + tuple(acts)
         if sig == self._fwd_sig:
             return
         self._fwd_sig = sig
         self._fwd = None
         if on and self._paramsE:
             fwd = LinearFwd(self)
-            if fwd.install(self.funcEX, self._paramsE, mode, bwd, bare, relu, sigmoid, gelu, softplus, elu):
+            if fwd.install(self.funcEX, self._paramsE, mode, bwd, bare, *acts):
                 self._fwd = fwd
 
     @property
@@ -1001,38 +989,26 @@ class RKSweep(object):
     def linear_relu(self):
         """How func's nn.Linear -> nn.ReLU pairs run in the solver's evaluations: "off (-pn_linear_relu 0)", "fused (N pairs; F forward,
         R backward calls so far)" or "stock modules (why)"."""
-        fwd = self._fwd
-        if fwd is None:
-            return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" \
-                if str(options.get_all().get("pn_linear_relu", "0")) == "1" else "off (-pn_linear_relu 0)"
-        return fwd.relu_status
+        return self._pair_status("relu")
 
     @property
     def linear_sigmoid(self):
         """How func's nn.Linear -> nn.Sigmoid pairs run in the solver's evaluations: "off (-pn_linear_sigmoid 0)", "fused (N pairs; F
         forward, R backward calls so far)" or "stock modules (why)"."""
-        fwd = self._fwd
-        if fwd is None:
-            return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" \
-                if str(options.get_all().get("pn_linear_sigmoid", "0")) == "1" else "off (-pn_linear_sigmoid 0)"
-        return fwd.sigmoid_status
+        return self._pair_status("sigmoid")
 
     @property
     def linear_gelu(self):
         """How func's nn.Linear -> nn.GELU pairs run in the solver's evaluations: "off (-pn_linear_gelu 0)", "fused (N pairs; F forward, R
         backward calls so far)" or "stock modules (why)"."""
-        fwd = self._fwd
-        if fwd is None:
-            return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" \
-                if str(options.get_all().get("pn_linear_gelu", "0")) == "1" else "off (-pn_linear_gelu 0)"
-        return fwd.gelu_status
+        return self._pair_status("gelu")
 
     def _pair_status(self, name):
         fwd = self._fwd
         if fwd is None:
             return "stock modules (no eligible pair, not an fp32 state on a HIP device, a theta stepper, or -pn_linear_fwd 0)" \
                 if str(options.get_all().get("pn_linear_" + name, "0")) == "1" else "off (-pn_linear_%s 0)" % name
-        return getattr(fwd, name).status
+        return fwd.records[name].status
 
     @property
     def linear_softplus(self):
