@@ -128,6 +128,23 @@ int pn_stream_wait_winf(void *stream, const double *result_host, int64_t n, doub
 /* The host half alone (no device): the largest of the per-workgroup partials of `block` (block[0] = their number), NaN if
  * any is NaN; 0.0 when every term was zero. */
 int pn_winf_finish(const double *block, int64_t n, double *value);
+/* pn_rk_combine_wrms / pn_rk_combine_winf with a tolerance per component (PETSc's TSSetTolerances(ts, atol, vatol, rtol, vrtol)
+ * with vectors, petsc4py's ts.setTolerances(rtol=Vec, atol=Vec) on the ode.ts a user of the reference holds, pa.py:370): the
+ * same arguments with `double atol, double rtol` replaced by two device vectors of `period` doubles and the period; element e
+ * of the flattened state uses entry e % period, i.e.
+ *   tol_e = vatol[e % period] + vrtol[e % period]*max(|unew_e|,|uhat_e|)
+ * and everything else -- update, err, the storage-type rounding of uhat, the fp32 form of the ratio, launch geometry, pinned
+ * partial block, finish (pn_stream_wait_wrms / pn_stream_wait_winf) and NaN/Inf propagation -- is the scalar entry point's:
+ * vectors filled with one value give its norm and its unew bit for bit.  period must divide n (period == n: one entry per
+ * element; period == n / B: one per component of a sample, repeated over the batch).  The vectors are only read.  They do
+ * not fit pn_vec_ops.rk_combine_wrms (two scalars), so the native step loop does not reach them: a caller walks the tableau
+ * itself (pn_rk_stage ... pn_rk_combine_wrms_v).  Profiled as PN_K_COMBINE_WRMS. */
+int pn_rk_combine_wrms_v(void *stream, int dtype, int64_t n, void *unew, const void *u,
+                         int nk, const void *const *K, const double *coef_b, const double *coef_e,
+                         const double *vatol, const double *vrtol, int64_t period, void *work, double *result_dev);
+int pn_rk_combine_winf_v(void *stream, int dtype, int64_t n, void *unew, const void *u,
+                         int nk, const void *const *K, const double *coef_b, const double *coef_e,
+                         const double *vatol, const double *vrtol, int64_t period, void *work, double *result_dev);
 /* A stream of the caller's own on the current device: priority > 0 the device's LOWEST priority (background work: the
  * weight-sensitivity products that run beside the reverse sweep's critical chain), < 0 the highest, 0 the default.  Not a
  * replacement of anything in the reference (PETSc's Vec operations run on one stream). */
@@ -580,6 +597,15 @@ int pn_rows_combine_wrms(void *stream, int dtype, int64_t B, int64_t d, void *un
 int pn_rows_combine_winf(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk,
                          const void *const *K, const double *coef_b, const double *coef_e, const double *h, double atol,
                          double rtol, double *enorm);
+/* pn_rows_combine_wrms / pn_rows_combine_winf with a tolerance per column (pn_rk_combine_wrms_v per row): vatol, vrtol hold
+ * `period` doubles on the device and period must be d -- every row uses entry c for its column c; the rows share the vectors,
+ * which are only read.  Everything else is the scalar entry point's; vectors filled with one value give its bits. */
+int pn_rows_combine_wrms_v(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk,
+                           const void *const *K, const double *coef_b, const double *coef_e, const double *h,
+                           const double *vatol, const double *vrtol, int64_t period, double *enorm);
+int pn_rows_combine_winf_v(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk,
+                           const void *const *K, const double *coef_b, const double *coef_e, const double *h,
+                           const double *vatol, const double *vrtol, int64_t period, double *enorm);
 /* One judgement per unfinished row with the controller constants of `ts` (TSAdaptChoose_Basic, MATCHSTEP, time span:
  * pn_ts_judge's arithmetic), one thread per row.  State: sd = doubles [4][B] (t, h, time of the row's next first stage
  * evaluation, the step remembered across an output time), si = int32 [8][B] (span counter, accepted steps, rejections,

@@ -92,6 +92,8 @@ PROTOTYPES = {
     "pn_rows_stage": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _vp]),
     "pn_rows_combine_wrms": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _d, _d, _vp]),
     "pn_rows_combine_winf": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _d, _d, _vp]),
+    "pn_rows_combine_wrms_v": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _vp, _vp, _i64, _vp]),
+    "pn_rows_combine_winf_v": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _vp, _vp, _i64, _vp]),
     "pn_rows_work_bytes": (_i64, [_i64]),
     "pn_rows_control": (_i, [_vp, _vp, _i64, _i, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pn_rows_control_host": (_i, [_vp, _i64, _i, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -125,6 +127,8 @@ PROTOTYPES = {
     "pn_stream_wait_wrms": (_i, [_vp, _vp, _i64, _pd]),
     "pn_rk_combine_winf": (_i, [_vp, _i, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _d, _d, _vp, _vp]),
     "pn_stream_wait_winf": (_i, [_vp, _vp, _i64, _pd]),
+    "pn_rk_combine_wrms_v": (_i, [_vp, _i, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _vp, _i64, _vp, _vp]),
+    "pn_rk_combine_winf_v": (_i, [_vp, _i, _i64, _vp, _vp, _i, _pvp, _pd, _pd, _vp, _vp, _i64, _vp, _vp]),
     "pn_winf_finish": (_i, [_vp, _i64, _pd]),
     "pn_pinned_scalar": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "pn_pinned_free": (_i, [_vp]),

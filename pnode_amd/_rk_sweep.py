@@ -107,7 +107,9 @@ class RKSweep(object):
         `tapes` (list of s entries, filled here) receives the autograd tape of each stage.
         """
         ops, s, A, b = self._ops, self._s, self._A, self._b
-        if self._native:
+        if self._native and not (want_err and self._vtol is not None):
+            # (per-component tolerances do not fit pn_vec_ops.rk_combine_wrms, which carries two scalars: such an attempt takes the
+            # stage loop below -- the same launches, the same bits -- and ends in the _v form of the norm, _errnorm.py)
             return self._rk_step_native(t, h, u, K0, unew, stage_dest, want_err, tapes, t_first)
         plan = self._stage_plan(h)
         K = [None] * s

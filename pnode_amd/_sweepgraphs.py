@@ -118,6 +118,10 @@ class SweepGraphs(object):
             # per-evaluation graphs, whose time argument is a tensor of their own)
             self._graph_status = "eager (t requires grad: the sweeps of a solve that differentiates with respect to t are not captured)"
             return None
+        if self._adaptive and self._vtol is not None:
+            # (setTolerances with a tensor: the attempts take the Python stage loop, which the per-evaluation graphs are not built around)
+            self._graph_status = "eager (per-component tolerances: adaptive attempts are launched by the Python stage loop)"
+            return None
         if self._adaptive and (self._theta is not None or not self._native or self._sharded()):
             # adaptive sweeps: per-evaluation graphs (_stagegraphs.py), explicit RK only; not for a batch sharded over ranks -- the
             # ranks meet in the error norm's all-reduce at every attempt, and a rank that validates (two sweeps) beside one that

@@ -123,6 +123,26 @@ class HipVecOps(object):
             self._vec_ops_inf = ctypes.cast(ctypes.pointer(self._vec_ops_inf_struct), ctypes.c_void_p)
         return self._vec_ops_inf
 
+    # ---- per-component tolerances (ODEPetsc.setTolerances; pnode_amd/_errnorm.py decides): vatol, vrtol are fp64 tensors of one
+    # period on this device; the norms land in the pinned block and are read by read_enorm / read_enorm_inf
+    vector_tolerances = True
+
+    def combine_wrms_v(self, unew, u, Ks, cb, ce, vatol, vrtol):
+        """combine_wrms with element e judged against vatol[e % p], vrtol[e % p], p = vatol.numel() (pn_rk_combine_wrms_v)."""
+        self.wrms_buffers()
+        check(self.lib.pn_rk_combine_wrms_v(self.stream(), self.code, self.n,
+                                            None if unew is None else unew.data_ptr(), u.data_ptr(),
+                                            len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce),
+                                            vatol.data_ptr(), vrtol.data_ptr(), vatol.numel(), self.work.data_ptr(), self._err_dev))
+
+    def combine_winf_v(self, unew, u, Ks, cb, ce, vatol, vrtol):
+        """combine_winf with per-component tolerances (pn_rk_combine_winf_v)."""
+        self.wrms_buffers()
+        check(self.lib.pn_rk_combine_winf_v(self.stream(), self.code, self.n,
+                                            None if unew is None else unew.data_ptr(), u.data_ptr(),
+                                            len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce),
+                                            vatol.data_ptr(), vrtol.data_ptr(), vatol.numel(), self.work.data_ptr(), self._err_dev))
+
     def adj_theta(self, w, lam, c_lam, dlams, coefs):
         check(self.lib.pn_adj_theta(self.stream(), self.code, self.n, w.data_ptr(),
                                     None if lam is None else lam.data_ptr(), c_lam,
@@ -405,6 +425,18 @@ class HipVecOps(object):
         check(self.lib.pn_rows_combine_winf(self.stream(), self.code, B, d, None if unew is None else unew.data_ptr(), u.data_ptr(),
                                             len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce), h.data_ptr(), atol, rtol,
                                             enorm.data_ptr()))
+
+    def rows_combine_wrms_v(self, B, d, unew, u, Ks, cb, ce, h, vatol, vrtol, enorm):
+        """rows_combine_wrms with column c judged against vatol[c], vrtol[c]: d entries each (pn_rows_combine_wrms_v)."""
+        check(self.lib.pn_rows_combine_wrms_v(self.stream(), self.code, B, d, None if unew is None else unew.data_ptr(), u.data_ptr(),
+                                              len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce), h.data_ptr(), vatol.data_ptr(),
+                                              vrtol.data_ptr(), vatol.numel(), enorm.data_ptr()))
+
+    def rows_combine_winf_v(self, B, d, unew, u, Ks, cb, ce, h, vatol, vrtol, enorm):
+        """rows_combine_winf with per-column tolerances (pn_rows_combine_winf_v)."""
+        check(self.lib.pn_rows_combine_winf_v(self.stream(), self.code, B, d, None if unew is None else unew.data_ptr(), u.data_ptr(),
+                                              len(Ks), self._ptrs(Ks), self._dbl(cb), self._dbl(ce), h.data_ptr(), vatol.data_ptr(),
+                                              vrtol.data_ptr(), vatol.numel(), enorm.data_ptr()))
 
     def rows_control(self, ts, B, nspan, span, max_time, enorm, sd, si, log_d, log_hit, accept, summary):
         """One judgement per unfinished row (pn_rows_control); `summary` is read by rows_summary."""

@@ -273,6 +273,122 @@ __global__ __launch_bounds__(kBlock) void pn_combine_winf_kernel(const T *x0, Er
 }
 
 // ---------------------------------------------------------------------------------------
+// Per-component tolerances (pn_rk_combine_wrms_v / pn_rk_combine_winf_v): the two kernels above with element e's term formed from
+// vatol[e % period], vrtol[e % period] instead of two kernel arguments -- the same loads of the state and the stage derivatives,
+// the same update and err chains, stores, ragged tail, trees and finishes, and the same wrms_term / winf_term, so that vectors
+// filled with one value give the scalar kernels' bits.  (Texts of their own: the scalar kernels' code stays what it was.)
+//
+// The index.  A thread's chunks start kBlock * VW elements apart and a chunk may straddle the period, which need not be a
+// multiple of VW (ROBER: 3).  So: ONE 64-bit remainder per thread (its first element), then additions with a wrap -- from chunk
+// to chunk by (kBlock * VW) % period, a wave-uniform value, and from element to element by one.  The tolerance entries are
+// per-lane vector loads (lanes hold different entries; a scalar load needs one address per wave), issued with the thread's other
+// loads; with period << n the two vectors stay in L1 / L2 and add no HBM traffic, with period == n they are two more streams.
+// ---------------------------------------------------------------------------------------
+template <typename T, int NK, int VW, int VPT, bool WRITE, int ST, bool INF>
+__device__ __forceinline__ double vtol_thread_part(const T *x0, const ErrArgs<T, NK> &a, T *unew_out, const double *__restrict__ vatol,
+                                                   const double *__restrict__ vrtol, int64_t period, int64_t nvec, int64_t n) {
+  // x0 / unew_out carry no __restrict__ (the caller may update a state in place); every thread loads all its
+  // elements before it stores any.
+  using V = Vec<T, VW>;
+  const int64_t base = (int64_t)blockIdx.x * (kBlock * VPT) + threadIdx.x;
+  const uint64_t per = (uint64_t)period;
+  const uint64_t hop = (uint64_t)(kBlock * VW) % per;
+  uint64_t r = (uint64_t)(base * VW) % per;
+  V ru[VPT], rk[VPT][NK];
+  double ta[VPT][VW], tr[VPT][VW];
+#pragma unroll
+  for (int p = 0; p < VPT; ++p) {
+    const int64_t i = base + (int64_t)p * kBlock;
+    if (i < nvec) {
+      ru[p] = reinterpret_cast<const V *>(x0)[i];
+#pragma unroll
+      for (int j = 0; j < NK; ++j) rk[p][j] = reinterpret_cast<const V *>(a.k[j])[i];
+      uint64_t q = r;
+#pragma unroll
+      for (int e = 0; e < VW; ++e) {
+        ta[p][e] = vatol[q];
+        tr[p][e] = vrtol[q];
+        if (++q == per) q = 0;
+      }
+    }
+    r += hop;
+    if (r >= per) r -= per;
+  }
+  double acc = 0;
+#pragma unroll
+  for (int p = 0; p < VPT; ++p) {
+    const int64_t i = base + (int64_t)p * kBlock;
+    if (i < nvec) {
+      V o;
+#pragma unroll
+      for (int e = 0; e < VW; ++e) {
+        T un = ru[p][e], er = (T)0;
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+          if (WRITE) un = fma(a.cb[j], rk[p][j][e], un);
+          er = fma(a.ce[j], rk[p][j][e], er);
+        }
+        o[e] = un;
+        if (INF) acc = nan_max(acc, winf_term<T>(un, er, ta[p][e], tr[p][e]));
+        else acc += wrms_term<T>(un, er, ta[p][e], tr[p][e]);
+      }
+      if (WRITE) pn_store<ST>(reinterpret_cast<V *>(unew_out) + i, o);
+    }
+  }
+  if (VW > 1 && blockIdx.x == 0) {
+    const int64_t i = nvec * VW + threadIdx.x;
+    if (i < n) {
+      uint64_t q = (uint64_t)(nvec * VW) % per + threadIdx.x;     // fewer than VW elements: at most VW - 1 wraps
+      while (q >= per) q -= per;
+      T un = x0[i], er = (T)0;
+#pragma unroll
+      for (int j = 0; j < NK; ++j) {
+        if (WRITE) un = fma(a.cb[j], a.k[j][i], un);
+        er = fma(a.ce[j], a.k[j][i], er);
+      }
+      if (WRITE) unew_out[i] = un;
+      if (INF) acc = nan_max(acc, winf_term<T>(un, er, vatol[q], vrtol[q]));
+      else acc += wrms_term<T>(un, er, vatol[q], vrtol[q]);
+    }
+  }
+  return acc;
+}
+
+template <typename T, int NK, int VW, int VPT, bool WRITE, int ST, int FIN>
+__global__ __launch_bounds__(kBlock) void pn_combine_wrms_v_kernel(const T *x0, ErrArgs<T, NK> a, T *unew_out, const double *vatol,
+                                                                   const double *vrtol, int64_t period, double *__restrict__ work,
+                                                                   int64_t nvec, int64_t n, double inv_n, double *result) {
+  const double s = block_sum(vtol_thread_part<T, NK, VW, VPT, WRITE, ST, false>(x0, a, unew_out, vatol, vrtol, period, nvec, n));
+  if (FIN == 0) {
+    if (threadIdx.x == 0) {
+      result[1 + blockIdx.x] = s;
+      if (blockIdx.x == 0) result[0] = (double)gridDim.x;
+    }
+    return;
+  }
+  double *partial = work + kTicketDoubles;       // pn_combine_wrms_kernel's in-launch finish (PN_TUNE "wfin=1")
+  if (threadIdx.x == 0) publish_partial(partial + blockIdx.x, s);
+  if (draw_ticket(work, gridDim.x, blockIdx.x)) {
+    const double tot = ordered_sum(partial, (int)gridDim.x);
+    if (threadIdx.x == 0) {
+      result[0] = 0.0;
+      result[1] = sqrt(tot * inv_n);
+    }
+  }
+}
+
+template <typename T, int NK, int VW, int VPT, bool WRITE, int ST>
+__global__ __launch_bounds__(kBlock) void pn_combine_winf_v_kernel(const T *x0, ErrArgs<T, NK> a, T *unew_out, const double *vatol,
+                                                                   const double *vrtol, int64_t period, int64_t nvec, int64_t n,
+                                                                   double *result) {
+  const double m = block_max(vtol_thread_part<T, NK, VW, VPT, WRITE, ST, true>(x0, a, unew_out, vatol, vrtol, period, nvec, n));
+  if (threadIdx.x == 0) {
+    result[1 + blockIdx.x] = m;
+    if (blockIdx.x == 0) result[0] = (double)gridDim.x;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // result[j] = <x, y_j>, j < NK: per-thread double partials -> wave shuffle -> LDS -> one double
 // per (block, j); a one-block kernel sums the block partials in index order.
 // ---------------------------------------------------------------------------------------
@@ -857,6 +973,74 @@ int launch_wrms(hipStream_t st, int64_t n, int nk, void *unew, const void *u, co
   return pn::or_fail(rc, "combine_wrms: between 1 and 7 stage derivatives supported");
 }
 
+// launch_wrms_n with the period vectors: the same alignment rule, vectors per thread, grid, store policy and finish
+template <typename T, int NK, bool WRITE, bool INF>
+int launch_wrms_v_n(hipStream_t st, int64_t n, void *unew, const void *u, const void *const *K, const double *cb,
+                    const double *ce, const double *vatol, const double *vrtol, int64_t period, double *work, double *result) {
+  ErrArgs<T, NK> a;
+  const bool al = pn::aligned16(u, unew) && pn::aligned16(K, NK);
+  for (int j = 0; j < NK; ++j) {
+    a.k[j] = (const T *)K[j];
+    a.cb[j] = (T)(cb ? cb[j] : 0.0);
+    a.ce[j] = (T)ce[j];
+  }
+  // the period vectors are read once from HBM (period == n: as two more streams), then from the caches
+  const double bytes = (double)n * sizeof(T) * (NK + 1 + (WRITE ? 1 : 0)) + 2.0 * (double)period * sizeof(double);
+  const double inv_n = 1.0 / (double)n;
+  if (al) {
+    constexpr int VW = vec_width<T>();
+    const int64_t nvec = n / VW;
+    const int vpt = pick_vpt_wrms(nvec), stp = tune().st[PN_K_COMBINE_WRMS] != 0 ? 1 : 0;
+    const int nblocks = (int)pn::blocks_for(nvec, (int64_t)kBlock * vpt);
+    if constexpr (INF) {
+#define PN_WGEO(V, S)                                                                                                   \
+  if (vpt == V && stp == S)                                                                                             \
+    return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_winf_v_kernel<T, NK, VW, V, WRITE, S>, dim3(nblocks), dim3(kBlock), st, \
+                      (const T *)u, a, (T *)unew, vatol, vrtol, period, nvec, n, result);
+      PN_WGEO(1, 0) PN_WGEO(1, 1) PN_WGEO(2, 0) PN_WGEO(2, 1) PN_WGEO(4, 0) PN_WGEO(4, 1)
+#undef PN_WGEO
+      return pn::fail("PN_TUNE: wvpt must be 1, 2 or 4");
+    }
+    const int fin = tune().wfin != 0 ? 1 : 0;
+#define PN_WGEO(V, S, F)                                                                                                \
+  if (vpt == V && stp == S && fin == F)                                                                                 \
+    return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_wrms_v_kernel<T, NK, VW, V, WRITE, S, F>, dim3(nblocks), dim3(kBlock), st, \
+                      (const T *)u, a, (T *)unew, vatol, vrtol, period, work, nvec, n, inv_n, result);
+    PN_WGEO(1, 0, 0) PN_WGEO(1, 1, 0) PN_WGEO(2, 0, 0) PN_WGEO(2, 1, 0) PN_WGEO(4, 0, 0) PN_WGEO(4, 1, 0)
+    PN_WGEO(1, 1, 1) PN_WGEO(2, 1, 1) PN_WGEO(4, 1, 1)
+#undef PN_WGEO
+    return pn::fail("PN_TUNE: wvpt must be 1, 2 or 4 (wfin=1 needs the default store policy)");
+  }
+  if constexpr (INF)
+    return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_winf_v_kernel<T, NK, 1, 1, WRITE, 0>, dim3((unsigned)pn::blocks_for(n, kBlock)),
+                      dim3(kBlock), st, (const T *)u, a, (T *)unew, vatol, vrtol, period, n, n, result);
+  return pn::launch(PN_K_COMBINE_WRMS, bytes, pn_combine_wrms_v_kernel<T, NK, 1, 1, WRITE, 0, 0>, dim3((unsigned)pn::blocks_for(n, kBlock)),
+                    dim3(kBlock), st, (const T *)u, a, (T *)unew, vatol, vrtol, period, work, n, n, inv_n, result);
+}
+
+template <bool INF>
+int combine_v(const char *name, void *stream, int dtype, int64_t n, void *unew, const void *u, int nk, const void *const *K,
+              const double *coef_b, const double *coef_e, const double *vatol, const double *vrtol, int64_t period, void *work,
+              double *result_dev) {
+  const std::string who(name);
+  if (n <= 0) return pn::fail(who + ": empty vector");
+  if (!work || !result_dev) return pn::fail(who + ": work/result buffers required");
+  if (!vatol || !vrtol) return pn::fail(who + ": the tolerance vectors are required (two scalars: the entry point without _v)");
+  if (period < 1 || period > n || n % period != 0) return pn::fail(who + ": the period must divide n (1 <= period <= n)");
+  hipStream_t st = (hipStream_t)stream;
+  double *w = (double *)work;
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const int r2 = pn::with_count<1, PN_MAX_STAGES>(nk, [&](auto N) {
+      constexpr int NK = decltype(N)::value;
+      return unew ? launch_wrms_v_n<T, NK, true, INF>(st, n, unew, u, K, coef_b, coef_e, vatol, vrtol, period, w, result_dev)
+                  : launch_wrms_v_n<T, NK, false, INF>(st, n, nullptr, u, K, nullptr, coef_e, vatol, vrtol, period, w, result_dev);
+    });
+    return pn::or_fail(r2, "combine_wrms: between 1 and 7 stage derivatives supported");
+  });
+  return pn::or_fail(rc, kBadDtype);
+}
+
 template <typename T, int NK>
 int launch_dots_n(hipStream_t st, int64_t n, const void *x, const void *const *y, double *work, double *result) {
   DotArgs<T, NK> a;
@@ -1076,6 +1260,18 @@ int pn_rk_combine_winf(void *stream, int dtype, int64_t n, void *unew, const voi
                 : launch_wrms<T, false, true>(st, n, nk, nullptr, u, K, nullptr, coef_e, atol, rtol, w, result_dev);
   });
   return pn::or_fail(rc, kBadDtype);
+}
+
+int pn_rk_combine_wrms_v(void *stream, int dtype, int64_t n, void *unew, const void *u, int nk, const void *const *K,
+                         const double *coef_b, const double *coef_e, const double *vatol, const double *vrtol, int64_t period,
+                         void *work, double *result_dev) {
+  return combine_v<false>("pn_rk_combine_wrms_v", stream, dtype, n, unew, u, nk, K, coef_b, coef_e, vatol, vrtol, period, work, result_dev);
+}
+
+int pn_rk_combine_winf_v(void *stream, int dtype, int64_t n, void *unew, const void *u, int nk, const void *const *K,
+                         const double *coef_b, const double *coef_e, const double *vatol, const double *vrtol, int64_t period,
+                         void *work, double *result_dev) {
+  return combine_v<true>("pn_rk_combine_winf_v", stream, dtype, n, unew, u, nk, K, coef_b, coef_e, vatol, vrtol, period, work, result_dev);
 }
 
 int pn_pinned_scalar(double **host_ptr, double **dev_ptr) {

@@ -297,6 +297,91 @@ __global__ __launch_bounds__(kBlock) void pn_rows_combine_winf_kernel(RowsErrArg
   }
 }
 
+// Per-component tolerances (pn_rows_combine_wrms_v / pn_rows_combine_winf_v): the two kernels above with column c's term formed
+// from vatol[c], vrtol[c] -- the period is the row, so the entry is the element's column and no remainder is taken.  The same
+// rows per workgroup, chunks, update and err chains, stores, dead rows, trees and finishes, and the same wrms_term / winf_term:
+// vectors filled with one value give those kernels' bits.  The 2 d doubles are re-read by every row from L1 / L2.  (A text of
+// its own, so that the scalar kernels' code stays what it was; INF picks the norm.)
+template <typename T>
+struct RowsErrVArgs {
+  T *unew;
+  const T *u;
+  const T *k[PN_MAX_STAGES];
+  double cb[PN_MAX_STAGES], ce[PN_MAX_STAGES];
+  const double *h;
+  double *enorm;
+  const double *vatol, *vrtol;   // d entries each
+};
+
+template <typename T, int NK, bool VEC, bool WRITE, bool INF>
+__global__ __launch_bounds__(kBlock) void pn_rows_combine_v_kernel(RowsErrVArgs<T> a, RowsGeom q) {
+  constexpr int VW = 16 / sizeof(T);
+  __shared__ double lds[kBlock / kWave];
+  const int G = 1 << q.lgG, g = threadIdx.x & (G - 1), sub = threadIdx.x >> q.lgG, rpb = kBlock >> q.lgG;
+  for (int64_t r0 = (int64_t)blockIdx.x * rpb; r0 < q.B; r0 += (int64_t)gridDim.x * rpb) {
+    const int64_t r = r0 + sub;
+    const bool live = r < q.B;
+    double sum = 0;
+    if (live) {
+      const double h = a.h[r];
+      T cb[NK], ce[NK];
+#pragma unroll
+      for (int j = 0; j < NK; ++j) {
+        cb[j] = (T)(h * a.cb[j]);
+        ce[j] = (T)(h * a.ce[j]);
+      }
+      const int64_t off = r * q.d;
+      for (int64_t ch = g; ch < q.nch; ch += G) {
+        T u[VW], k[NK][VW], o[VW];
+        double ta[VW], tr[VW];
+        load_chunk<T, VEC>(a.u + off, ch, q.d, u);
+#pragma unroll
+        for (int j = 0; j < NK; ++j) load_chunk<T, VEC>(a.k[j] + off, ch, q.d, k[j]);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+          const int64_t c = ch * VW + e;
+          const bool in = VEC || c < q.d;
+          ta[e] = in ? a.vatol[c] : 1.0;
+          tr[e] = in ? a.vrtol[c] : 0.0;
+        }
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+          T un = u[e], er = (T)0;
+#pragma unroll
+          for (int j = 0; j < NK; ++j) {
+            if (WRITE) un = fma(cb[j], k[j][e], un);
+            er = fma(ce[j], k[j][e], er);
+          }
+          o[e] = un;
+          if (VEC || ch * VW + e < q.d) {
+            if (INF) sum = nan_max(sum, winf_term<T>(un, er, ta[e], tr[e]));
+            else sum += wrms_term<T>(un, er, ta[e], tr[e]);
+          }
+        }
+        if (WRITE) store_chunk<T, VEC>(a.unew + off, ch, q.d, o);
+      }
+    }
+    if (G <= kWave) {
+      for (int o = G >> 1; o > 0; o >>= 1) {
+        const double other = __shfl_down(sum, o, G);
+        sum = INF ? nan_max(sum, other) : sum + other;
+      }
+    } else {
+      sum = INF ? wave_max(sum) : wave_sum(sum);
+      const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+      if (lane == 0) lds[wid] = sum;
+      __syncthreads();
+      if (g == 0) {
+        const int w0 = sub * (G / kWave);
+        sum = 0;
+        for (int w = 0; w < G / kWave; ++w) sum = INF ? nan_max(sum, lds[w0 + w]) : sum + lds[w0 + w];
+      }
+      __syncthreads();
+    }
+    if (live && g == 0) a.enorm[r] = INF ? sum : sqrt(sum / (double)q.d);
+  }
+}
+
 // unext[r] = accept[r] ? unew[r] : u[r];  sol[hit[r]][r] = unew[r] where hit[r] >= 0
 template <typename T, bool VEC>
 __global__ __launch_bounds__(kBlock) void pn_rows_commit_kernel(RowsCommitArgs<T> a, RowsGeom q) {
@@ -887,6 +972,32 @@ int rows_combine(hipStream_t st, int64_t B, int64_t d, void *unew, const void *u
   return pn::or_fail(rc, "pn_rows_combine_wrms: nk out of range");
 }
 
+// rows_combine with the period vectors (d entries each); booked under the error-norm kernels' id like pn_rows_combine_winf
+template <typename T, bool INF>
+int rows_combine_v(const char *name, hipStream_t st, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K,
+                   const double *cb, const double *ce, const double *h, const double *vatol, const double *vrtol, double *enorm) {
+  RowsErrVArgs<T> a = {};
+  a.unew = (T *)unew;
+  a.u = (const T *)u;
+  a.h = h;
+  a.enorm = enorm;
+  a.vatol = vatol;
+  a.vrtol = vrtol;
+  for (int j = 0; j < nk; ++j) {
+    a.k[j] = (const T *)K[j];
+    a.cb[j] = cb ? cb[j] : 0.0;
+    a.ce[j] = ce[j];
+  }
+  const bool al = pn::aligned16(u, unew) && pn::aligned16(K, nk);
+  const double bytes = (double)B * (double)d * sizeof(T) * (nk + 1 + (unew ? 1 : 0)) + 2.0 * (double)d * sizeof(double);
+  const int rc = rows_launch<T, 1, PN_MAX_STAGES>(name, st, B, d, al, nk, a, [&](auto N, auto V) {
+    constexpr int NK = decltype(N)::value;
+    constexpr bool VEC = decltype(V)::value;
+    return unew ? pn_rows_combine_v_kernel<T, NK, VEC, true, INF> : pn_rows_combine_v_kernel<T, NK, VEC, false, INF>;
+  }, PN_K_COMBINE_WRMS, bytes);
+  return pn::or_fail(rc, (std::string(name) + ": nk out of range").c_str());
+}
+
 template <typename T>
 int rows_commit(hipStream_t st, int64_t B, int64_t d, void *unext, const void *u, const void *unew, const int32_t *accept,
                 const int32_t *hit, void *sol, int64_t ld, int nout) {
@@ -1061,6 +1172,25 @@ int rows_adj_theta(const char *name, void *stream, int dtype, int64_t B, int64_t
   return rc == pn::kNoCase ? pn::fail(std::string(name) + ": unknown dtype") : rc;
 }
 
+template <bool INF>
+int rows_combine_v_entry(const char *name, void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk,
+                         const void *const *K, const double *coef_b, const double *coef_e, const double *h, const double *vatol,
+                         const double *vrtol, int64_t period, double *enorm) {
+  if (bad_shape(name, B, d)) return 1;
+  const std::string who(name);
+  if (!u || !h || !enorm || nk < 1 || nk > PN_MAX_STAGES || !K || !coef_e || (unew && !coef_b))
+    return pn::fail(who + ": null argument or nk outside 1..7");
+  if (!vatol || !vrtol) return pn::fail(who + ": the tolerance vectors are required (two scalars: the entry point without _v)");
+  if (period != d) return pn::fail(who + ": the period must be d (one entry per column; the rows share the vectors)");
+  for (int j = 0; j < nk; ++j)
+    if (!K[j]) return pn::fail(who + ": null stage derivative");
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pn::with_dtype(dtype, [&](auto t) {
+    return rows_combine_v<decltype(t), INF>(name, st, B, d, unew, u, nk, K, coef_b, coef_e, h, vatol, vrtol, enorm);
+  });
+  return pn::or_fail(rc, (who + ": unknown dtype").c_str());
+}
+
 }  // namespace
 
 extern "C" {
@@ -1098,6 +1228,18 @@ int pn_rows_combine_winf(void *stream, int dtype, int64_t B, int64_t d, void *un
   hipStream_t st = (hipStream_t)stream;
   const int rc = pn::with_dtype(dtype, [&](auto t) { return rows_combine<decltype(t), true>(st, B, d, unew, u, nk, K, coef_b, coef_e, h, atol, rtol, enorm); });
   return pn::or_fail(rc, "pn_rows_combine_winf: unknown dtype");
+}
+
+int pn_rows_combine_wrms_v(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K,
+                           const double *coef_b, const double *coef_e, const double *h, const double *vatol, const double *vrtol,
+                           int64_t period, double *enorm) {
+  return rows_combine_v_entry<false>("pn_rows_combine_wrms_v", stream, dtype, B, d, unew, u, nk, K, coef_b, coef_e, h, vatol, vrtol, period, enorm);
+}
+
+int pn_rows_combine_winf_v(void *stream, int dtype, int64_t B, int64_t d, void *unew, const void *u, int nk, const void *const *K,
+                           const double *coef_b, const double *coef_e, const double *h, const double *vatol, const double *vrtol,
+                           int64_t period, double *enorm) {
+  return rows_combine_v_entry<true>("pn_rows_combine_winf_v", stream, dtype, B, d, unew, u, nk, K, coef_b, coef_e, h, vatol, vrtol, period, enorm);
 }
 
 int64_t pn_rows_work_bytes(int64_t B) {

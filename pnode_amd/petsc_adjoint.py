@@ -483,6 +483,7 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs, ErrorNorm):
         check(self._lib.pn_ts_get_tolerances(self._ts, ctypes.byref(a), ctypes.byref(r)))
         self._atol, self._rtol = a.value, r.value
         self._errnorm_from_options()          # -ts_adapt_wnormtype: which norm, and whether the backend has it
+        self._tol_apply()                     # what setTolerances asked for holds across set-ups (PnError where it no longer fits)
         # budgeted checkpoints with -ts_trajectory_solution_only 0: a checkpoint holds the stage values
         # of its step as well (PETSc's checkpoints do), so reversing a checkpointed step recomputes nothing
         self._budget_stages = self._max_cps > 0 and not self._solution_only
@@ -573,6 +574,7 @@ class ODEPetsc(RowSweep, RKSweep, SweepGraphs, ErrorNorm):
                                  else "none (fixed steps)",
                                  "; final time matched exactly (MATCHSTEP)"))
         print("  state: %s %s on %s;  trainable parameters: %d" % (tuple(self.tensor_size), str(self.tensor_dtype).replace("torch.", ""), self.device, self.np))
+        print("  tolerances: %s" % self.tolerances)
         print("  launches: %s;  step loop: %s" % (self._graph_status, "C++ (pn_rk_attempt / pn_rk_adjoint_step)" if self._native else "Python"))
         print("  output times: %s" % ("interpolate (continuous extension of order %d; the steps are those of the end points alone)"
                                       % self._dense_order if self._dense else "match (a step ends on every output time)"))
